@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Benchmark of the batched control cycle (BASELINE.json metric: 7-DOF IK cycles/s at batch 65 536).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: this process starts the N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                             (N > 1: this process starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,15 +13,21 @@ this with 8 ranks, so scaling is weak and there is no collective on the data pat
 
 Timing (median and p10/p90): the timed region -- barrier, synchronize, stamp, EXACTLY K
 launches, synchronize, stamp -- is repeated R times (--reps); the collective that takes the maximum over
-ranks runs after the last repetition, outside every stamped interval.  `value` comes from the MEDIAN
-repetition; p10/p90 are printed next to it.  R further repetitions, interleaved with those, bracket the same K
-launches with HIP events on the launch stream and give the kernel's launch period for `roofline`.
+ranks runs after the last repetition, outside every stamped interval.  `value` and `ms_per_step` come from
+the MEDIAN repetition.  A plain run has R = 1: it sets up, warms up, times exactly K steps, writes the
+outputs of the last one (--dump-outputs) and prints its line -- nothing else.
 
-Rank 0 prints one JSON line.  `roofline` prices the kernel against HBM with the ALGORITHMIC bytes of
-SURVEY 8d (384 B per cycle at C3); `cpu_baseline` (N = 1 only) times the CPU oracle (oracle/, the build's
-port of the reference loop -- the reference itself cannot run) on this box's host cores, BEFORE
-this process touches the GPU: the reference-style per-arm NumPy loop as one process per core over disjoint
-arm slices (kind "port"), and the C/OpenMP port as `best_cpu`.
+--full (R = 30 unless --reps says otherwise) adds everything beyond the headline: p10/p90 of the R
+repetitions; R further repetitions, interleaved with those, that bracket the same K launches with HIP
+events on the launch stream and give the kernel's launch period for `roofline`; the cold state, the
+secondary scenes, the rollout and host-path rates; and the accuracy check against the CPU oracle
+(`max_abs_err_rad_s`).  `roofline` prices the kernel against HBM with the ALGORITHMIC bytes of SURVEY 8d
+(384 B per cycle at C3); `cpu_baseline` (N = 1 only) times the CPU oracle (oracle/, the build's port of the
+reference loop -- the reference itself cannot run) on this box's host cores, BEFORE this process
+touches the GPU: the reference-style per-arm NumPy loop as one process per core over disjoint arm slices
+(kind "port"), and the C/OpenMP port as `best_cpu`.
+
+Rank 0 prints one JSON line.
 """
 import argparse
 import json
@@ -57,6 +64,10 @@ WORKLOADS = {
 }
 
 MIB = 1 << 20
+# launches per captured hipGraph: a region of more launches replays graphs of this many (capturing and instantiating a graph of
+# 10^5-10^6 kernel nodes would cost the run more than the region itself); also the length of the warm-up trial of --launch auto
+GRAPH_CHUNK = 1000
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all (a fixed, seeded sample of arms beyond it)
 
 
 def host_cores(cap=16):
@@ -184,19 +195,40 @@ def pctl(xs, p):
     return xs[lo] + (xs[hi] - xs[lo]) * (k - lo)
 
 
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: (B, ...) array} as <directory>/<name>.npy: floating outputs in their own precision, integer ones (status) as
+    float64, which holds them exactly.  Above `limit` bytes in all, every array keeps the same fixed, seeded sample of rows."""
+    out = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > limit:
+        B = next(iter(out.values())).shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(B, int(B * limit // total), replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(out)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=30, help="repetitions of the timed region (K steps each); value = median repetition")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region (K steps each); value = median repetition "
+                    "(default: 1; 30 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: HIP-event repetitions and `roofline`, the cold state, the secondary "
+                         "scenes, the rollout and host-path rates, the CPU baseline and the accuracy check against the CPU oracle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0: qdot_out and the workload's other outputs) as DIR/<name>.npy")
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
-    ap.add_argument("--secondary", type=int, default=1, help="C3 at N = 1: also time the batch with per-arm (safe distance, force) pairs and with "
-                    "integer orders that differ (never `value`); 0: skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--secondary", type=int, default=1, help="--full, C3 at N = 1: also time the batch with per-arm (safe distance, force) pairs and "
+                    "with integer orders that differ (never `value`); 0: skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes / threads of the CPU baseline (0 = this box's CPU share, at most 16)")
-    ap.add_argument("--rollout", type=int, default=100, help="also time vfik_rollout with this many cycles per launch (0 = skip)")
-    ap.add_argument("--host-path", type=int, default=100, help="also time this many steps with q/qdot in host memory (0 = skip)")
+    ap.add_argument("--rollout", type=int, default=100, help="--full: also time vfik_rollout with this many cycles per launch (0 = skip)")
+    ap.add_argument("--host-path", type=int, default=100, help="--full: also time this many steps with q/qdot in host memory (0 = skip)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) is the real thing; gloo + --single-device rehearses the N>1 control flow on a 1-GPU box")
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -207,12 +239,14 @@ def parse_args(argv=None):
                          "two uses of a set exceed 640 MiB, at least 24; 0 = skip)")
     ap.add_argument("--state", default="both", choices=["both", "warm", "cold"],
                     help="both: `value` and `roofline` from back-to-back launches of ONE input set (cache-resident), `roofline.cold` from the "
-                         "rotating sets; cold: every launch of the run rotates (what a rocprofv3 trace of the cold state needs); warm: no rotation")
+                         "rotating sets (--full); cold: every launch of the run rotates (what a rocprofv3 trace of the cold state needs); "
+                         "warm: no rotation")
     ap.add_argument("--launch", default="auto", choices=["auto", "direct", "graph"],
-                    help="how the K launches of a timed region reach the GPU: direct = K vfik_step calls; graph = one replay of a hipGraph that "
-                         "captured those K vfik_step calls (the host then costs ~0.3 us per launch instead of 3-5); auto = whichever the warm-up "
-                         "measures faster on this box (graph only when it wins by > 3 %: it pays when the enqueue loop, not the GPU, sets the pace)")
-    ap.add_argument("--dump-reps", default=None, help="diagnostic: write the per-repetition times (us per launch, HIP events) to this file")
+                    help="how the K launches of a timed region reach the GPU: direct = K vfik_step calls; graph = replays of hipGraphs that "
+                         "captured those K vfik_step calls, at most %d to a graph (the host then costs ~0.3 us per launch instead of 3-5); "
+                         "auto = whichever the warm-up measures faster on this box (graph only when it wins by > 3 %%: it pays when the enqueue "
+                         "loop, not the GPU, sets the pace)" % GRAPH_CHUNK)
+    ap.add_argument("--dump-reps", default=None, help="diagnostic, --full: write the per-repetition times (us per launch, HIP events) to this file")
     ap.add_argument("--sync-each", action="store_true",
                     help="diagnostic: synchronize after every launch (un-overlapped kernel durations for a rocprofv3 kernel trace); "
                          "the line is then not a throughput measurement")
@@ -221,6 +255,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.reps is None:
+        args.reps = 30 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.reps < 1 or args.warmup < 0:
         raise SystemExit("--gpus, --steps, --reps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -248,7 +284,7 @@ def worker(args):
 
     # CPU baseline first, while this process has not initialised the GPU (rank 0 at N = 1 only)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cores = args.cpu_procs if args.cpu_procs > 0 else host_cores()
         cpu = numpy_loop_node_rate(chain, params, w, procs=cores)
         cpu["os_cpu_count"] = os.cpu_count()
@@ -380,7 +416,7 @@ def worker(args):
     # --kernel-trace --stats runs of this command): quoted beside the live HIP-event figure, never in place of it
     ktrace = None
     kt = os.path.join(ROOT, "profiles", "kernel_trace.json")
-    if os.path.exists(kt):
+    if args.full and os.path.exists(kt):
         try:
             ktrace = json.load(open(kt)).get(args.workload)
         except Exception:
@@ -390,15 +426,16 @@ def worker(args):
     # at 4 cycles each (wave64 on a 16-lane SIMD; float64 FMA is full rate on gfx950)
     sq = None
     sqf = os.path.join(ROOT, "profiles", "pmc_sq.json")
-    if os.path.exists(sqf):
+    if args.full and os.path.exists(sqf):
         try:
             sq = json.load(open(sqf)).get(args.workload)
         except Exception:
             sq = None
     # rotating input sets (the COLD state): enough of them that the bytes touched between two uses of a set exceed 640 MiB
+    # (built for `--state cold`, whose every launch rotates, and for `roofline.cold` of a --full run in `--state both`)
     per_launch = float(traffic) if traffic else float(bytes_per_cycle * B)
     n_sets = 0
-    if args.state != "warm" and args.rotate != 0:
+    if (args.state == "cold" or (args.state == "both" and args.full)) and args.rotate != 0:
         n_sets = args.rotate if args.rotate > 0 else max(24, int(640 * MIB / per_launch) + 2)
     sets = [(eng, io)]
     keep = [(q, outs0)]
@@ -420,32 +457,46 @@ def worker(args):
         return [float(x) for x in t.cpu()]
 
     def capture(active_sets, K):
-        """The K launches of a region as ONE hipGraph (torch.cuda.CUDAGraph captures the vfik_step calls on the launch stream)."""
+        """The K launches of a region as hipGraphs of at most GRAPH_CHUNK launches each (torch.cuda.CUDAGraph captures the vfik_step calls
+        on the launch stream); returns the function that replays them in order.  A chunk is a whole number of rounds over the sets, so
+        that launch i still goes to set i mod len(active_sets)."""
         ns = len(active_sets)
         steppers = [e_i.stepper(io_i) for e_i, io_i in active_sets]
-        g = torch.cuda.CUDAGraph()
-        # (thread-local capture mode: a collective library's watchdog thread querying its events must not invalidate the capture)
-        with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
-            for i in range(K):
-                steppers[i % ns]()
-        torch.cuda.synchronize()
-        return g
+        chunk = min(K, max(ns, GRAPH_CHUNK // ns * ns))
 
-    def timed(active_sets, K, R, wall=True, graph=None):
+        def one(n):
+            g = torch.cuda.CUDAGraph()
+            # (thread-local capture mode: a collective library's watchdog thread querying its events must not invalidate the capture)
+            with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
+                for i in range(n):
+                    steppers[i % ns]()
+            return g
+        g_chunk = one(chunk)
+        g_rest = one(K % chunk) if K % chunk else None
+        torch.cuda.synchronize()
+
+        def replay():
+            for _ in range(K // chunk):
+                g_chunk.replay()
+            if g_rest is not None:
+                g_rest.replay()
+        return replay
+
+    def timed(active_sets, K, R, wall=True, events=True, graph=None):
         """R repetitions of the timed region; returns (wall seconds per WALL repetition, enqueue seconds, HIP-event ms per EVENT
-        repetition).  Repetitions alternate between two kinds: WALL repetitions (even) carry nothing but the K launches between
-        the stamps and give `value`; EVENT repetitions (odd) bracket the same K launches with HIP events on the launch stream
-        and give the kernel's launch period for `roofline` (with one priming launch in front of the first event, so that all K
-        timed launches run back to back whatever K is).  (Recording two timing events costs a 20-launch region ~20 us --
-        1 us a step -- which is why they are kept out of the interval that `value` comes from.)  Launch i of a repetition
-        goes to input set i mod len(active_sets): one set = back-to-back launches over the same bytes (cache-resident),
-        many = every launch finds its inputs in HBM."""
+        repetition).  With `wall` and `events`, repetitions alternate between two kinds: WALL repetitions (even) carry nothing but
+        the K launches between the stamps and give `value`; EVENT repetitions (odd) bracket the same K launches with HIP events on
+        the launch stream and give the kernel's launch period for `roofline` (with one priming launch in front of the first event,
+        so that all K timed launches run back to back whatever K is).  One of the two alone: R repetitions of that kind.
+        (Recording two timing events costs a 20-launch region ~20 us -- 1 us a step -- which is why they are kept out of the
+        interval that `value` comes from.)  Launch i of a repetition goes to input set i mod len(active_sets): one set =
+        back-to-back launches over the same bytes (cache-resident), many = every launch finds its inputs in HBM."""
         ns = len(active_sets)
         steppers = [e_i.stepper(io_i) for e_i, io_i in active_sets]   # byref / prototype bound once: the hot enqueue
         steps = [steppers[i % ns] for i in range(K)]
         wall_s, ev_pairs, enqueue_s = [], [], []
-        for r in range(2 * R if wall else R):
-            with_events = (r % 2 == 1) or not wall
+        kinds = ([False, True] * R if events else [False] * R) if wall else [True] * R
+        for with_events in kinds:
             if with_events:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             barrier()                      # ranks start together; the barrier itself is NOT inside the interval
@@ -458,7 +509,7 @@ def worker(args):
                 steppers[(ns - 1) % ns]()
                 ev0.record(stream)
             if graph is not None:
-                graph.replay()
+                graph()
             elif args.sync_each:
                 for step in steps:
                     step()
@@ -488,26 +539,33 @@ def worker(args):
     graph, launch_note = None, "direct: K vfik_step calls per region"
     if args.launch != "direct" and not args.sync_each:
         g, why = None, ""
+        Kt = min(K, GRAPH_CHUNK)   # the trial's regions: the whole region when K is no longer than a captured graph
         try:
-            g = capture(primary, K)
+            g = capture(primary, Kt)
         except Exception as e:  # capture not possible on this stack: stay direct, say so
             why = str(e).splitlines()[0][:120] if str(e) else type(e).__name__
         # every rank takes the same path from here on (the trial regions carry barriers): graphs only if EVERY rank captured one
         all_ok = reduce_max([0.0 if g is not None else 1.0])[0] == 0.0
         if not all_ok:
             launch_note = "direct (graph capture failed%s)" % (": " + why if why else " on another rank")
-        elif args.launch == "graph":
-            graph = g
         else:
-            d_s, _, _ = timed(primary, K, 5)
-            g_s, _, _ = timed(primary, K, 5, graph=g)
-            picks = reduce_max([pctl(d_s, 50), pctl(g_s, 50)])   # one decision for all ranks: on the slowest rank's times
-            if picks[1] < 0.97 * picks[0]:
-                graph = g
-            launch_note += " (auto; warm-up trial, us per step: direct %.3f, graph %.3f)" % (picks[0] * 1e6 / K, picks[1] * 1e6 / K)
+            use = args.launch == "graph"
+            if not use:
+                d_s, _, _ = timed(primary, Kt, 5)
+                g_s, _, _ = timed(primary, Kt, 5, graph=g)
+                picks = reduce_max([pctl(d_s, 50), pctl(g_s, 50)])   # one decision for all ranks: on the slowest rank's times
+                use = picks[1] < 0.97 * picks[0]
+                launch_note += " (auto; warm-up trial, us per step: direct %.3f, graph %.3f)" % (picks[0] * 1e6 / Kt, picks[1] * 1e6 / Kt)
+            if use:
+                graph = g if Kt == K else capture(primary, K)
         if graph is not None:
-            launch_note = launch_note.replace("direct: K vfik_step calls per region", "hipGraph: one replay of K captured vfik_step launches per region")
-    wall_s, enqueue_s, ev_ms = timed(primary, K, R, graph=graph)
+            launch_note = launch_note.replace("direct: K vfik_step calls per region",
+                                              "hipGraph: K captured vfik_step launches per region, replayed as graphs of at most %d" % GRAPH_CHUNK)
+    wall_s, enqueue_s, ev_ms = timed(primary, K, R, events=args.full, graph=graph)
+    if args.dump_outputs and rank == 0:
+        # what the last timed launch wrote (launch K-1 of a region goes to set (K-1) mod the sets), fetched before any later launch
+        last = keep[(K - 1) % len(primary)][1]
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
     own_wall_s = list(wall_s)
     wall_s = reduce_max(wall_s)        # per repetition: the slowest rank
     per_rank_ms = None
@@ -545,7 +603,7 @@ def worker(args):
     # distance and force (compact image, 24 B a slot) and (b) with integer orders that differ by obstacle as in old/README.old:75
     # (order-20 obstacles beside an order-5 near-goal repeller: the order planes, MIXO kernel variants), warm, HIP events only.
     secondary = None
-    if world == 1 and args.workload == "C3" and args.secondary:
+    if args.full and world == 1 and args.workload == "C3" and args.secondary:
         secondary = {}
         rng2 = np.random.default_rng(77)
         variants = {}
@@ -580,7 +638,7 @@ def worker(args):
     # secondary figure (never `value`): closed-loop rollout, K control cycles per launch with q integrated in
     # registers -- what the cycle costs once the per-launch boundary is amortised
     rollout = None
-    if args.rollout > 0:
+    if args.full and args.rollout > 0:
         q_end = torch.empty_like(q)
         qd2 = torch.empty_like(qdot)
         io_r = eng.make_io(q, qdot_out=qd2)
@@ -602,7 +660,7 @@ def worker(args):
     # secondary figure (never `value`): the PCIe-inclusive rate when q and qdot live in HOST memory, as they do
     # for a host that talks to robots -- synchronous pageable copies vs the three-stream pipeline on pinned buffers
     host_path = None
-    if world == 1 and args.host_path > 0:
+    if args.full and world == 1 and args.host_path > 0:
         hq = eng.host_array((B, chain.n))
         hq[:] = w["q"].astype(io_dtype)
         houts = [{"qdot_out": eng.host_array((B, chain.n))} for _ in range(3)]
@@ -635,24 +693,8 @@ def worker(args):
         gathered = sharded[0].gather(src)   # sharding.collate: one all_gather over xGMI (RCCL), gloo in the rehearsal
 
     if rank == 0:
-        got = qdot.cpu().numpy().astype(np.float64)
-        from oracle import oracle_c  # checker only: accuracy half of the metric
-        ref = oracle_c.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], want=("qdot_out",))
-        max_err = float(np.abs(got - ref["qdot_out"]).max())
         med_s, p10_s, p90_s = pctl(wall_s, 50), pctl(wall_s, 10), pctl(wall_s, 90)
-        us_launch = [m * 1e3 / K for m in ev_ms]
-        us_med = pctl(us_launch, 50)
-        if args.dump_reps:
-            with open(args.dump_reps, "w") as f:
-                f.write("\n".join("%.4f %.4f" % (u, ws * 1e6 / K) for u, ws in zip(us_launch, wall_s)) + "\n")
-        achieved = bytes_per_cycle * B / (us_med * 1e-6) / 1e9
         total = world * B * K
-        if len(primary) > 1:
-            state_txt = ("cold: every launch of the run rotates over %d input sets (own handle, q and output buffers each), %.0f MiB touched "
-                         "between two uses of a set, against 256 MiB of Infinity Cache: inputs come from HBM" % (len(primary), (len(primary) - 1) * per_launch / MIB))
-        else:
-            state_txt = ("warm: back-to-back launches over ONE input set (%.1f MB), which stays in the 256 MiB Infinity Cache: this is "
-                         "the fraction of the HBM roofline at cache-resident inputs; `cold` = the same launches with inputs from HBM" % (per_launch / 1e6))
         line = {
             "metric": "7-DOF IK cycles/sec (whole node), batch=65536; max |qdot-qdot_ref|",
             "value": total / med_s,
@@ -675,20 +717,38 @@ def worker(args):
                             "ms_per_step_p10": p10_s * 1e3 / K, "ms_per_step_median": med_s * 1e3 / K, "ms_per_step_p90": p90_s * 1e3 / K,
                             "timed": "per repetition: barrier, synchronize, stamp, K launches, synchronize, stamp; max over ranks per repetition; "
                                      "no collective inside a stamped interval"},
-            "max_abs_err_rad_s": max_err,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-                         # which memory the launches of the timed region found their inputs in
-                         "state": state_txt,
-                         "real_bytes_frac": (traffic / (us_med * 1e-6) / 1e9 / HBM_PEAK_GBPS) if traffic else None,
-                         # <io type, joints, nullspace module, PLAIN, rollout, straight-line field path, LEAN>: the bench
-                         # workloads (revolute chain, identity tool, unit weights, integer-order repellers, qdot_out only)
-                         "kernel": kernel_name(io_name, chain.n, flags, B, eng.small_batch_launches > 0, bool(extra_outs), eng.uniform_repellers, eng.dh_pattern),
-                         "algorithmic_bytes_per_cycle": bytes_per_cycle,
-                         "us_per_launch_hip_events": us_med,
-                         "us_per_launch_p10": pctl(us_launch, 10), "us_per_launch_p90": pctl(us_launch, 90),
-                         "launches_timed": R * K, "timed": "R repetitions of K launches between two HIP events on the launch stream (one untimed priming launch in front of the first event), interleaved with the wall-clock repetitions"},
         }
+    if rank == 0 and args.full:
+        got = qdot.cpu().numpy().astype(np.float64)
+        from oracle import oracle_c  # checker only: accuracy half of the metric
+        ref = oracle_c.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], want=("qdot_out",))
+        max_err = float(np.abs(got - ref["qdot_out"]).max())
+        us_launch = [m * 1e3 / K for m in ev_ms]
+        us_med = pctl(us_launch, 50)
+        if args.dump_reps:
+            with open(args.dump_reps, "w") as f:
+                f.write("\n".join("%.4f %.4f" % (u, ws * 1e6 / K) for u, ws in zip(us_launch, wall_s)) + "\n")
+        achieved = bytes_per_cycle * B / (us_med * 1e-6) / 1e9
+        if len(primary) > 1:
+            state_txt = ("cold: every launch of the run rotates over %d input sets (own handle, q and output buffers each), %.0f MiB touched "
+                         "between two uses of a set, against 256 MiB of Infinity Cache: inputs come from HBM" % (len(primary), (len(primary) - 1) * per_launch / MIB))
+        else:
+            state_txt = ("warm: back-to-back launches over ONE input set (%.1f MB), which stays in the 256 MiB Infinity Cache: this is "
+                         "the fraction of the HBM roofline at cache-resident inputs; `cold` = the same launches with inputs from HBM" % (per_launch / 1e6))
+        line["max_abs_err_rad_s"] = max_err
+        line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                            "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+                            # which memory the launches of the timed region found their inputs in
+                            "state": state_txt,
+                            "real_bytes_frac": (traffic / (us_med * 1e-6) / 1e9 / HBM_PEAK_GBPS) if traffic else None,
+                            # <io type, joints, nullspace module, PLAIN, rollout, straight-line field path, LEAN>: the bench
+                            # workloads (revolute chain, identity tool, unit weights, integer-order repellers, qdot_out only)
+                            "kernel": kernel_name(io_name, chain.n, flags, B, eng.small_batch_launches > 0, bool(extra_outs), eng.uniform_repellers, eng.dh_pattern),
+                            "algorithmic_bytes_per_cycle": bytes_per_cycle,
+                            "us_per_launch_hip_events": us_med,
+                            "us_per_launch_p10": pctl(us_launch, 10), "us_per_launch_p90": pctl(us_launch, 90),
+                            "launches_timed": R * K, "timed": "R repetitions of K launches between two HIP events on the launch stream (one untimed priming launch in front of the first event), interleaved with the wall-clock repetitions"}
+    if rank == 0:
         if args.sync_each:
             line["diagnostic"] = "--sync-each: every launch was followed by a synchronize; not a throughput measurement"
         if sq and sq.get("SQ_INSTS_VALU"):

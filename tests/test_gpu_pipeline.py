@@ -179,7 +179,7 @@ def test_bench_two_ranks_fall_back_to_gloo_when_rccl_cannot_start():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--single-device", "--steps", "10", "--warmup", "3", "--reps", "3",
-                          "--no-cpu-baseline", "--rollout", "0", "--host-path", "0", "--state", "warm"], capture_output=True, text=True, timeout=300)
+                          "--full", "--no-cpu-baseline", "--rollout", "0", "--host-path", "0", "--state", "warm"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["value"] > 1e9

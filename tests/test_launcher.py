@@ -102,6 +102,38 @@ def test_percentiles():
     assert bench.pctl(xs, 50) == 6 and bench.pctl(xs, 10) == 2 and bench.pctl(xs, 90) == 10 and bench.pctl([7.0], 90) == 7.0
 
 
+def test_dump_outputs_float_files_and_a_fixed_sample_above_the_cap(tmp_path):
+    """--dump-outputs: one float32 / float64 .npy per output (integer status as float64, exactly); above the size cap every output
+    keeps the same seeded rows, so that two runs -- or two builds -- compare row for row."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"qdot_out": rng.standard_normal((1000, 7)).astype(np.float32), "status": rng.integers(0, 4, 1000).astype(np.int32)}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["qdot_out", "status"]
+    q, st = np.load(tmp_path / "all" / "qdot_out.npy"), np.load(tmp_path / "all" / "status.npy")
+    assert q.dtype == np.float32 and np.array_equal(q, arrays["qdot_out"])
+    assert st.dtype == np.float64 and np.array_equal(st, arrays["status"])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=8000)
+    qa, sa = np.load(tmp_path / "a" / "qdot_out.npy"), np.load(tmp_path / "a" / "status.npy")
+    assert 0 < qa.nbytes + sa.nbytes <= 8000 and qa.shape[1] == 7 and len(qa) == len(sa)
+    assert np.array_equal(qa, np.load(tmp_path / "b" / "qdot_out.npy")) and np.array_equal(sa, np.load(tmp_path / "b" / "status.npy"))
+    rows = [int(np.flatnonzero((arrays["qdot_out"] == r).all(axis=1))[0]) for r in qa]
+    assert rows == sorted(rows) and np.array_equal(sa, arrays["status"][rows])
+
+
+def test_plain_bench_runs_one_repetition_full_runs_thirty(monkeypatch):
+    """--steps K of a plain run is the number of timed steps: one repetition unless --reps says otherwise; --full keeps R = 30."""
+    sys.path.insert(0, ROOT)
+    import bench
+    seen = {}
+    monkeypatch.setattr(bench, "worker", lambda args: seen.setdefault(args.full, args.reps) and 0)
+    bench.main(["--steps", "7"])
+    bench.main(["--steps", "7", "--full"])
+    assert seen == {False: 1, True: 30}
+
+
 BIG_SCRIPT = textwrap.dedent("""
     import os, sys, time
     rank = int(os.environ["RANK"])

@@ -24,7 +24,7 @@ def run(lib, workload, state):
     env.pop("VFIK_HIP_LIB", None)
     if lib:
         env["VFIK_HIP_LIB"] = os.path.abspath(lib)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--no-cpu-baseline", "--host-path", "0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--full", "--no-cpu-baseline", "--host-path", "0",
                           "--rollout", "0", "--steps", "200", "--reps", "30", "--state", state, "--launch", "direct", "--secondary", "0"], env=env, capture_output=True, text=True, timeout=600)
     d = json.loads(out.stdout.strip().split("\n")[-1])
     return d["roofline"]["us_per_launch_p10"], d["max_abs_err_rad_s"]

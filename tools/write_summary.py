@@ -17,7 +17,7 @@ txt = """# %(R)s -- rocprofv3 summaries of the final round-%(rnd)d build (un-ins
 
 Produced by `tools/profile_round.sh %(tag)s <workloads>` (each command with `python3` directly after `--`), digested by
 `tools/profile_digest.py gpurun_out/%(tag)s %(rnd)d` and laid out by `tools/write_summary.py` (round-specific notes: last section).  Raw
-statistics: `%(R)s_kernel_stats_{warm,cold}_<W>.csv`; the bench lines: `%(R)s_bench_<W>.json` (plain runs: warm headline + `roofline.cold`),
+statistics: `%(R)s_kernel_stats_{warm,cold}_<W>.csv`; the bench lines: `%(R)s_bench_<W>.json` (`--full` runs: warm headline + `roofline.cold`),
 `%(R)s_bench_under_rocprofv3_{warm,cold}_<W>.json` (what the traced commands printed).
 
 ## States
@@ -25,10 +25,10 @@ statistics: `%(R)s_kernel_stats_{warm,cold}_<W>.csv`; the bench lines: `%(R)s_be
 * **warm** = `bench.py --state warm`: back-to-back launches over ONE input set, which never leaves the 256 MiB Infinity Cache: the fraction
   of the HBM roofline at cache-resident inputs (what a closed loop over one handle sees).
 * **cold** = `bench.py --state cold`: every launch of the run rotates over 24-42 independent input sets (own handle, q and output
-  buffers; >= 640 MiB touched between two uses of a set): inputs come from HBM.  The plain `bench.py` line carries both
+  buffers; >= 640 MiB touched between two uses of a set): inputs come from HBM.  The `bench.py --full` line carries both
   (`roofline.state`, `roofline.cold`).
 
-## Kernel trace: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload W --no-cpu-baseline --rollout 0 --host-path 0 --secondary 0 --launch graph --state {warm,cold}`
+## Kernel trace: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload W --full --no-cpu-baseline --rollout 0 --host-path 0 --secondary 0 --launch graph --state {warm,cold}`
 
 (12 020+ dispatches each: warm-up + 2 x 30 repetitions x 200 launches.  Algorithmic bytes per launch, SURVEY 8d: C2 512 B x 4 096,
 C3 / C3N 384 B x 65 536, C5 696 B x 65 536, C3F 600 B x 65 536, C5F 996 B x 65 536.  frac = algorithmic bytes / mean duration / 8 TB/s.)
