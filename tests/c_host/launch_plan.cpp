@@ -1,0 +1,102 @@
+// Prints the kernel each launch description takes under the launch plan (vfik_kernel.h: plan_cycle), with its grid, block and LDS bytes:
+// one line of `key=value` pairs per launch on stdin (KArgs members; pointers: 1 = given), one line per launch on stdout.  Host code only, no GPU:
+// built and run by tests/test_launch_plan.py.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <sstream>
+#include <string>
+
+#include "../../vfclik_amd/csrc/vfik_kernel.h"
+
+using vfik::CycleFamily;
+
+static const char* b(bool v) { return v ? "true" : "false"; }
+
+// the demangled name of the instantiation (template arguments in the order the kernels declare them)
+static std::string kernel_name(const vfik::CyclePlan& p, int nj, int io_bits, bool ns) {
+    const char* t = io_bits == 32 ? "float" : "double";
+    char s[256];
+    switch (p.family) {
+        case CycleFamily::Refused: return "refused";
+        case CycleFamily::Sub8:
+            std::snprintf(s, sizeof s, "cycle_sub8_kernel%s<%s, %d, %s, %d>", ns ? "" : "_x", t, nj, b(ns), p.dhp);
+            return s;
+        case CycleFamily::Mixo:
+            std::snprintf(s, sizeof s, "cycle_kernel_m<%s, %d, %s, %d, %s, %d>", t, nj, b(ns), p.lean, b(p.fun), p.dhp);
+            return s;
+        case CycleFamily::Lean:
+        case CycleFamily::LeanPersistent:
+        case CycleFamily::LeanTwoWaves:
+            std::snprintf(s, sizeof s, "cycle_kernel_s<%s, %d, %s, true, false, true, 1, %d, %s, %s, %d, %s, %d>", t, nj, b(ns), p.cf, b(p.pers), b(p.fun), p.waves,
+                          b(p.uni), p.dhp);
+            return s;
+        default:
+            std::snprintf(s, sizeof s, "cycle_kernel_x<%s, %d, %s, %s, %s, %s, %d, %d, %s, %s, %d, %s, false, %d>%s", t, nj, b(ns), b(p.plain), b(p.roll), b(p.fastf),
+                          p.lean, p.cf, b(p.pers), b(p.fun), p.waves, b(p.uni), p.dhp, p.heavy ? " [heavy]" : "");
+            return s;
+    }
+}
+
+int main() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        if (line.empty()) continue;
+        std::map<std::string, long> kv;
+        std::istringstream in(line);
+        std::string tok;
+        while (in >> tok) {
+            const size_t eq = tok.find('=');
+            kv[tok.substr(0, eq)] = std::strtol(tok.c_str() + eq + 1, nullptr, 0);
+        }
+        auto get = [&](const char* k, long d) { auto it = kv.find(k); return it == kv.end() ? d : it->second; };
+        auto ptr = [&](const char* k) { return get(k, 0) ? reinterpret_cast<void*>(0x1000) : nullptr; };
+        vfik::KArgs a;
+        std::memset(&a, 0, sizeof a);
+        const int nj = (int)get("nj", 7), io = (int)get("io", 32), block = (int)get("block", 256);
+        a.B = (int)get("B", 4096);
+        a.Bpad = (a.B + 63) / 64 * 64;
+        a.flags = (unsigned)get("flags", 0);
+        a.fast_order = (int)get("fast_order", 5);
+        a.slots_used = (int)get("slots_used", 6);
+        a.slots_used_fast = (int)get("slots_used_fast", 4);
+        a.tool_stride = get("tool", 0) ? a.Bpad : 0;
+        a.plain = (int)get("plain", 1);
+        a.dhp = (int)get("dhp", 0);
+        a.mixw = ptr("mixw");
+        a.wts = static_cast<const double*>(ptr("wts"));
+        a.ext = ptr("ext");
+        a.q_ref = ptr("q_ref");
+        a.q_cmded = ptr("q_cmded");
+        a.q_lo = ptr("q_lo");
+        a.q_hi = a.q_lo;
+        a.q_ref_out = ptr("q_ref_out");
+        a.null_control = ptr("null_control");
+        a.qdot_vf = ptr("qdot_vf");
+        a.qdot_null = ptr("qdot_null");
+        a.qdot_out = get("qdot_out", 1) ? reinterpret_cast<void*>(0x1000) : nullptr;
+        a.pose = ptr("pose");
+        a.pose_nt = ptr("pose_nt");
+        a.v6 = ptr("v6");
+        a.qdist = ptr("qdist");
+        a.goal_dist = ptr("goal_dist");
+        a.active = static_cast<const int*>(ptr("active"));
+        a.q_out = ptr("q_out");
+        a.n_cycles = (int)get("n_cycles", 0);
+        a.sub8_max_batch = (int)get("sub8", 0);
+        a.sub8_max_batch_ns = (int)get("sub8_ns", 0);
+        a.sub8_max_batch_full = (int)get("sub8_full", 4096);
+        a.n_simd = (int)get("n_simd", 1024);
+        a.has_funnel = (int)get("funnel", 0);
+        a.mixed = (int)get("mixed", 0);
+        a.uni = (int)get("uni", 0);
+        a.pers = (int)get("pers", 0);
+        a.waves2 = (int)get("waves2", 0);
+        const bool ns = a.flags & VFIK_F_NULLSPACE;
+        const vfik::CyclePlan p = vfik::plan_cycle(a, nj, io, ns, block);
+        std::printf("%s grid=%u block=%u lds=%zu\n", kernel_name(p, nj, io, ns).c_str(), p.grid, p.block, p.lds);
+    }
+    return 0;
+}

@@ -933,7 +933,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
     a.clamp = clamp ? 1 : 0;
     if (n_cycles > 0 && (io->track_error || io->obj_dist))
         return fail(VFIK_E_ARG, "io->track_error / io->obj_dist are per control cycle: vfik_step only, not a rollout");
-    if (n_cycles > 0 && (h->n > VFIK_ROLL_MAX_NJ || a.plain != 1)) {
+    if (n_cycles > 0 && !vfik::rollout_in_kernel(h->n, a.plain)) {
         // Long chains, and (round 4) chains with a tool, IK weights or prismatic joints, whose in-kernel loop spilled 12-268 B per
         // lane: the rollout is n_cycles single-cycle launches, each integrating q on its way out
         // (q ping-pongs between two device buffers; the caller's io->q is never written).  The kernel has

@@ -1,5 +1,6 @@
 // vfik_kernel.h -- kernel argument block shared by vfik_kernel.hip (device) and vfik_abi.cpp (host).
 #pragma once
+#include <algorithm>
 #include <cstddef>
 
 #include <hip/hip_runtime.h>
@@ -106,9 +107,45 @@ template <> struct DhPattern<6, 1> { static constexpr unsigned SWAP = 0x1Du, NON
 // the pattern id of a chain with these masks (0: none built for it)
 int dh_pattern_of(int nj, unsigned swap, unsigned none, unsigned d0, unsigned off0, unsigned offpi, bool base_identity);
 
+// Per-wave LDS region of the cycle kernel (vfik_kernel.hip, cycle_body), by I/O type T.
+template <typename T> struct Stage {
+    // Slots staged at a time (prefetch window / chunk size).  float64 I/O stages 4: with 8 the region is 56 KB
+    // and only three of a CU's four SIMDs get a wave (160 KB LDS) -- the launch then runs in two rounds
+    // (measured 15.3 us instead of ~8 for the C3 batch).
+    static constexpr int PRE = sizeof(T) == 8 ? 4 : 8;
+    static constexpr int Q16 = (int)sizeof(T) / 4;           // 16-B pieces per quad
+    static constexpr int QBYTES = 4 * (int)sizeof(T);        // bytes of one quad
+    static constexpr int QSTEP = Q16 * 1024;                 // LDS bytes of one staged quad (a 1-KiB row per 16 bytes per lane)
+    static constexpr int QPCF = 3 * PRE / 2;                 // quads of one chunk of the compact repeller image
+    // Region of one wave, in the order [goal 4 | slot quads 0 .. QPCF-1 | q | kinematics | table] -- that much is all a LEAN
+    // launch on the straight-line path touches (`lean_bytes`: 19.75 KB for 7 joints with float I/O, eight waves per CU) --
+    // then [slot quads QPCF .. 2 PRE - 1 | tool 3 | mixer weights 2] for the general path and the optional per-arm inputs.
+    static constexpr int GOAL_OFF = 0, SLOT_OFF = 4 * QSTEP, Q_OFF = (4 + QPCF) * QSTEP;
+    // q is batch-major ([B][n]): a lane's n values are contiguous and travel as 16-byte pieces plus a
+    // remainder of one to three 4-byte pieces (a 12-byte LDS-DMA did not land lane-linear on gfx950)
+    __host__ __device__ static constexpr int qbytes(int nj) { return nj * (int)sizeof(T); }
+    __host__ __device__ static constexpr int q16(int nj) { return qbytes(nj) / 16; }
+    __host__ __device__ static constexpr int qrem(int nj) { return qbytes(nj) % 16; }
+    __host__ __device__ static constexpr int qregion(int nj) { return q16(nj) * 1024 + qrem(nj) * 64; }
+    __host__ __device__ static constexpr int kin_rows(int nj) { return ((12 + 10 * nj + 4 + 10 + VFIK_MIX_CHANNELS + 12 + 6 + nj) * 8 + 1023) / 1024; }  // = KConst<nj>::KIN_ROWS
+    __host__ __device__ static constexpr int kin_off(int nj) { return Q_OFF + qregion(nj); }
+    __host__ __device__ static constexpr int tab_off(int nj) { return kin_off(nj) + kin_rows(nj) * 1024; }  // sin / cos table, 1 KiB
+    __host__ __device__ static constexpr int lean_bytes(int nj) { return tab_off(nj) + 1024; }
+    __host__ __device__ static constexpr int slot_off(int idx, int nj) {  // slot quad idx of the staged chunk
+        return idx < QPCF ? SLOT_OFF + idx * QSTEP : lean_bytes(nj) + (idx - QPCF) * QSTEP;
+    }
+    __host__ __device__ static constexpr int tool_off(int nj) { return lean_bytes(nj) + (2 * PRE - QPCF) * QSTEP; }
+    __host__ __device__ static constexpr int mixw_off(int nj) { return tool_off(nj) + 3 * QSTEP; }
+    __host__ __device__ static constexpr int bytes(int nj) { return mixw_off(nj) + 2 * QSTEP; }
+};
+
 // Chains longer than this have no registers left for loop-carried state: their rollout is a sequence of
 // single-cycle launches that integrate q on the way out (vfik_abi.cpp), not the ROLL kernel variant.
 #define VFIK_ROLL_MAX_NJ 7
+// Chains of VFIK_HEAVY_MIN_NJ joints or more: the non-lean single-cycle variants are an object of their own (-DVFIK_HEAVY_PART, Makefile)
+#ifndef VFIK_HEAVY_MIN_NJ
+#define VFIK_HEAVY_MIN_NJ 12
+#endif
 
 struct KArgs {
     int B;
@@ -194,6 +231,221 @@ struct KLean {
 size_t kconst_bytes(int nj);
 // fill a host image of KConst<nj> at dst
 double kconst_fill(int nj, void* dst, const vfik_chain& chain, const vfik_params& p, const double* tool12, int* plain, int* dhp = nullptr);
+
+// ------------------------------------------------------------------------------------------------
+// The launch plan of a control cycle: which kernel variant a launch takes, with which template arguments, grid, block and LDS.
+// Plain host code (no HIP call): vfik_kernel.hip's launcher maps a plan to its instantiation, tests/c_host/launch_plan.cpp prints it.
+// ------------------------------------------------------------------------------------------------
+enum class CycleFamily {
+    Refused,          // a rollout the kernels do not run in-kernel (rollout_in_kernel): the caller steps it (vfik_abi.cpp: launch_cycles)
+    Sub8,             // eight lanes per arm (cycle_sub8_kernel): small batches of the outputs the per-arm processes publish
+    Lean,             // q -> qdot_out on the straight-line field path (cycle_kernel_s, LEAN 1)
+    LeanPersistent,   // ... beyond one wave per SIMD: one wave per SIMD striding over the batch (PERS)
+    LeanTwoWaves,     // ... beyond one wave per SIMD: two waves per SIMD (WAVES 2)
+    PublishingLean,   // no per-arm option, the published rows at run time (cycle_kernel_x, LEAN 3)
+    Mixo,             // decay orders that differ, lean or publishing-lean (cycle_kernel_m)
+    Rollout,          // in-kernel rollout (ROLL, LEAN 0)
+    RolloutLean,      // in-kernel rollout of a lean launch (ROLL, LEAN 1)
+    SteppedCycle,     // one cycle of a host-stepped rollout of a long chain: lean, q integrated on the way out (LEAN 2)
+    GeneralLean,      // q -> qdot_out on the general field path (LEAN 1, FASTF 0)
+    Full,             // every other launch (LEAN 0); `heavy`: the long chains' object of its own
+};
+
+// the flag sets of the nullspace module in vfclik's default process set (nullspace + mixer; C5 adds the joint-limit task): the CF variants
+constexpr int CF_NSMIX = VFIK_F_NULLSPACE | VFIK_F_MIXER, CF_NSJLMIX = CF_NSMIX | VFIK_F_JOINT_LIMIT_TASK;
+
+struct CyclePlan {
+    CycleFamily family;
+    // the kernel's template arguments as compiled (cycle_kernel_s / _x / _m; Sub8: dhp alone)
+    bool plain, roll, fastf;
+    int lean;        // 0 general, 1 lean, 2 a stepped rollout's cycle, 3 publishing lean
+    int cf;          // the flag set as a compile-time constant, or -1
+    bool pers, fun;
+    int waves;
+    bool uni, mixo;
+    int dhp;         // DH-pattern bits the variant is built with (bit 0 pattern, bit 1 shared tool, bit 2 shared IK weights)
+    bool heavy;      // Full of a long chain: launch_heavy_nj<n>
+    unsigned grid, block;
+    size_t lds;
+    // kernel arguments the plan rewrites
+    int fast_order;  // -1: the general field path; UNI: the uniform image's offset in the upper bits
+    int slots_used;  // the straight-line path counts the slots of the compact image
+};
+
+// Whether an n_cycles > 0 launch runs as ONE in-kernel rollout (ROLL variants: PLAIN chains of up to 7 joints without shared options); else the
+// caller steps it cycle by cycle -- with a tool, IK weights or prismatic joints the loop-carried state no longer fits the registers.
+inline bool rollout_in_kernel(int nj, int plain) { return nj <= VFIK_ROLL_MAX_NJ && plain == 1; }
+
+inline bool has_dh_pattern(int nj) {
+    switch (nj) {
+#define X(n) case n: return DhPattern<n, 1>::SWAP != 0;
+        VFIK_NJ_LIST
+#undef X
+        default: return false;
+    }
+}
+
+// ---- what a launch asks for (KArgs), as the plan reads it
+// no per-arm option: tool, mixer weights, IK weights, extra mixer channels, joint controller, LWR command form, per-cycle limits
+inline bool no_per_arm_option(const KArgs& a) {
+    return !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded && !a.q_lo && !a.q_ref_out;
+}
+inline bool single_cycle(const KArgs& a) { return !a.q_out && a.n_cycles == 0; }
+// without the nullspace module a lean variant assumes no feature flag
+inline bool lean_flags(const KArgs& a, bool ns) { return ns || a.flags == 0; }
+// the rows the per-arm processes publish every cycle
+inline bool publishes_rows(const KArgs& a) { return a.qdot_vf || a.qdot_null || a.pose || a.pose_nt || a.qdist; }
+// nothing but q -> qdot_out (and status): no other input or output, whatever the field path (q_out may be a stepped rollout's)
+inline bool qdot_out_only(const KArgs& a, bool ns) {
+    return lean_flags(a, ns) && no_per_arm_option(a) && !publishes_rows(a) && !a.null_control && !a.v6 && !a.goal_dist && !a.active;
+}
+// the lean and publishing-lean single-cycle launches: the only ones with FUN and MIXO variants
+inline bool lean_single(const KArgs& a, bool ns) { return lean_flags(a, ns) && no_per_arm_option(a) && single_cycle(a); }
+// the launches the eight-lanes kernel serves (before the batch-size cap)
+inline bool sub8_served(const KArgs& a, bool ns) {
+    return no_per_arm_option(a) && single_cycle(a) && !a.active && !a.v6 && !a.goal_dist && a.qdot_out && (ns || (a.flags == 0 && !a.null_control));
+}
+
+namespace plan_detail {
+struct Sizes { size_t bytes, lean, kin, tool, qstep; };
+inline Sizes sizes(int io_bits, int nj) {
+    if (io_bits == 32) return {(size_t)Stage<float>::bytes(nj), (size_t)Stage<float>::lean_bytes(nj), (size_t)Stage<float>::kin_off(nj), (size_t)Stage<float>::tool_off(nj), (size_t)Stage<float>::QSTEP};
+    return {(size_t)Stage<double>::bytes(nj), (size_t)Stage<double>::lean_bytes(nj), (size_t)Stage<double>::kin_off(nj), (size_t)Stage<double>::tool_off(nj), (size_t)Stage<double>::QSTEP};
+}
+
+// The route of a plain (pl) or general launch.  `shared`: the PLAIN kernels with the batch's shared tool / IK weights in dhp's bits 1-2 --
+// only the eight-lanes kernel and the lean / publishing-lean float32 straight-line variants have those; false when none serves the launch.
+inline bool route(const KArgs& a, int nj, int io_bits, bool ns, bool pl, int dhp, bool shared, CyclePlan& p) {
+    const bool f32 = io_bits == 32;
+    const Sizes s = sizes(io_bits, nj);
+    // FASTF: the straight-line repeller path.  A funnel block (FUN) or decay orders that differ (MIXO) keep it only for the lean and
+    // publishing-lean single-cycle launches of PLAIN chains; every other launch of such a batch takes the general path.
+    bool fastf = a.fast_order >= 0, fun = false, mixo = false;
+    if (fastf && a.has_funnel) {
+        if (pl && lean_single(a, ns)) fun = true;
+        else fastf = false;
+    }
+    if (fastf && a.mixed) {
+        if (pl && lean_single(a, ns)) mixo = true;
+        else fastf = fun = false;
+    }
+    p.plain = pl;
+    p.fastf = fastf;
+    p.fun = fun;
+    p.fast_order = fastf ? a.fast_order : -1;
+    p.slots_used = fastf ? a.slots_used_fast : a.slots_used;
+    // the uniform repeller image (UNI): the lean single-cycle straight-line variants, when every decay repeller shares one safe distance and force
+    const bool uni = fastf && !fun && !mixo && a.uni;
+    const bool lean = pl && qdot_out_only(a, ns) && fastf;
+    const size_t waves = p.block / 64;
+    const size_t lds_full = p.lds;
+    // LEAN launches touch only the head of the region: they ask for no more while the launch is at most one wave per SIMD; beyond, the
+    // full size keeps it in rounds of one wave per SIMD (two waves per SIMD compete for the same HBM time; profiles/r02_batch_scaling.txt)
+    const size_t lds_lean = (long)p.grid * (long)waves <= (long)a.n_simd ? waves * s.lean : lds_full;
+    const size_t lds_fun = std::max(lds_lean, waves * (s.lean + 6 * s.qstep));   // + the aux block's six rows per wave
+    // the DH pattern a cycle_kernel variant is built with: the lean straight-line variants but the persistent one and
+    // the two-waves one on the compact image (it spilled with the pattern); float64 I/O: the pattern alone, for the 7-joint chain
+    auto use = [&](CycleFamily f, bool roll, int lean_v, size_t lds) {
+        p.family = f;
+        p.roll = roll;
+        p.lean = lean_v;
+        p.lds = lds;
+        const bool built = fastf && (roll ? lean_v == 1 : lean_v != 0) && !p.pers && !(p.waves == 2 && !p.uni);
+        p.dhp = built ? (f32 ? dhp : (nj == 7 ? (dhp & 1) : 0)) : 0;
+        return true;
+    };
+    // the nullspace module's two flag sets of the default process set, as compile-time constants (chains of up to 7 joints)
+    const int cf = (!shared && ns && nj <= 7 && (a.flags == (unsigned)CF_NSMIX || a.flags == (unsigned)CF_NSJLMIX)) ? (int)a.flags : -1;
+    if (pl && a.n_cycles > 0 && nj <= VFIK_ROLL_MAX_NJ)
+        return lean ? use(CycleFamily::RolloutLean, true, 1, lds_lean) : use(CycleFamily::Rollout, true, 0, lds_full);
+    // small batches: eight lanes per arm, where the same-box A/B wins (profiles/r03_latency_small_*.txt): launches that publish the rows at
+    // every size up to sub8_max_batch_full; qdot_out alone, with or without the nullspace module, up to its own cap
+    if (pl && nj <= (ns ? 7 : 8) && fastf && !fun && !mixo && sub8_served(a, ns) &&
+        a.B <= (publishes_rows(a) ? a.sub8_max_batch_full : (ns ? a.sub8_max_batch_ns : a.sub8_max_batch))) {
+        p.family = CycleFamily::Sub8;
+        p.dhp = dhp;
+        p.grid = (unsigned)((a.B + 7) / 8);
+        p.block = 64;
+        p.lds = 8 * 1024;
+        return true;
+    }
+    if (shared && !f32) return false;
+    if (mixo) {   // one wave per block; beyond one wave per SIMD the full region (rounds, as above); + one row for the order bytes
+        p.mixo = true;
+        p.grid = (unsigned)((a.B + 63) / 64);
+        p.block = 64;
+        size_t lds = (long)p.grid <= (long)a.n_simd ? s.lean : s.bytes;
+        if (fun) lds = std::max(lds, s.lean + 6 * s.qstep);
+        return use(CycleFamily::Mixo, false, qdot_out_only(a, ns) ? 1 : 3, lds + 1024);
+    }
+    // batches beyond one wave per SIMD: the persistent launch, one wave per SIMD striding over the 64-arm chunks (float I/O, up to 7 joints)
+    if (!shared && f32 && nj <= 7 && lean && !fun && single_cycle(a) && a.pers && (long)((a.B + 63) / 64) > (long)a.n_simd) {
+        p.pers = true;
+        const size_t lds = s.lean + s.kin;   // two per-arm areas
+        p.grid = (unsigned)a.n_simd;
+        p.block = 64;
+        return use(CycleFamily::LeanPersistent, false, 1, lds);
+    }
+    if (lean && !a.q_out) {
+        if (fun) return use(CycleFamily::Lean, false, 1, lds_fun);
+        // beyond one wave per SIMD: the two-waves-per-SIMD build (float I/O, up to 7 joints; with the nullspace module on the uniform image only --
+        // the compact-image variants of that build spilled)
+        if (!shared && f32 && nj <= 7 && a.waves2 && (long)p.grid * (long)waves > (long)a.n_simd && (!ns || uni)) {
+            p.waves = 2;
+            p.uni = uni;
+            p.cf = cf;
+            return use(CycleFamily::LeanTwoWaves, false, 1, waves * s.lean);
+        }
+        p.uni = uni;
+        p.cf = cf;
+        return use(CycleFamily::Lean, false, 1, lds_lean);
+    }
+    if (!shared && nj > VFIK_ROLL_MAX_NJ && lean) return use(CycleFamily::SteppedCycle, false, 2, lds_lean);   // (q_out: a stepped rollout's cycle)
+    if (pl && fastf && lean_single(a, ns)) {
+        if (fun) return use(CycleFamily::PublishingLean, false, 3, lds_fun);
+        p.uni = uni;
+        p.cf = cf;
+        return use(CycleFamily::PublishingLean, false, 3, lds_lean);
+    }
+    if (shared) return false;
+    if (pl && qdot_out_only(a, ns) && !fastf && !a.q_out) return use(CycleFamily::GeneralLean, false, 1, lds_full);
+    p.heavy = nj >= VFIK_HEAVY_MIN_NJ;
+    return use(CycleFamily::Full, false, 0, lds_full);
+}
+}  // namespace plan_detail
+
+// The plan of one launch of the cycle kernel: nj joints, io_bits 32 / 64, ns = the launch's flags carry VFIK_F_NULLSPACE, block = the
+// handle's threads per block.  The decisions are taken in this order, the first that applies wins.
+inline CyclePlan plan_cycle(const KArgs& a, int nj, int io_bits, bool ns, int block) {
+    CyclePlan p{};
+    p.family = CycleFamily::Refused;
+    p.cf = -1;
+    p.waves = 1;
+    // A full region that does not fit the CU four times (float64 I/O from 10 joints on: 42-44 KB) would leave one SIMD of every CU idle: such
+    // launches go as one wave per block, each block asking for the part of the region its options use -- the rows of a per-arm tool and of
+    // per-arm mixer weights are the region's tail (profiles/r04_heavy_variants.txt).  (VFIK_BLOCK: a block's waves must fit the CU's 160 KB.)
+    const plan_detail::Sizes s = plan_detail::sizes(io_bits, nj);
+    if (4 * s.bytes > 160u * 1024u) {
+        block = 64;
+        p.lds = (a.tool_stride || a.mixw) ? s.bytes : s.tool;
+    } else {
+        while (block > 64 && (size_t)(block / 64) * s.bytes > 160u * 1024u) block -= 64;
+        p.lds = (size_t)(block / 64) * s.bytes;
+    }
+    p.block = (unsigned)block;
+    p.grid = (unsigned)((a.B + block - 1) / block);
+    if (a.n_cycles > 0 && !rollout_in_kernel(nj, a.plain)) return p;
+    const int dhp = (a.plain && a.dhp == 1 && has_dh_pattern(nj)) ? 1 : 0;   // (the chain matches the pattern built for its joint count)
+    if (a.plain >= 2 && dhp == (has_dh_pattern(nj) ? 1 : 0)) {
+        // The batch's shared tool (a.plain - 1 bit 0) and / or IK weights other than one (bit 1, chains of up to 7 joints) on the PLAIN kernels;
+        // a launch none of their variants serves, or a chain off its pattern, takes the general variants
+        const int opt = a.plain - 1, bits = opt == 1 ? 2 : (nj <= 7 && opt == 2) ? 4 : (nj <= 7 && opt == 3) ? 6 : 0;
+        CyclePlan q = p;
+        if (bits && plan_detail::route(a, nj, io_bits, ns, true, dhp | bits, true, q)) return q;
+    }
+    plan_detail::route(a, nj, io_bits, ns, a.plain == 1, a.plain == 1 ? dhp : 0, false, p);
+    return p;
+}
 
 // Type-erased launchers (implemented in vfik_kernel.hip).  kargs points to a KArgs<nj>.
 uint32_t supported_joints_mask();

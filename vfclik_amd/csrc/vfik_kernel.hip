@@ -12,9 +12,13 @@
 // cross-lane traffic is needed, no lane idles, and the per-arm field list is read as a structure of
 // arrays so every wave-level load is one contiguous 1-KiB row.  No MFMA: there is no contraction to feed it.
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
-// no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins (launch_v).
-// Kernels of this file: cycle_kernel (variants by template: io type, joints, nullspace module, PLAIN, rollout, field path, LEAN,
-// compile-time flags, persistent), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel.
+// no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
+// Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel.
+// Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
+// of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
+// switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
+// variant from a patch file).  Every route switch is a run-time one (VFIK_BLOCK, VFIK_SUB8_MAX_BATCH, VFIK_PERSISTENT, VFIK_TWO_WAVES, ...).
 //
 // Arithmetic is float64 whatever the io dtype (DESIGN.md "Precision").
 #include "vfik_kernel.h"
@@ -27,12 +31,8 @@
 namespace vfik {
 #define VFIK_CAT2(a, b) a##b
 #define VFIK_CAT(a, b) VFIK_CAT2(a, b)
-// Chains of VFIK_HEAVY_MIN_NJ joints or more: the non-lean single-cycle variants are an object of their own (-DVFIK_HEAVY_PART; launch_v)
-#ifndef VFIK_HEAVY_MIN_NJ
-#define VFIK_HEAVY_MIN_NJ 12
-#endif
 #if defined(VFIK_ONLY_NJ) && VFIK_ONLY_NJ >= VFIK_HEAVY_MIN_NJ
-void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, bool plain, bool fastf, const KArgs& a, dim3 grid, dim3 blk, size_t lds, hipStream_t stream);
+void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, const KArgs& a, const CyclePlan& p, hipStream_t stream);
 #endif
 namespace {
 
@@ -91,12 +91,6 @@ __device__ __forceinline__ void sqrt_rsqrt(double x, double& root, double& inv) 
     inv = h + h;
 }
 
-__device__ __forceinline__ double norm3(double x, double y, double z) {
-    double r, i;
-    sqrt_rsqrt(x * x + y * y + z * z, r, i);
-    return r;
-}
-
 // acc + x*w with the product and the sum rounded separately, as CPython evaluates
 // `result[i] += v[i] * w` (command_mixer.py:81).  HIP's __dmul_rn/__dadd_rn are plain operators that
 // the compiler may still fuse, so contraction is switched off for this statement block.
@@ -113,8 +107,8 @@ __device__ __forceinline__ double mul_unfused(double x, double w) {
 
 // sin and cos: Cody-Waite reduction by pi/2 in three parts, then the classic minimax kernels on
 // [-pi/4, pi/4] (coefficients of fdlibm's __kernel_sin / __kernel_cos), < 1 ulp for |x| up to ~1e5 rad.
-// Joint angles live inside their limits (a few radians).
-__device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
+// Joint angles live inside their limits (a few radians).  (The eight-lanes kernel's: not instantiated for the longer chains.)
+[[maybe_unused]] __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
     const double k = __builtin_rint(x * 6.36619772367581382433e-01);
     double r = __builtin_fma(-k, 1.57079632673412561417e+00, x);
     r = __builtin_fma(-k, 6.07710050630396597660e-11, r);
@@ -654,36 +648,7 @@ __device__ __forceinline__ bool nullspace_core(double (&Jm)[NJ][6], double* lv_r
 //     quad rows  [tool 3 | goal 4 | slots 2*PRE | mixer weights 2] x Q16 x 1 KiB, then q (16-byte and 4-byte pieces),
 //     then the kinematics block of KConst (1-2 KiB)
 // ------------------------------------------------------------------------------------------------
-template <typename T> struct Stage {
-    // Slots staged at a time (prefetch window / chunk size).  float64 I/O stages 4: with 8 the region is 56 KB
-    // and only three of a CU's four SIMDs get a wave (160 KB LDS) -- the launch then runs in two rounds
-    // (measured 15.3 us instead of ~8 for the C3 batch).
-    static constexpr int PRE = sizeof(T) == 8 ? 4 : 8;
-    static constexpr int Q16 = (int)sizeof(T) / 4;           // 16-B pieces per quad
-    static constexpr int QBYTES = 4 * (int)sizeof(T);        // bytes of one quad
-    static constexpr int QSTEP = Q16 * 1024;                 // LDS bytes of one staged quad (a 1-KiB row per 16 bytes per lane)
-    static constexpr int QPCF = 3 * PRE / 2;                 // quads of one chunk of the compact repeller image
-    // Region of one wave, in the order [goal 4 | slot quads 0 .. QPCF-1 | q | kinematics | table] -- that much is all a LEAN
-    // launch on the straight-line path touches (`lean_bytes`: 19.75 KB for 7 joints with float I/O, eight waves per CU) --
-    // then [slot quads QPCF .. 2 PRE - 1 | tool 3 | mixer weights 2] for the general path and the optional per-arm inputs.
-    static constexpr int GOAL_OFF = 0, SLOT_OFF = 4 * QSTEP, Q_OFF = (4 + QPCF) * QSTEP;
-    // q is batch-major ([B][n]): a lane's n values are contiguous and travel as 16-byte pieces plus a
-    // remainder of one to three 4-byte pieces (a 12-byte LDS-DMA did not land lane-linear on gfx950)
-    __host__ __device__ static constexpr int qbytes(int nj) { return nj * (int)sizeof(T); }
-    __host__ __device__ static constexpr int q16(int nj) { return qbytes(nj) / 16; }
-    __host__ __device__ static constexpr int qrem(int nj) { return qbytes(nj) % 16; }
-    __host__ __device__ static constexpr int qregion(int nj) { return q16(nj) * 1024 + qrem(nj) * 64; }
-    __host__ __device__ static constexpr int kin_rows(int nj) { return ((12 + 10 * nj + 4 + 10 + VFIK_MIX_CHANNELS + 12 + 6 + nj) * 8 + 1023) / 1024; }  // = KConst<nj>::KIN_ROWS
-    __host__ __device__ static constexpr int kin_off(int nj) { return Q_OFF + qregion(nj); }
-    __host__ __device__ static constexpr int tab_off(int nj) { return kin_off(nj) + kin_rows(nj) * 1024; }  // sin / cos table, 1 KiB
-    __host__ __device__ static constexpr int lean_bytes(int nj) { return tab_off(nj) + 1024; }
-    __host__ __device__ static constexpr int slot_off(int idx, int nj) {  // slot quad idx of the staged chunk
-        return idx < QPCF ? SLOT_OFF + idx * QSTEP : lean_bytes(nj) + (idx - QPCF) * QSTEP;
-    }
-    __host__ __device__ static constexpr int tool_off(int nj) { return lean_bytes(nj) + (2 * PRE - QPCF) * QSTEP; }
-    __host__ __device__ static constexpr int mixw_off(int nj) { return tool_off(nj) + 3 * QSTEP; }
-    __host__ __device__ static constexpr int bytes(int nj) { return mixw_off(nj) + 2 * QSTEP; }
-};
+// (Stage<T>, the region's layout: vfik_kernel.h -- the launch plan sizes the LDS from it)
 
 // LDS byte address (relative to the q area) of byte b of this lane's q vector
 template <typename T, int NJ>
@@ -698,30 +663,21 @@ __device__ __forceinline__ int q_lds_off(int b, int lane) {
 typedef __attribute__((address_space(1))) const void* GPtr;
 typedef __attribute__((address_space(3))) void* LPtr;
 
-// one quad plane: this lane's quad (QBYTES at gsrc) -> the Q16 1-KiB rows at byte offset `off` of the region.
-// NT: non-temporal cache policy (aux = 2) for bytes that one wave reads once per launch.  Round 2 adopted it for the long
+// one quad plane: this lane's quad (QBYTES at gsrc) -> the Q16 1-KiB rows at byte offset `off` of the region, with the
+// non-temporal cache policy (aux = 2): bytes that one wave reads once per launch.  Round 2 adopted it for the long
 // chains only (C5 -4.2 %; C3 and C3N +-0.6 %), from A/Bs in which back-to-back launches re-read one input set out of the
 // Infinity Cache.  With the inputs coming from HBM (rotating input sets, bench.py --state cold) it is worth -6.8 % on C3
 // (6.62 -> 6.16 us) and -5.8 % on C5, at +0.8 % / -4.3 % in the cache-resident state: every chain uses it since round 3
 // (profiles/r03_nt_ab.txt).
-#ifndef VFIK_SADDR_REQUESTS
-#define VFIK_SADDR_REQUESTS 0     // 1: requests in the SGPR-base form (A/B builds: C5 +2.6 %, C3 +-0.5 % -- profiles/r03_ab_experiments.md 21)
-#endif
 // The address is (wave-uniform plane base) + (this lane's 32-bit byte offset).  Round 3 tried the SGPR-base form of the instruction
 // (`global_load_lds v_off, s[base]`: the offset unsigned and opaque, so that the backend reads base + zext(offset)): 30 of the 34 requests
 // take it, one 64-bit vector addition a request becomes two to three scalar instructions -- and a lone wave pays an issue slot for
-// either: C3 +-0.5 %, C5 +2.6 % warm / +1.8 % cold.  Off (VFIK_SADDR_REQUESTS); voff < 4 GiB either way.
-template <typename T, bool NT = false>
+// either: C3 +-0.5 %, C5 +2.6 % warm / +1.8 % cold (profiles/r03_ab_experiments.md 21).  Not adopted; voff < 4 GiB either way.
+template <typename T>
 __device__ __forceinline__ void stage_quad(const char* gbase, unsigned voff, char* region, int off) {
-#if VFIK_SADDR_REQUESTS
-    asm("" : "+v"(voff));   // (opaque: or the optimiser widens the offset's multiplication and the addition no longer reads base + zext(offset))
-    __builtin_amdgcn_global_load_lds((GPtr)(gbase + voff), (LPtr)(region + off), 16, 0, NT ? 2 : 0);
-    if (Stage<T>::Q16 == 2) __builtin_amdgcn_global_load_lds((GPtr)(gbase + 16 + voff), (LPtr)(region + off + 1024), 16, 0, NT ? 2 : 0);
-#else
     const char* gsrc = gbase + (long)(int)voff;
-    __builtin_amdgcn_global_load_lds((GPtr)gsrc, (LPtr)(region + off), 16, 0, NT ? 2 : 0);
-    if (Stage<T>::Q16 == 2) __builtin_amdgcn_global_load_lds((GPtr)(gsrc + 16), (LPtr)(region + off + 1024), 16, 0, NT ? 2 : 0);
-#endif
+    __builtin_amdgcn_global_load_lds((GPtr)gsrc, (LPtr)(region + off), 16, 0, 2);
+    if (Stage<T>::Q16 == 2) __builtin_amdgcn_global_load_lds((GPtr)(gsrc + 16), (LPtr)(region + off + 1024), 16, 0, 2);
 }
 
 template <typename T>
@@ -753,12 +709,6 @@ template <typename T> struct SlotLds {
         return *reinterpret_cast<const double*>(region + off + (c >> 1) * 1024 + lane * 16 + (c & 1) * 8);
     }
 };
-
-// Chains of at least this many joints request their per-arm input planes with the non-temporal cache policy (stage_quad).
-// A build knob for the A/B of that policy in the warm (cache-resident) and the cold (HBM-sourced) state: tools/ab_compare.py --state.
-#ifndef VFIK_NT_MIN_NJ
-#define VFIK_NT_MIN_NJ 0
-#endif
 
 
 // A scalar of the lean paths (lambda2, rot_slow, mix_w ...): they sit behind the kinematics block in KConst and travel to LDS with it.
@@ -815,15 +765,6 @@ template <typename T> struct SlotLds {
 // phase, q round trip and tail.
 // Lean single-cycle launches on the straight-line path take the 56-byte KLean instead of the 340-byte KArgs (vfik_kernel.h): the
 // handle's state is one arena whose layout follows from (io type, joints, Bpad).  (The diagnostic stamps build keeps KArgs.)
-#ifndef VFIK_Q_FIRST
-#define VFIK_Q_FIRST 0            // 1: q's pieces requested in front of the constants (A/B builds: no gain, profiles/r03_ab_experiments.md 18)
-#endif
-#ifndef VFIK_NT_STORES
-#define VFIK_NT_STORES 0          // 1: the lane-by-lane output stores non-temporal (A/B builds)
-#endif
-#ifndef VFIK_SCALAR_KERNARG
-#define VFIK_SCALAR_KERNARG 1     // 0: every kernel takes its argument block by value, as until round 3 (A/B builds)
-#endif
 #ifdef VFIK_STAMPS
 template <int LEAN, bool ROLL, bool FASTF, bool MIXO = false> struct SmallArgs { static constexpr bool value = false; };
 #else
@@ -859,7 +800,7 @@ template <typename T, int NJ> struct ArenaLayout {
 // default robot (vfclik:42) -- has a = 0 on every link and alpha = +-pi/2 on six of seven; such a link's rotation about x is a renaming
 // with a sign instead of 12 operations, its a-term vanishes, and links with d = 0 skip the offset: 114 of the lean C3 kernel's 1 269
 // vector instructions (C3 -5.3 % warm / -3.7 % cold, C3N -3.1 %, C3F -2.7 %: profiles/r04_ab_dhp.txt, before the swap lost its last
-// multiplications).  Built for the lean and the publishing-lean straight-line float variants (dhp_of); every other variant, and every
+// multiplications).  Built for the lean and the publishing-lean straight-line float variants (plan_cycle); every other variant, and every
 // chain that does not match a built pattern, runs the general DH form.
 template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF, bool PERS, bool FUN, int WAVES, bool UNI, bool MIXO, int DHP>
 __device__ __forceinline__ void
@@ -922,13 +863,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         if constexpr (LEAN == 1) a.status_or = 0;  // (a stepped rollout accumulates the status bits of its cycles)
         if constexpr (!ROLL && LEAN == 1) a.q_out = nullptr;  // (a rollout's q_out is its result)
     }
-    // Fetch the kernel arguments the prologue needs with one batch of scalar loads: left to itself the
-    // compiler loads them one by one, each time waiting out a full scalar-load latency.
-    // (Entered through cycle_kernel_s / cycle_kernel_x they arrive preloaded in SGPRs, and the rest of the block is best left where
-    // the compiler first needs it.)
-    if constexpr (!VFIK_SCALAR_KERNARG)
-        asm volatile("" ::"s"(a.B), "s"(a.block), "s"(a.Bpad), "s"(a.slots_used), "s"(a.tool_stride), "s"(a.q), "s"(a.goal), "s"(a.slots), "s"(a.slots_fast),
-                     "s"(a.tool), "s"(a.mixw), "s"(a.kc));
     // PERS: one wave per block; chunk = 64 consecutive arms; lanes past the end of the batch compute arm B - 1 again and store nothing
     const int nchunks = (a.B + 63) >> 6;
     int chunk = PERS ? (int)blockIdx.x : 0;
@@ -936,7 +870,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     const long Bs = a.B;
     constexpr unsigned DHP_SWAP = DhPattern<NJ, DHPAT>::SWAP, DHP_NONE = DhPattern<NJ, DHPAT>::NONE, DHP_D0 = DhPattern<NJ, DHPAT>::D0;
     constexpr bool TABSC = NJ <= 8;  // sin / cos through the LDS table (sincos_tab_n)
-    constexpr bool NTL = NJ >= VFIK_NT_MIN_NJ;   // non-temporal policy for the per-arm input planes (stage_quad)
     // batch constants through the constant address space: always scalar loads
     typedef const KConst<NJ> __attribute__((address_space(4))) * KcPtr;
     const KcPtr kc_launch = (KcPtr)(unsigned long long)a.kc;
@@ -964,35 +897,15 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     const long planeB = Bp * QB;  // bytes of one quad plane
     constexpr int NQREQ = Stage<T>::q16(NJ) + Stage<T>::qrem(NJ) / 4;   // requests that bring one q vector
     auto issue_q_piece = [&](int r, int armx, char* dr) {  // piece r of arm armx's q into the per-arm area dr
-#if VFIK_SADDR_REQUESTS
-        const char* const q0 = static_cast<const char*>(a.q);            // (uniform base + unsigned lane offset: stage_quad)
-        unsigned qv = (unsigned)armx * (unsigned)(NJ * sizeof(T));
-        asm("" : "+v"(qv));
-        char* qrow = dr + Stage<T>::Q_OFF;
-        constexpr int n16 = Stage<T>::q16(NJ);
-        if (r < n16) __builtin_amdgcn_global_load_lds((GPtr)(q0 + r * 16 + qv), (LPtr)(qrow + r * 1024), 16, 0, 0);
-        else __builtin_amdgcn_global_load_lds((GPtr)(q0 + (n16 * 16 + (r - n16) * 4) + qv), (LPtr)(qrow + n16 * 1024 + (r - n16) * 256), 4, 0, 0);
-#else
         const char* qg = static_cast<const char*>(a.q) + (long)armx * NJ * sizeof(T);
         char* qrow = dr + Stage<T>::Q_OFF;
         constexpr int n16 = Stage<T>::q16(NJ);
-#ifndef VFIK_Q_NT
-#define VFIK_Q_NT 0               // 1: q's pieces with the non-temporal policy too (A/B builds)
-#endif
-        if (r < n16) __builtin_amdgcn_global_load_lds((GPtr)(qg + r * 16), (LPtr)(qrow + r * 1024), 16, 0, VFIK_Q_NT ? 2 : 0);
-        else __builtin_amdgcn_global_load_lds((GPtr)(qg + n16 * 16 + (r - n16) * 4), (LPtr)(qrow + n16 * 1024 + (r - n16) * 256), 4, 0, VFIK_Q_NT ? 2 : 0);
-#endif
+        if (r < n16) __builtin_amdgcn_global_load_lds((GPtr)(qg + r * 16), (LPtr)(qrow + r * 1024), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds((GPtr)(qg + n16 * 16 + (r - n16) * 4), (LPtr)(qrow + n16 * 1024 + (r - n16) * 256), 4, 0, 0);
     };
     // (Round 3 tried q's pieces FIRST, in front of the constants -- q is the one input the wave cannot start without, and with the
     // inputs in HBM the one it waits for longest: C3 / C3N +-0.1 % cold and warm, C5 +0.9 % cold.  Two requests earlier is nothing
     // against a round trip.)
-    constexpr bool QFIRST = VFIK_Q_FIRST && !PERS;
-    if constexpr (QFIRST) {
-        if (arm < a.B) {
-#pragma unroll
-            for (int r = 0; r < NQREQ; ++r) issue_q_piece(r, arm, dreg);
-        }
-    }
     {   // kinematics constants (oldest request: covered by the first wait).  All 64 lanes copy
         // 16 bytes each, so this comes before the lanes past the end of the batch retire.
         const char* kg = static_cast<const char*>(a.kc) + lane * 16;
@@ -1008,12 +921,9 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // every lane reads ITS row from there (row stride n sizeof(T): 7 dwords, odd, conflict-free).  Two requests instead of four at ~70 cycles of
     // the issuing wave each.  The lanes fetch pieces, not rows, so this happens before the lanes past the end of the batch retire; pieces past
     // the batch's last row are not requested.
-#ifndef VFIK_Q_BLOCK
-#define VFIK_Q_BLOCK 1            // 0: q arm by arm, as until round 3 (A/B builds)
-#endif
     // (the lean single-cycle variants at one wave per SIMD: elsewhere the few registers of the block form tipped variants that sit at their
     // register limit into scratch -- 12 to 130 B per lane in seven of them)
-    constexpr bool QBLK = VFIK_Q_BLOCK && !PERS && !QFIRST && !ROLL && LEAN != 0 && WAVES == 1;
+    constexpr bool QBLK = !PERS && !ROLL && LEAN != 0 && WAVES == 1;
     if constexpr (QBLK) {
         constexpr int BQ = NJ * (int)sizeof(T);              // bytes of one row
         constexpr int NBLK = (BQ + 15) / 16;                 // requests: 64 BQ bytes in pieces of 64 x 16
@@ -1040,14 +950,14 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     if (a.tool_stride) {          // per-arm tools ([3][Bpad] quads); a shared tool sits in KConst
         const char* tg = static_cast<const char*>(a.tool);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) stage_quad<T, NTL>(tg + k * planeB, (unsigned)arm * (unsigned)QB, region, Stage<T>::tool_off(NJ) + k * Stage<T>::QSTEP);
+        for (int k = 0; k < 3; ++k) stage_quad<T>(tg + k * planeB, (unsigned)arm * (unsigned)QB, region, Stage<T>::tool_off(NJ) + k * Stage<T>::QSTEP);
     }
     if (a.mixw) {  // per-arm mixer weights ([2][Bpad] quads: w0..w3 | w4 w5 - -); else KConst::mix_w
         const char* mg = static_cast<const char*>(a.mixw);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) stage_quad<T, NTL>(mg + k * planeB, (unsigned)arm * (unsigned)QB, region, Stage<T>::mixw_off(NJ) + k * Stage<T>::QSTEP);
+        for (int k = 0; k < 2; ++k) stage_quad<T>(mg + k * planeB, (unsigned)arm * (unsigned)QB, region, Stage<T>::mixw_off(NJ) + k * Stage<T>::QSTEP);
     }
-    if constexpr (!QFIRST && !QBLK) {
+    if constexpr (!QBLK) {
 #pragma unroll
         for (int r = 0; r < NQREQ; ++r) issue_q_piece(r, arm, dreg);
     }
@@ -1061,9 +971,8 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     constexpr int QPC = UNI ? PRE : (FASTF ? 3 * PRE / 2 : 2 * PRE);       // slot quads per chunk
     const char* const goal0 = static_cast<const char*>(a.goal);
     const char* const slots0 = static_cast<const char*>(FASTF ? a.slots_fast : a.slots);
-    const char* sg = slots0 + (long)arm * QB;  // this arm's quad of slot plane 0
     auto issue_goal_quad = [&](int k, int armx, char* dr) {
-        stage_quad<T, NTL>(goal0 + k * planeB, (unsigned)armx * (unsigned)QB, dr, Stage<T>::GOAL_OFF + k * Stage<T>::QSTEP);
+        stage_quad<T>(goal0 + k * planeB, (unsigned)armx * (unsigned)QB, dr, Stage<T>::GOAL_OFF + k * Stage<T>::QSTEP);
     };
     auto issue_slot_quad_of = [&](int idx, int armx, char* dr) {  // idx in [0, QPC): quad idx of the first chunk of slots
         // quads past the slots in use re-request plane 0 (cache hit) and are masked below, so the
@@ -1073,7 +982,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         // (UNI: plane 0 of the uniform image is an EMPTY slot for every arm -- radius -inf --, slot m sits in plane m + 1: a quad past the
         // slots in use is then harmless by itself and the chunk needs no mask)
         const bool in = UNI ? idx < npre : (FASTF ? 2 * (idx / 3) < npre : (idx >> 1) < npre);
-        stage_quad<T, NTL>(slots0 + (in ? (long)(UNI ? idx + 1 : idx) * planeB : 0), (unsigned)armx * (unsigned)QB, dr, Stage<T>::slot_off(idx, NJ));
+        stage_quad<T>(slots0 + (in ? (long)(UNI ? idx + 1 : idx) * planeB : 0), (unsigned)armx * (unsigned)QB, dr, Stage<T>::slot_off(idx, NJ));
     };
     auto issue_slot_quad = [&](int idx) { issue_slot_quad_of(idx, arm, dreg); };
     constexpr int N_SLOT = QPC * Q16;                       // requests issued after the goal
@@ -1085,19 +994,8 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // wave's ~20 requests of the launch's first half microsecond compete for the same bandwidth -- 16.5 MB in all, 2-3 us of HBM time -- and
     // what a wave needs FIRST (q: 1.8 MB over the batch, then the goal block) queued behind slot data it needs last: slot quads requested
     // between the joints instead, C3 cold 5.57 -> 5.21 us (-6.5 %), three early 5.44; warm +-0 (profiles/r04_ab_early_q.txt).
-#ifndef VFIK_EARLY_Q
-#define VFIK_EARLY_Q 0            // slot quads requested into q's round trip (A/B builds)
-#endif
-    constexpr int EARLY_Q = PERS ? QPC : (NJ >= 10 ? 0 : (VFIK_EARLY_Q < QPC ? VFIK_EARLY_Q : QPC));
-#ifndef VFIK_GOAL_LATE
-#define VFIK_GOAL_LATE 0          // 1: the goal block requested behind the first joint's transform instead of in front of the kinematics (A/B builds)
-#endif
-#ifndef VFIK_SLOT_JOINT0
-#define VFIK_SLOT_JOINT0 0        // first joint behind which slot quads are requested (A/B builds)
-#endif
-    constexpr bool GOAL_LATE = VFIK_GOAL_LATE && !PERS;
-    constexpr int SJ0 = (VFIK_SLOT_JOINT0 < NJ - 1 && !PERS) ? VFIK_SLOT_JOINT0 : 0;
-    constexpr int SLOTQ_PER_JOINT = (QPC - EARLY_Q + (NJ - SJ0) - 1) / (NJ - SJ0);  // slot quads requested after each joint
+    constexpr int EARLY_Q = PERS ? QPC : 0;
+    constexpr int SLOTQ_PER_JOINT = (QPC - EARLY_Q + NJ - 1) / NJ;  // slot quads requested after each joint
     // PERS: request r of a chunk's NPF = q pieces, goal quads, slot quads, in that order (float I/O: one request a quad)
     constexpr int NPF = PERS ? NQREQ + 4 + QPC : 0;
     constexpr int PF_PER_JOINT = (NPF + NJ - 1) / NJ;
@@ -1106,19 +1004,17 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         else if (r < NQREQ + 4) issue_goal_quad(r - NQREQ, armx, dr);
         else issue_slot_quad_of(r - NQREQ - 4, armx, dr);
     };
-    if constexpr (!GOAL_LATE) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) issue_goal_quad(k, arm, dreg);
-    }
+    for (int k = 0; k < 4; ++k) issue_goal_quad(k, arm, dreg);
     if constexpr (FUN) {  // the funnel block, right behind the goal block: the goal's wait covers it
         const char* fg = static_cast<const char*>(a.funnel);
 #pragma unroll
-        for (int k = 0; k < NFUN; ++k) stage_quad<T, NTL>(fg + k * planeB, (unsigned)arm * (unsigned)QB, region, FUN_OFF + k * Stage<T>::QSTEP);
+        for (int k = 0; k < NFUN; ++k) stage_quad<T>(fg + k * planeB, (unsigned)arm * (unsigned)QB, region, FUN_OFF + k * Stage<T>::QSTEP);
     }
     // MIXO: the 16 order bytes that cover slots [c0 & ~15, +16) of this arm -> the order row (one request whatever T)
     auto issue_orders = [&](int c0) {
         const char* og = static_cast<const char*>(a.orders) + (long)(c0 >> 4) * Bp * 16 + (long)arm * 16;
-        __builtin_amdgcn_global_load_lds((GPtr)og, (LPtr)(region + ORD_OFF), 16, 0, NTL ? 2 : 0);
+        __builtin_amdgcn_global_load_lds((GPtr)og, (LPtr)(region + ORD_OFF), 16, 0, 2);
     };
     if constexpr (MIXO) issue_orders(0);  // (behind the goal / aux blocks: the goal's wait covers it)
 #pragma unroll
@@ -1128,7 +1024,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // left alone, the compiler fetches each where it is first used -- a round trip to the kernarg segment every time)
     // (not in the non-lean variants of the long chains: 34 scalar registers pinned from here to the epilogue spill to vector lanes in kernels
     // that have no vector register to spare -- part of what took their scratch away, profiles/r04_ab_experiments.md C)
-    if constexpr (VFIK_SCALAR_KERNARG && !SmallArgs<LEAN, ROLL, FASTF, MIXO>::value && !(LEAN == 0 && NJ >= 12))
+    if constexpr (!SmallArgs<LEAN, ROLL, FASTF, MIXO>::value && !(LEAN == 0 && NJ >= 12))
         asm volatile("" ::"s"(a.null_control), "s"(a.qdot_vf), "s"(a.qdot_null), "s"(a.pose), "s"(a.pose_nt), "s"(a.v6), "s"(a.qdist), "s"(a.goal_dist),
                      "s"(a.status), "s"(a.q_out), "s"(a.ext), "s"(a.q_ref), "s"(a.q_cmded), "s"(a.q_lo), "s"(a.q_hi), "s"(a.q_ref_out), "s"(a.wts));
     STAMP(1);
@@ -1158,7 +1054,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         }
     };
     if constexpr (!PERS) {
-        VFIK_WAIT_VM(((GOAL_LATE ? 0 : 4) + NFUN + EARLY_Q) * Q16 + NORD);  // constants, table, tool and q have landed (the goal, funnel, order and early slot requests may still be out)
+        VFIK_WAIT_VM((4 + NFUN + EARLY_Q) * Q16 + NORD);  // constants, table, tool and q have landed (the goal, funnel, order and early slot requests may still be out)
         STAMP(2);
         read_q();
     }
@@ -1348,13 +1244,9 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
 #pragma unroll
         for (int r = 0; r < 3; ++r) { R[3 * r + 1] = __builtin_fma(ca, ym[r], t1[r]); R[3 * r + 2] = __builtin_fma(ca, R[3 * r + 2], -t2[r]); }
         }
-        if (GOAL_LATE && first && i == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) issue_goal_quad(k, arm, dreg);
-        }
 #pragma unroll
         for (int k = 0; k < SLOTQ_PER_JOINT; ++k)
-            if (first && i >= SJ0 && EARLY_Q + (i - SJ0) * SLOTQ_PER_JOINT + k < QPC) issue_slot_quad(EARLY_Q + (i - SJ0) * SLOTQ_PER_JOINT + k);
+            if (first && EARLY_Q + i * SLOTQ_PER_JOINT + k < QPC) issue_slot_quad(EARLY_Q + i * SLOTQ_PER_JOINT + k);
         if constexpr (PERS) {  // the next chunk's requests, into the other per-arm area, a few after every joint
             if (has_next) {
 #pragma unroll
@@ -1726,7 +1618,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                     for (int idx = 0; idx < QPC; ++idx) {
                         const int m = UNI ? c0 + PRE + idx : c0 + PRE + 2 * (idx / 3);  // (first) slot of the quad
                         const char* sm = slots0 + (m < a.slots_used ? (long)(UNI ? c0 + PRE + idx + 1 : (c0 + PRE) / 2 * 3 + idx) * planeB : 0);
-                        stage_quad<T, NTL>(sm, (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
+                        stage_quad<T>(sm, (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
                     }
                     if constexpr (MIXO) issue_orders(c0 + PRE);   // (the row's bytes of this chunk are in registers)
                 }
@@ -1884,7 +1776,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                     for (int idx = 0; idx < 2 * PRE; ++idx) {
                         const int m = c0 + (idx >> 1);
                         const char* sm = slots0 + (m < a.slots_used ? (long)m * 2 * planeB : 0) + (idx & 1) * planeB;
-                        stage_quad<T, NTL>(sm, (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
+                        stage_quad<T>(sm, (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
                     }
                 }
                 VFIK_WAIT_VM(0);
@@ -2293,11 +2185,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             } else {
     #pragma unroll
                 for (int i = 0; i < K; ++i) {
-#if VFIK_NT_STORES
-                    __builtin_nontemporal_store((T)val(i), &o[(long)arm * K + i]);
-#else
                     o[(long)arm * K + i] = (T)val(i);
-#endif
                 }
             }
         };
@@ -2416,21 +2304,14 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         const int an = chunk * 64 + (int)threadIdx.x;
         act = an < a.B;
         arm = arm_next;
-        sg = slots0 + (long)arm * QB;
         dreg = dreg_next;
     }
     }  // chunks of this wave (PERS)
 }
 
-// The kernel proper: the body above behind an argument block (KArgs, or KLean for the lean single-cycle straight-line variants) ...
-template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool PERS = false, bool FUN = false, int WAVES = 1, bool UNI = false, bool MIXO = false, int DHP = 0>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-cycle_kernel(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::value, KLean, KArgs>::type a_in) {
-    cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, PERS, FUN, WAVES, UNI, MIXO, DHP>(a_in);
-}
-// ... or, for the KLean variants, behind KLean's ten members as SCALAR kernel arguments: those the command processor can preload into
-// the wave's SGPRs at dispatch (-amdgpu-kernarg-preload-count, Makefile; an argument block passed by value is never preloaded), which
-// takes the scalar-load round trip of the kernarg out of every wave's prologue.
+// The kernel proper: the body above behind scalar kernel arguments -- those the command processor can preload into the wave's SGPRs
+// at dispatch (-amdgpu-kernarg-preload-count, Makefile; an argument block passed by value is never preloaded), which takes the
+// scalar-load round trip of the kernarg out of every wave's prologue.  The KLean variants: KLean's ten members alone ...
 template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool PERS = false, bool FUN = false, int WAVES = 1, bool UNI = false, int DHP = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 cycle_kernel_s(const void* base, const void* q, void* qdot_out, int* status, int B, int Bpad, int slots_used, int fast_order, unsigned flags, int block) {
@@ -2736,8 +2617,7 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
     // The members of the argument block the rest of the kernel needs, in ONE batch of scalar loads behind the requests above (entered
     // through cycle_sub8_kernel_x, whose scalars are preloaded, the compiler otherwise fetches them one by one where each is first
     // used, every time a full round trip to the kernarg segment).
-    if constexpr (VFIK_SCALAR_KERNARG)
-        asm volatile("" ::"s"(a.qdot_vf), "s"(a.qdot_null), "s"(a.pose), "s"(a.pose_nt), "s"(a.qdist), "s"(a.status));
+    asm volatile("" ::"s"(a.qdot_vf), "s"(a.qdot_null), "s"(a.pose), "s"(a.pose_nt), "s"(a.qdist), "s"(a.status));
 
     // ---- A3: sin / cos of joint j on lane j, exchanged through LDS
     {
@@ -3076,374 +2956,158 @@ cycle_sub8_kernel_x(const void* base, const void* q, void* qdot_out, const void*
     cycle_sub8_body<T, NJ, NS, DHP>(a);
 }
 
-// The argument block a kernel variant takes: KLean for the lean single-cycle straight-line variants, KArgs otherwise
-template <int LEAN, bool ROLL, bool FASTF>
-typename std::conditional<SmallArgs<LEAN, ROLL, FASTF>::value, KLean, KArgs>::type args_for(const KArgs& a) {
-    if constexpr (SmallArgs<LEAN, ROLL, FASTF>::value) {
-        KLean k;
-        k.base = a.arena; k.q = a.q; k.qdot_out = a.qdot_out; k.status = a.status;
-        k.B = a.B; k.Bpad = a.Bpad; k.slots_used = a.slots_used; k.fast_order = a.fast_order; k.flags = a.flags; k.block = a.block;
-        return k;
-    } else {
-        return a;
-    }
+// ------------------------------------------------------------------------------------------------
+// The launcher: a launch plan (vfik_kernel.h: plan_cycle) -> the kernel instantiation it names.  The plan's run-time template
+// arguments are expanded over the values of the variants that are BUILT -- the predicates below; a plan outside them is an error.
+// ------------------------------------------------------------------------------------------------
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+template <int V> using int_c = std::integral_constant<int, V>;
+#define VFIK_V(c) decltype(c)::value
+template <typename F> void as_bool(bool v, F&& f) { if (v) f(bool_c<true>()); else f(bool_c<false>()); }
+template <int... Vs, typename F> void as_int(int v, F&& f) { (void)((v == Vs ? (f(int_c<Vs>()), true) : false) || ...); }
+template <typename F> void as_dhp(int d, F&& f) { as_int<0, 1, 2, 3, 4, 5, 6, 7>(d, f); }
+template <typename F> void as_cf(int cf, F&& f) { as_int<-1, CF_NSMIX, CF_NSJLMIX>(cf, f); }
+
+// DH-pattern bits built (plan_cycle: the DH pattern of a cycle_kernel variant): the chain's pattern where one exists for the joint count (float64
+// I/O: the 7-joint chain's alone), and, float32 I/O, the batch's shared tool (bit 1) and shared IK weights (bit 2, up to 7 joints) on top of it
+template <int NJ> constexpr int PATTERN_BIT = DhPattern<NJ, 1>::SWAP != 0 ? 1 : 0;
+template <int NJ> constexpr bool dhp_shared(int d) { return d == (PATTERN_BIT<NJ> | 2) || (NJ <= 7 && (d == (PATTERN_BIT<NJ> | 4) || d == (PATTERN_BIT<NJ> | 6))); }
+template <typename T, int NJ> constexpr bool dhp_plain(int d) { return d == 0 || (d == 1 && PATTERN_BIT<NJ> && (sizeof(T) == 4 || NJ == 7)); }
+template <typename T, int NJ> constexpr bool dhp_lean(int d) { return dhp_plain<T, NJ>(d) || (sizeof(T) == 4 && dhp_shared<NJ>(d)); }
+// ... the eight-lanes kernel: the pattern and the shared bits at either I/O type
+template <int NJ> constexpr bool dhp_sub8(int d) { return d == 0 || (d == 1 && PATTERN_BIT<NJ>) || dhp_shared<NJ>(d); }
+// the lean and publishing-lean variants (WAVES 1): the flag sets of the nullspace module for chains of up to 7 joints, without the aux block
+// or the shared bits; the aux block (FUN) on the compact image
+template <typename T, int NJ, bool NS, int CF, bool FUN, bool UNI, int D>
+constexpr bool lean_built() { return dhp_lean<T, NJ>(D) && !(FUN && UNI) && (CF == -1 || (NS && NJ <= 7 && !FUN && D <= 1)); }
+
+// cycle_kernel_x: the prologue's arguments as preloaded scalars in front of the argument block
+template <typename T, int NJ, bool NS, bool PL, bool ROLL, bool FASTF, int LEAN, int CF, bool PERS, bool FUN, int WAVES, bool UNI, int D>
+void launch_x(const KArgs& a, const CyclePlan& p, hipStream_t stream) {
+    hipLaunchKernelGGL((cycle_kernel_x<T, NJ, NS, PL, ROLL, FASTF, LEAN, CF, PERS, FUN, WAVES, UNI, false, D>), dim3(p.grid), dim3(p.block), p.lds, stream, a.arena, a.q,
+                       a.qdot_out, a.active, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block, a);
 }
 
-// Launch of a KLean variant (lean, single cycle, straight-line field path): scalar kernel arguments, or the argument block.
-// UNI variants read the uniform repeller image, which sits a.uni_planes quad planes behind the compact one: the offset rides in the
-// upper bits of fast_order (KLean's fourteen dwords are all taken).
-// The DH pattern a variant is built with: the requested one for the lean / publishing-lean single-cycle straight-line float variants and the lean rollout
-// (not the persistent one), none for every other variant -- so that asking for a pattern never multiplies the kernels of the rest.
-// float64 I/O (what a port-level caller's bottles are): the pattern alone, for the 7-joint chain (the LWR) -- C3's batch with float64 I/O
-// 6.12 -> 5.5 us; the shared-tool / shared-weights bits are float32-I/O only (launch_v).
-template <typename T, bool PL, bool ROLL, bool FASTF, int LEAN, bool PERS, int NJ>
-constexpr int dhp_of(int dhp) {
-    return (PL && FASTF && (ROLL ? LEAN == 1 : LEAN != 0) && !PERS) ? (sizeof(T) == 4 ? dhp : (NJ == 7 ? (dhp & 1) : 0)) : 0;
+// Full: the non-lean single-cycle variants (of the long chains: an object of their own, launch_heavy_nj<n>)
+template <typename T, int NJ, bool NS>
+void launch_full(const KArgs& a, const CyclePlan& p, hipStream_t stream) {
+    as_bool(p.plain, [&](auto PL) {
+        as_bool(p.fastf, [&](auto FASTF) { launch_x<T, NJ, NS, VFIK_V(PL), false, VFIK_V(FASTF), 0, -1, false, false, 1, false, 0>(a, p, stream); });
+    });
 }
 
-template <typename T, int NJ, bool NS, bool PL, int CF = -1, bool PERS = false, bool FUN = false, int WAVES = 1, bool UNI = false, int DHP = 0>
-void launch_lean(const KArgs& a_in, dim3 grid, dim3 blk, size_t lds, hipStream_t stream) {
-    // (the two-waves build on the compact image spilled 9 registers per lane with the pattern: it keeps the general DH form)
-    constexpr int D = (WAVES == 2 && !UNI) ? 0 : dhp_of<T, PL, false, true, 1, PERS, NJ>(DHP);
+template <typename T, int NJ, bool NS>   // NS: the launch's flags carry VFIK_F_NULLSPACE (one object per (n, T, NS))
+hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream) {
     KArgs a = a_in;
-    if constexpr (UNI) a.fast_order = (a.fast_order & 255) | (a.uni_planes << 8);
-    if constexpr (SmallArgs<1, false, true>::value && VFIK_SCALAR_KERNARG) {
-        hipLaunchKernelGGL((cycle_kernel_s<T, NJ, NS, PL, false, true, 1, CF, PERS, FUN, WAVES, UNI, D>), grid, blk, lds, stream, (const void*)a.arena, a.q, a.qdot_out,
-                           a.status, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block);
-    } else {
-        hipLaunchKernelGGL((cycle_kernel<T, NJ, NS, PL, false, true, 1, CF, PERS, FUN, WAVES, UNI, false, D>), grid, blk, lds, stream, args_for<1, false, true>(a));
-    }
-}
-
-// Launch of any other variant: the prologue's arguments as scalars in front of the argument block, or the block alone
-template <typename T, int NJ, bool NS, bool PL, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool PERS = false, bool FUN = false, bool UNI = false, bool MIXO = false, int DHP = 0>
-void launch_full(const KArgs& a_in, dim3 grid, dim3 blk, size_t lds, hipStream_t stream) {
-    constexpr int D = dhp_of<T, PL, ROLL, FASTF, LEAN, PERS, NJ>(DHP);
-    if constexpr (SmallArgs<LEAN, ROLL, FASTF, MIXO>::value) {
-        launch_lean<T, NJ, NS, PL, CF, PERS, FUN, 1, UNI, DHP>(a_in, grid, blk, lds, stream);
-    } else {
-        KArgs a = a_in;
-        if constexpr (UNI) a.fast_order = (a.fast_order & 255) | (a.uni_planes << 8);
-        if constexpr (VFIK_SCALAR_KERNARG) {
-            hipLaunchKernelGGL((cycle_kernel_x<T, NJ, NS, PL, ROLL, FASTF, LEAN, CF, PERS, FUN, 1, UNI, MIXO, D>), grid, blk, lds, stream, (const void*)a.arena, a.q, a.qdot_out,
-                               a.active, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block, a);
-        } else {
-            hipLaunchKernelGGL((cycle_kernel<T, NJ, NS, PL, ROLL, FASTF, LEAN, CF, PERS, FUN, 1, UNI, MIXO, D>), grid, blk, lds, stream, a);
-        }
-    }
-}
-
-template <typename T, int NJ, bool NS, bool PL, int DHP = 0>
-void launch_v(const KArgs& a_in, dim3 grid, dim3 blk, size_t lds, hipStream_t stream, int* sub8) {
-    // FASTF: the straight-line repeller path and the general field path are separate kernels -- compiled into
-    // one, the general path's code cost the straight-line launches 2.7 % (register allocation and layout).
-    KArgs a = a_in;
-    bool fastf = a.fast_order >= 0;
-    // a funnel block in the batch (the goalAndNormal scene): the straight-line path has FUN variants for the lean single-cycle
-    // launches of PLAIN chains; every other launch of such a batch takes the general path
-    bool fun = false;
-    if (fastf && a.has_funnel) {
-        bool lean13 = false;
-        if constexpr (PL)
-            lean13 = (NS || a.flags == 0) && !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded && !a.q_lo && !a.q_ref_out &&
-                     !a.q_out && a.n_cycles == 0;
-        if (lean13) fun = true;
-        else { fastf = false; a.fast_order = -1; }
-    }
-    // decay orders that differ (between slots or arms): the MIXO variants serve the lean and the publishing-lean single-cycle launches
-    // of PLAIN chains, with or without the aux block; every other launch of such a batch takes the general path
-    bool mixo = false;
-    if (fastf && a.mixed) {
-        bool lean13 = false;
-        if constexpr (PL)
-            lean13 = (NS || a.flags == 0) && !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded && !a.q_lo && !a.q_ref_out &&
-                     !a.q_out && a.n_cycles == 0;
-        if (lean13) mixo = true;
-        else { fastf = false; fun = false; a.fast_order = -1; }
-    }
-    if (fastf) a.slots_used = a.slots_used_fast;  // (the straight-line path counts the slots of the compact image)
-    // every decay repeller of the batch with one safe distance and one force (what the object feeder sends): the lean single-cycle
-    // variants read the uniform image -- one quad per slot, the pair in the constants (cycle_body, UNI)
-    const bool uni = fastf && !fun && !mixo && a.uni;
-    // LEAN launches touch only the head of the region.  They ask for no more than that while the launch is at most one
-    // wave per SIMD (C5 -2 %, C3N -0.6 %, C3 +-0 at 65 536 arms); beyond, the full size keeps the launch in rounds of one
-    // wave per SIMD -- with eight waves resident per CU a 131 072-arm launch took 12.5 instead of 11.0 us (two waves
-    // per SIMD compete for the same HBM time; profiles/r02_batch_scaling.txt).
-    const size_t lds_lean = ((long)grid.x * (blk.x / 64) <= (long)a.n_simd) ? (size_t)(blk.x / 64) * Stage<T>::lean_bytes(NJ) : lds;
-    bool lean = false, lean_any = false;  // lean: on the straight-line field path; lean_any: whatever the field path
-    if constexpr (PL)
-        lean_any = (NS || a.flags == 0) && !a.tool_stride && !a.mixw && !a.wts && !a.null_control && !a.ext && !a.q_ref && !a.q_cmded &&
-               !a.qdot_vf && !a.qdot_null && !a.pose && !a.pose_nt && !a.v6 && !a.qdist && !a.goal_dist && !a.active && !a.q_lo &&
-               !a.q_ref_out;
-    lean = lean_any && fastf;
-    // In-kernel rollouts (ROLL) exist for PLAIN chains of up to 7 joints; with a tool, IK weights or prismatic joints the loop-carried
-    // state no longer fits the registers (12-268 B of scratch per lane until round 3) and the rollout is stepped by the host side
-    // (vfik_abi.cpp, launch_cycles), as for the long chains.
-    if constexpr (NJ <= VFIK_ROLL_MAX_NJ && PL) {
-        if (a.n_cycles > 0) {
-            if (lean) {
-                launch_full<T, NJ, NS, PL, true, true, 1, -1, false, false, false, false, DHP>(a, grid, blk, lds_lean, stream);
-                return;
-            }
-            if (fastf) launch_full<T, NJ, NS, PL, true, true, 0, -1, false, false, false, false, DHP>(a, grid, blk, lds, stream);
-            else launch_full<T, NJ, NS, PL, true, false, 0, -1, false, false, false, false, DHP>(a, grid, blk, lds, stream);
-            return;
-        }
-    }
-    bool small8 = false;   // a launch the eight-lanes kernel serves, at a size where it wins
-    if constexpr (PL && NJ <= (NS ? 7 : 8)) {
-        // small batches: eight lanes per arm (cycle_sub8_kernel) for the launches it serves -- the straight-line field path, no
-        // per-arm option, the outputs the per-arm processes publish every cycle.  VFIK_SUB8_MAX_BATCH = 0 switches it off.
-        const bool served = fastf && !fun && !mixo && !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded && !a.active && !a.q_lo &&
-                            !a.q_ref_out && !a.v6 && !a.goal_dist && !a.q_out && a.n_cycles == 0 && a.qdot_out &&
-                            (NS || (a.flags == 0 && !a.null_control));
-        // Adopted where the same-box A/B wins (profiles/r03_latency_small_*.txt, 1 ... 4 096 arms): launches that publish the
-        // per-cycle rows (pose, pose_no_tool, qdotOut, qdotout, qdist) -18 ... -22 % at every size; qdot_out alone without the
-        // nullspace module -4 ... -20 %; qdot_out alone WITH it -7 ... -11 % for a handful of arms, +-3 % from 64 arms on.
-        const bool rows = a.qdot_vf || a.qdot_null || a.pose || a.pose_nt || a.qdist;
-        const int cap = rows ? a.sub8_max_batch_full : (NS ? a.sub8_max_batch_ns : a.sub8_max_batch);
-        small8 = served && a.B <= cap;   // (with a shared tool / shared IK weights: the option block below launches this kernel's variants)
-        if (served && a.B <= cap && a.plain == 1) {
-            const dim3 g8((a.B + 7) / 8), b8(64);
-            // (with the nullspace module the scalar entry measures 1-2 % SLOWER -- one arm 5.83 against 5.73 us, C2F 7.17 against 7.07 --
-            // with or without a batch fetch of the block's other members: that variant keeps the block entry)
-            if constexpr (VFIK_SCALAR_KERNARG && !NS)
-                hipLaunchKernelGGL((cycle_sub8_kernel_x<T, NJ, NS, DHP>), g8, b8, 8 * 1024, stream, (const void*)a.arena, a.q, a.qdot_out, a.null_control, a.slots, a.B, a.Bpad,
-                                   a.slots_used, a.flags, a);
-            else
-                hipLaunchKernelGGL((cycle_sub8_kernel<T, NJ, NS, DHP>), g8, b8, 8 * 1024, stream, a);
-            if (sub8) *sub8 = 1;
-            return;
-        }
-    }
-    if constexpr (PL) {
-        if (a.plain >= 2) {
-            // The batch's shared options on the kernels built for plain chains: ONE tool for the batch (`set tool`, old/README.old:84;
-            // a.plain - 1 bit 0) and / or IK weights other than one (/weight, vf:295-309; bit 1).  The lean and the publishing-lean
-            // single-cycle float32 launches on the straight-line path -- what the default process set asks of an array caller and of
-            // ControlCycleBatch -- and the eight-lanes kernel (both I/O types) have variants that apply them (cycle_body / cycle_sub8_body:
-            // TOOLC = DHP bit 1, WTSC = DHP bit 2, the latter for chains of up to 7 joints; run-time flags; with the uniform image, the aux
-            // block, the order planes), for the chain's DH pattern where one is built for the joint count.  Every other launch of such a
-            // handle (float64 I/O beyond the eight-lanes sizes, a rollout, per-arm options, the general field path, a chain off its
-            // pattern) takes the general variants, as until round 4.
-            constexpr bool PAT = DHP == (DhPattern<NJ, 1>::SWAP != 0 ? 1 : 0);
-            auto launch_opt = [&](auto dt) -> bool {
-                constexpr int DT = decltype(dt)::value;
-                if constexpr (PL && NJ <= (NS ? 7 : 8)) {
-                    if (small8) {
-                        const dim3 g8((a.B + 7) / 8), b8(64);
-                        if constexpr (VFIK_SCALAR_KERNARG && !NS)
-                            hipLaunchKernelGGL((cycle_sub8_kernel_x<T, NJ, NS, DT>), g8, b8, 8 * 1024, stream, (const void*)a.arena, a.q, a.qdot_out, a.null_control, a.slots, a.B,
-                                               a.Bpad, a.slots_used, a.flags, a);
-                        else
-                            hipLaunchKernelGGL((cycle_sub8_kernel<T, NJ, NS, DT>), g8, b8, 8 * 1024, stream, a);
-                        if (sub8) *sub8 = 1;
-                        return true;
-                    }
+    // UNI variants read the uniform repeller image, a.uni_planes quad planes behind the compact one: the offset rides in the upper bits of
+    // fast_order (KLean's fourteen dwords are all taken)
+    a.fast_order = p.uni ? (p.fast_order & 255) | (a.uni_planes << 8) : p.fast_order;
+    a.slots_used = p.slots_used;
+    a.block = p.block;
+    const dim3 grid(p.grid), blk(p.block);
+    bool launched = false;
+    // cycle_kernel_s: the lean single-cycle straight-line variants (the diagnostic stamps build gives them the whole block: cycle_kernel_x)
+    auto lean_s = [&](auto CF, auto PERS, auto FUN, auto WAVES, auto UNI, auto D) {
+        if constexpr (SmallArgs<1, false, true>::value)
+            hipLaunchKernelGGL((cycle_kernel_s<T, NJ, NS, true, false, true, 1, VFIK_V(CF), VFIK_V(PERS), VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>), grid, blk, p.lds,
+                               stream, a.arena, a.q, a.qdot_out, a.status, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block);
+        else
+            launch_x<T, NJ, NS, true, false, true, 1, VFIK_V(CF), VFIK_V(PERS), VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
+        launched = true;
+    };
+    switch (p.family) {
+    case CycleFamily::Sub8:
+        if constexpr (NJ <= (NS ? 7 : 8)) {
+            as_dhp(p.dhp, [&](auto D) {
+                if constexpr (dhp_sub8<NJ>(VFIK_V(D))) {
+                    // (with the nullspace module the scalar entry measures 1-2 % SLOWER -- one arm 5.83 against 5.73 us, C2F 7.17 against 7.07 --
+                    // with or without a batch fetch of the block's other members: that variant keeps the block entry)
+                    if constexpr (NS)
+                        hipLaunchKernelGGL((cycle_sub8_kernel<T, NJ, NS, VFIK_V(D)>), grid, blk, p.lds, stream, a);
+                    else
+                        hipLaunchKernelGGL((cycle_sub8_kernel_x<T, NJ, NS, VFIK_V(D)>), grid, blk, p.lds, stream, a.arena, a.q, a.qdot_out, a.null_control, a.slots, a.B,
+                                           a.Bpad, a.slots_used, a.flags, a);
+                    launched = true;
                 }
-                if constexpr (sizeof(T) == 4) {
-                    const bool lean1 = lean && !a.q_out && a.n_cycles == 0;
-                    const bool lean3 = fastf && (NS || a.flags == 0) && !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded &&
-                                       !a.q_lo && !a.q_ref_out && !a.q_out && a.n_cycles == 0;
-                    if (!(lean1 || lean3)) return false;
-                    if (mixo) {
-                        const dim3 g64((unsigned)((a.B + 63) / 64)), b64(64);
-                        size_t lds_m = (long)g64.x <= (long)a.n_simd ? Stage<T>::lean_bytes(NJ) : Stage<T>::bytes(NJ);
-                        if (fun) lds_m = std::max(lds_m, (size_t)(Stage<T>::lean_bytes(NJ) + 6 * Stage<T>::QSTEP));
-                        lds_m += 1024;
-                        a.block = 64;
-#define VFIK_LAUNCH_MT(LEANV, FUNV)                                                                                                         \
-    hipLaunchKernelGGL((cycle_kernel_m<T, NJ, NS, LEANV, FUNV, DT>), g64, b64, lds_m, stream, (const void*)a.arena, a.q, a.qdot_out, a.active, a.orders, a.B, \
-                       a.Bpad, a.slots_used, a.flags, a)
-                        if (lean1 && fun) VFIK_LAUNCH_MT(1, true);
-                        else if (lean1) VFIK_LAUNCH_MT(1, false);
-                        else if (fun) VFIK_LAUNCH_MT(3, true);
-                        else VFIK_LAUNCH_MT(3, false);
-#undef VFIK_LAUNCH_MT
-                        return true;
-                    }
-                    const size_t lds_funt = std::max(lds_lean, (size_t)(blk.x / 64) * (Stage<T>::lean_bytes(NJ) + 6 * Stage<T>::QSTEP));
-                    if (lean1) {
-                        if (fun) launch_lean<T, NJ, NS, PL, -1, false, true, 1, false, DT>(a, grid, blk, lds_funt, stream);
-                        else if (uni) launch_lean<T, NJ, NS, PL, -1, false, false, 1, true, DT>(a, grid, blk, lds_lean, stream);
-                        else launch_lean<T, NJ, NS, PL, -1, false, false, 1, false, DT>(a, grid, blk, lds_lean, stream);
-                    } else {
-                        if (fun) launch_full<T, NJ, NS, PL, false, true, 3, -1, false, true, false, false, DT>(a, grid, blk, lds_funt, stream);
-                        else if (uni) launch_full<T, NJ, NS, PL, false, true, 3, -1, false, false, true, false, DT>(a, grid, blk, lds_lean, stream);
-                        else launch_full<T, NJ, NS, PL, false, true, 3, -1, false, false, false, false, DT>(a, grid, blk, lds_lean, stream);
-                    }
-                    return true;
-                }
-                return false;
-            };
-            if constexpr (PAT) {
-                bool done = false;
-                const int opt = a.plain - 1;   // bit 0: shared tool, bit 1: shared IK weights
-                if (opt == 1) done = launch_opt(std::integral_constant<int, DHP | 2>());
-                if constexpr (NJ <= 7) {
-                    if (opt == 2) done = launch_opt(std::integral_constant<int, DHP | 4>());
-                    if (opt == 3) done = launch_opt(std::integral_constant<int, DHP | 6>());
-                }
-                if (done) return;
-            }
-            launch_v<T, NJ, NS, false, 0>(a_in, grid, blk, lds, stream, sub8);
-            return;
+            });
         }
-    }
-    if constexpr (PL) {
-        if (mixo) {   // (run-time flags: the compile-time flag sets of the default process set are worth ~1 % and a dozen more kernels)
-            const bool lean1 = lean_any && !a.q_out;
-            const dim3 g64((unsigned)((a.B + 63) / 64)), b64(64);    // one wave per block (cycle_kernel_m)
-            size_t lds_m = (long)g64.x <= (long)a.n_simd ? Stage<T>::lean_bytes(NJ) : Stage<T>::bytes(NJ);   // (beyond one wave per SIMD: rounds, as above)
-            if (fun) lds_m = std::max(lds_m, (size_t)(Stage<T>::lean_bytes(NJ) + 6 * Stage<T>::QSTEP));
-            lds_m += 1024;
-            a.block = 64;
-#define VFIK_LAUNCH_M(LEANV, FUNV)                                                                                                              \
-    hipLaunchKernelGGL((cycle_kernel_m<T, NJ, NS, LEANV, FUNV, dhp_of<T, PL, false, true, LEANV, false, NJ>(DHP)>), g64, b64, lds_m, stream, (const void*)a.arena, a.q, a.qdot_out, a.active, a.orders, a.B, \
-                       a.Bpad, a.slots_used, a.flags, a)
-            if (lean1 && fun) VFIK_LAUNCH_M(1, true);
-            else if (lean1) VFIK_LAUNCH_M(1, false);
-            else if (fun) VFIK_LAUNCH_M(3, true);
-            else VFIK_LAUNCH_M(3, false);
-#undef VFIK_LAUNCH_M
-            return;
-        }
-    }
-    if constexpr (PL && sizeof(T) == 4 && NJ <= 7) {
-        // Batches beyond one wave per SIMD: the persistent launch -- one wave per SIMD, each striding over the 64-arm chunks
-        // with the next chunk's inputs in flight under the current chunk's arithmetic (cycle_kernel, PERS).  Two per-arm
-        // areas per wave: lean_bytes + kin_off = 37.5 KB for 7 joints, four waves per CU.
-        const long nchunks = (a.B + 63) / 64;
-        if (lean && !fun && !a.q_out && a.n_cycles == 0 && a.pers && nchunks > (long)a.n_simd) {
-            const dim3 gp((unsigned)a.n_simd), bp(64);
-            const size_t lds_p = Stage<T>::lean_bytes(NJ) + Stage<T>::kin_off(NJ);
-            launch_lean<T, NJ, NS, PL, -1, true, false, 1, false, DHP>(a, gp, bp, lds_p, stream);
-            return;
-        }
-    }
-    // (FUN launches: the lean region + the aux block's six rows per wave; beyond one wave per SIMD the full region, as above)
-    const size_t lds_fun = std::max(lds_lean, (size_t)(blk.x / 64) * (Stage<T>::lean_bytes(NJ) + 6 * Stage<T>::QSTEP));
-    if constexpr (PL) {
-        if (fun && lean && !a.q_out) {
-            launch_lean<T, NJ, NS, PL, -1, false, true, 1, false, DHP>(a, grid, blk, lds_fun, stream);
-            return;
-        }
-        if (lean && !a.q_out) {
-            // (chains of up to 7 joints: C3N -1 %; the 14-joint kernel got 10 % SLOWER with its flags fixed -- the
-            // compiler then hoists the joint-limit task's constants over the whole kernel -- and keeps them run-time)
-            if constexpr (sizeof(T) == 4 && NJ <= 7) {
-                // beyond one wave per SIMD: the two-waves-per-SIMD build, two blocks' lean regions resident per CU
-                // (with the nullspace module only on the uniform repeller image: the compact-image variants of that build spilled 6 registers
-                // per lane for 2-6 % -- they stay in rounds of one wave per SIMD)
-                if (a.waves2 && (long)grid.x * (blk.x / 64) > (long)a.n_simd && (!NS || uni)) {
-                    const size_t lds2 = (size_t)(blk.x / 64) * Stage<T>::lean_bytes(NJ);
-                    constexpr int NSMIX = VFIK_F_NULLSPACE | VFIK_F_MIXER, NSJLMIX = NSMIX | VFIK_F_JOINT_LIMIT_TASK;
-                    if constexpr (NS) {
-                        if (a.flags == (unsigned)NSMIX) launch_lean<T, NJ, NS, PL, NSMIX, false, false, 2, true, DHP>(a, grid, blk, lds2, stream);
-                        else if (a.flags == (unsigned)NSJLMIX) launch_lean<T, NJ, NS, PL, NSJLMIX, false, false, 2, true, DHP>(a, grid, blk, lds2, stream);
-                        else launch_lean<T, NJ, NS, PL, -1, false, false, 2, true, DHP>(a, grid, blk, lds2, stream);
-                    } else {
-                        if (uni) launch_lean<T, NJ, NS, PL, -1, false, false, 2, true, DHP>(a, grid, blk, lds2, stream);
-                        else launch_lean<T, NJ, NS, PL, -1, false, false, 2, false, DHP>(a, grid, blk, lds2, stream);
-                    }
-                    return;
+        break;
+    case CycleFamily::Lean:
+    case CycleFamily::PublishingLean:
+        as_dhp(p.dhp, [&](auto D) { as_cf(p.cf, [&](auto CF) { as_bool(p.fun, [&](auto FUN) { as_bool(p.uni, [&](auto UNI) {
+            if constexpr (lean_built<T, NJ, NS, VFIK_V(CF), VFIK_V(FUN), VFIK_V(UNI), VFIK_V(D)>()) {
+                if (p.lean == 1) {
+                    lean_s(CF, bool_c<false>(), FUN, int_c<1>(), UNI, D);
+                } else {
+                    launch_x<T, NJ, NS, true, false, true, 3, VFIK_V(CF), false, VFIK_V(FUN), 1, VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
+                    launched = true;
                 }
             }
-            if constexpr (NS && NJ <= 7) {  // the flag sets of the default process set, as compile-time constants
-                constexpr int NSMIX = VFIK_F_NULLSPACE | VFIK_F_MIXER, NSJLMIX = NSMIX | VFIK_F_JOINT_LIMIT_TASK;
-                if (a.flags == (unsigned)NSMIX) {
-                    { if (uni) launch_lean<T, NJ, NS, PL, NSMIX, false, false, 1, true, DHP>(a, grid, blk, lds_lean, stream); else launch_lean<T, NJ, NS, PL, NSMIX, false, false, 1, false, DHP>(a, grid, blk, lds_lean, stream); }
-                    return;
-                }
-                if (a.flags == (unsigned)NSJLMIX) {
-                    { if (uni) launch_lean<T, NJ, NS, PL, NSJLMIX, false, false, 1, true, DHP>(a, grid, blk, lds_lean, stream); else launch_lean<T, NJ, NS, PL, NSJLMIX, false, false, 1, false, DHP>(a, grid, blk, lds_lean, stream); }
-                    return;
-                }
+        }); }); }); });
+        break;
+    case CycleFamily::LeanPersistent:
+        if constexpr (sizeof(T) == 4 && NJ <= 7) lean_s(int_c<-1>(), bool_c<true>(), bool_c<false>(), int_c<1>(), bool_c<false>(), int_c<0>());
+        break;
+    case CycleFamily::LeanTwoWaves:   // (with the nullspace module on the uniform image only; on the compact image without the pattern)
+        if constexpr (sizeof(T) == 4 && NJ <= 7) {
+            as_dhp(p.dhp, [&](auto D) { as_cf(p.cf, [&](auto CF) { as_bool(p.uni, [&](auto UNI) {
+                if constexpr (VFIK_V(D) <= 1 && (VFIK_V(UNI) ? (VFIK_V(CF) == -1 || NS) : (!NS && VFIK_V(D) == 0 && VFIK_V(CF) == -1)))
+                    lean_s(CF, bool_c<false>(), bool_c<false>(), int_c<2>(), UNI, D);
+            }); }); });
+        }
+        break;
+    case CycleFamily::Mixo:
+        as_dhp(p.dhp, [&](auto D) { as_int<1, 3>(p.lean, [&](auto LEAN) { as_bool(p.fun, [&](auto FUN) {
+            if constexpr (dhp_lean<T, NJ>(VFIK_V(D))) {
+                // the order planes' address among the preloaded scalars: it is needed in the request phase
+                hipLaunchKernelGGL((cycle_kernel_m<T, NJ, NS, VFIK_V(LEAN), VFIK_V(FUN), VFIK_V(D)>), grid, blk, p.lds, stream, a.arena, a.q, a.qdot_out, a.active, a.orders,
+                                   a.B, a.Bpad, a.slots_used, a.flags, a);
+                launched = true;
             }
-            { if (uni) launch_lean<T, NJ, NS, PL, -1, false, false, 1, true, DHP>(a, grid, blk, lds_lean, stream); else launch_lean<T, NJ, NS, PL, -1, false, false, 1, false, DHP>(a, grid, blk, lds_lean, stream); }
-            return;
+        }); }); });
+        break;
+    case CycleFamily::Rollout:
+        if constexpr (NJ <= VFIK_ROLL_MAX_NJ) {
+            as_bool(p.fastf, [&](auto FASTF) { launch_x<T, NJ, NS, true, true, VFIK_V(FASTF), 0, -1, false, false, 1, false, 0>(a, p, stream); });
+            launched = true;
         }
-        if constexpr (NJ > VFIK_ROLL_MAX_NJ) {  // a cycle of a stepped rollout: lean, but it integrates q on the way out
-            if (lean) {
-                launch_full<T, NJ, NS, PL, false, true, 2, -1, false, false, false, false, DHP>(a, grid, blk, lds_lean, stream);
-                return;
-            }
-        }
-    }
-    if constexpr (PL) {
-        // publishing lean launches (LEAN 3): the straight-line path, no per-arm option, single cycle
-        const bool lean3 = fastf && (NS || a.flags == 0) && !a.tool_stride && !a.mixw && !a.wts && !a.ext && !a.q_ref && !a.q_cmded &&
-                           !a.q_lo && !a.q_ref_out && !a.q_out && a.n_cycles == 0;
-        if (lean3 && fun) {
-            launch_full<T, NJ, NS, PL, false, true, 3, -1, false, true, false, false, DHP>(a, grid, blk, lds_fun, stream);
-            return;
-        }
-        if (lean3) {
-            if constexpr (NS && NJ <= 7) {
-                constexpr int NSMIX = VFIK_F_NULLSPACE | VFIK_F_MIXER, NSJLMIX = NSMIX | VFIK_F_JOINT_LIMIT_TASK;
-                if (a.flags == (unsigned)NSMIX) {
-                    { if (uni) launch_full<T, NJ, NS, PL, false, true, 3, NSMIX, false, false, true, false, DHP>(a, grid, blk, lds_lean, stream); else launch_full<T, NJ, NS, PL, false, true, 3, NSMIX, false, false, false, false, DHP>(a, grid, blk, lds_lean, stream); }
-                    return;
+        break;
+    case CycleFamily::RolloutLean:
+        if constexpr (NJ <= VFIK_ROLL_MAX_NJ) {
+            as_dhp(p.dhp, [&](auto D) {
+                if constexpr (dhp_plain<T, NJ>(VFIK_V(D))) {
+                    launch_x<T, NJ, NS, true, true, true, 1, -1, false, false, 1, false, VFIK_V(D)>(a, p, stream);
+                    launched = true;
                 }
-                if (a.flags == (unsigned)NSJLMIX) {
-                    { if (uni) launch_full<T, NJ, NS, PL, false, true, 3, NSJLMIX, false, false, true, false, DHP>(a, grid, blk, lds_lean, stream); else launch_full<T, NJ, NS, PL, false, true, 3, NSJLMIX, false, false, false, false, DHP>(a, grid, blk, lds_lean, stream); }
-                    return;
+            });
+        }
+        break;
+    case CycleFamily::SteppedCycle:
+        if constexpr (NJ > VFIK_ROLL_MAX_NJ) {
+            as_dhp(p.dhp, [&](auto D) {
+                if constexpr (dhp_plain<T, NJ>(VFIK_V(D))) {
+                    launch_x<T, NJ, NS, true, false, true, 2, -1, false, false, 1, false, VFIK_V(D)>(a, p, stream);
+                    launched = true;
                 }
-            }
-            { if (uni) launch_full<T, NJ, NS, PL, false, true, 3, -1, false, false, true, false, DHP>(a, grid, blk, lds_lean, stream); else launch_full<T, NJ, NS, PL, false, true, 3, -1, false, false, false, false, DHP>(a, grid, blk, lds_lean, stream); }
-            return;
+            });
         }
-    }
-    if constexpr (PL) {
-        // the general field path (funnel / hemisphere / further attractors, mixed decay orders -- a goalAndNormal scene,
-        // object_feeder:248-303) with nothing but q -> qdot_out asked for: its own LEAN variant (the optional inputs and
-        // outputs as compile-time nulls free the registers the 14-joint kernel otherwise spills)
-        if (lean_any && !fastf && !a.q_out) {
-            launch_full<T, NJ, NS, PL, false, false, 1, -1, false, false, false, false, DHP>(a, grid, blk, lds, stream);
-            return;
-        }
-    }
-    // The non-lean single-cycle variants.  Those of the long chains sit at the register file's limit (512 per lane, the Jacobian alone
-    // is 168) and are compiled as an object of their own with its own scheduling and allocation flags (Makefile, HEAVY): with the
-    // flags that suit the lean kernels five of them spilled 12-128 B per lane.
+        break;
+    case CycleFamily::GeneralLean:
+        launch_x<T, NJ, NS, true, false, false, 1, -1, false, false, 1, false, 0>(a, p, stream);
+        launched = true;
+        break;
+    case CycleFamily::Full:
 #if defined(VFIK_ONLY_NJ) && VFIK_ONLY_NJ >= VFIK_HEAVY_MIN_NJ && !defined(VFIK_HEAVY_PART)
-    VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(sizeof(T) == 4 ? 32 : 64, NS, PL, fastf, a, grid, blk, lds, stream);
+        VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(sizeof(T) == 4 ? 32 : 64, NS, a, p, stream);
 #else
-    if (fastf) launch_full<T, NJ, NS, PL, false, true, 0, -1, false, false, false, false, DHP>(a, grid, blk, lds, stream);
-    else launch_full<T, NJ, NS, PL, false, false, 0, -1, false, false, false, false, DHP>(a, grid, blk, lds, stream);
+        launch_full<T, NJ, NS>(a, p, stream);
 #endif
-}
-
-template <typename T, int NJ, bool NS>   // NS: the launch's flags carry VFIK_F_NULLSPACE (decided by the caller: one object per (n, T, NS))
-hipError_t launch_t(const KArgs& a0, int block, hipStream_t stream, int* sub8) {
-    KArgs a = a0;
-    // (VFIK_BLOCK is a tuning knob: a block's waves must fit the CU's 160 KB of LDS with their regions)
-    // A full region that does not fit the CU four times (float64 I/O from 10 joints on: 42-44 KB) would leave one SIMD of every CU idle
-    // and run a 65 536-arm launch in two rounds.  Such launches go as one wave per block, each block asking for the part of the region
-    // its options use: the rows of a per-arm tool and of per-arm mixer weights are the region's tail (14 joints, float64: 34 of 44 KB
-    // without them, four blocks per CU again -- 34.3 -> 17 us with a shared tool, profiles/r04_heavy_variants.txt).
-    size_t lds;
-    if (4 * (size_t)Stage<T>::bytes(NJ) > 160u * 1024u) {
-        block = 64;
-        lds = (a.tool_stride || a.mixw) ? Stage<T>::bytes(NJ) : Stage<T>::tool_off(NJ);
-    } else {
-        while (block > 64 && (size_t)(block / 64) * Stage<T>::bytes(NJ) > 160u * 1024u) block -= 64;
-        lds = (size_t)(block / 64) * Stage<T>::bytes(NJ);
+        launched = true;
+        break;
+    case CycleFamily::Refused:
+        return hipErrorInvalidValue;   // (stepped by the caller: vfik_abi.cpp, launch_cycles)
     }
-    a.block = block;
-    const dim3 grid((a.B + block - 1) / block), blk(block);
-    if (a.n_cycles > 0 && (a.plain != 1 || NJ > VFIK_ROLL_MAX_NJ)) return hipErrorInvalidValue;   // (stepped by the caller: launch_cycles; a tool too -- the rollout variants have no register to spare for it)
-    if (a.plain) {
-        if constexpr (DhPattern<NJ, 1>::SWAP != 0) {   // (float64 I/O: only the eight-lanes kernel has pattern variants, dhp_of)
-            if (a.dhp == 1) {   // the chain matches the DH pattern built for this joint count (vfik_abi.cpp: upload_kconst)
-                launch_v<T, NJ, NS, true, 1>(a, grid, blk, lds, stream, sub8);
-                return hipGetLastError();
-            }
-        }
-        launch_v<T, NJ, NS, true>(a, grid, blk, lds, stream, sub8);
-    } else {
-        launch_v<T, NJ, NS, false>(a, grid, blk, lds, stream, sub8);
-    }
+    if (!launched) return hipErrorInvalidDeviceFunction;   // a plan no built variant serves
     return hipGetLastError();
 }
 
@@ -3452,24 +3116,16 @@ hipError_t launch_t(const KArgs& a0, int block, hipStream_t stream, int* sub8) {
 // The library is built from this one source compiled several times (csrc/Makefile): per joint count, I/O type and with / without the
 // nullspace module with -DVFIK_ONLY_NJ=<n> -DVFIK_ONLY_T=<32|64> -DVFIK_ONLY_NS=<0|1> (the kernels of that combination, in parallel make
 // jobs: sixteen objects of 20-70 kernels each instead of four of 85-160), once per long chain with -DVFIK_HEAVY_PART, and once with
-// -DVFIK_DISPATCH (launch dispatch, mixer kernel, host-side constant preparation).
+// -DVFIK_DISPATCH (the launch plan's dispatch, mixer kernel, host-side constant preparation).
 #ifdef VFIK_ONLY_NJ
 #ifdef VFIK_HEAVY_PART
 // -DVFIK_ONLY_NJ=<n> -DVFIK_HEAVY_PART: the non-lean single-cycle variants of a long chain, and nothing else
-void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, bool plain, bool fastf, const KArgs& a, dim3 grid, dim3 blk, size_t lds, hipStream_t stream) {
-#define VFIK_HEAVY(T, NS, PL)                                                                                                      \
-    do {                                                                                                                            \
-        if (fastf) launch_full<T, VFIK_ONLY_NJ, NS, PL, false, true, 0, -1, false, false, false, false, 0>(a, grid, blk, lds, stream);  \
-        else launch_full<T, VFIK_ONLY_NJ, NS, PL, false, false, 0, -1, false, false, false, false, 0>(a, grid, blk, lds, stream);       \
-    } while (0)
+void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, const KArgs& a, const CyclePlan& p, hipStream_t stream) {
     if (io_dtype == 32) {
-        if (ns) { if (plain) VFIK_HEAVY(float, true, true); else VFIK_HEAVY(float, true, false); }
-        else { if (plain) VFIK_HEAVY(float, false, true); else VFIK_HEAVY(float, false, false); }
+        if (ns) launch_full<float, VFIK_ONLY_NJ, true>(a, p, stream); else launch_full<float, VFIK_ONLY_NJ, false>(a, p, stream);
     } else {
-        if (ns) { if (plain) VFIK_HEAVY(double, true, true); else VFIK_HEAVY(double, true, false); }
-        else { if (plain) VFIK_HEAVY(double, false, true); else VFIK_HEAVY(double, false, false); }
+        if (ns) launch_full<double, VFIK_ONLY_NJ, true>(a, p, stream); else launch_full<double, VFIK_ONLY_NJ, false>(a, p, stream);
     }
-#undef VFIK_HEAVY
 }
 #else
 #if VFIK_ONLY_T == 32
@@ -3478,18 +3134,18 @@ typedef float VfikOnlyT;
 typedef double VfikOnlyT;
 #endif
 #define VFIK_PART_NAME VFIK_CAT(VFIK_CAT(VFIK_CAT(VFIK_CAT(VFIK_CAT(launch_cycle_nj, VFIK_ONLY_NJ), _t), VFIK_ONLY_T), _ns), VFIK_ONLY_NS)
-hipError_t VFIK_PART_NAME(const KArgs& kargs, int block, hipStream_t stream, int* sub8) {
-    return launch_t<VfikOnlyT, VFIK_ONLY_NJ, VFIK_ONLY_NS != 0>(kargs, block, stream, sub8);
+hipError_t VFIK_PART_NAME(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream) {
+    return launch_plan<VfikOnlyT, VFIK_ONLY_NJ, VFIK_ONLY_NS != 0>(kargs, plan, stream);
 }
 #endif
 }  // namespace vfik
 #else  // VFIK_DISPATCH
 
 #define X(n)                                                                                                      \
-    hipError_t launch_cycle_nj##n##_t32_ns0(const KArgs& kargs, int block, hipStream_t stream, int* sub8);       \
-    hipError_t launch_cycle_nj##n##_t32_ns1(const KArgs& kargs, int block, hipStream_t stream, int* sub8);       \
-    hipError_t launch_cycle_nj##n##_t64_ns0(const KArgs& kargs, int block, hipStream_t stream, int* sub8);       \
-    hipError_t launch_cycle_nj##n##_t64_ns1(const KArgs& kargs, int block, hipStream_t stream, int* sub8);
+    hipError_t launch_cycle_nj##n##_t32_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t32_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t64_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t64_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);
 VFIK_NJ_LIST
 #undef X
 
@@ -3613,7 +3269,7 @@ double kconst_fill_t(void* dst, const vfik_chain& ch, const vfik_params& p, cons
     // PLAIN variant of the kernel: revolute joints only, no trailing screw.  *plain: 0 general variants; else 1 + (the batch's shared tool
     // is not the identity ? 1 : 0) + (its IK weights are not all one ? 2 : 0): the lean float32 kernels and the eight-lanes kernel have
     // variants that apply a shared tool and shared weights themselves (cycle_body: TOOLC, WTSC), every other launch of such a handle takes
-    // the general variants (launch_v).
+    // the general variants (plan_cycle).
     bool pl = c.prismatic_mask == 0 && c.tail_c == 1.0 && c.tail_s == 0.0 && c.tail_e == 0.0;
     static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     bool tool_ident = true;
@@ -3664,11 +3320,13 @@ uint32_t supported_joints_mask() {
 
 hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, int* sub8) {
     const bool ns = kargs.flags & VFIK_F_NULLSPACE;
+    const CyclePlan plan = plan_cycle(kargs, nj, io_dtype, ns, block);
+    if (sub8 && plan.family == CycleFamily::Sub8) *sub8 = 1;
     switch (nj) {
 #define X(n)                                                                                                                        \
     case n:                                                                                                                         \
-        return io_dtype == 32 ? (ns ? launch_cycle_nj##n##_t32_ns1(kargs, block, stream, sub8) : launch_cycle_nj##n##_t32_ns0(kargs, block, stream, sub8))  \
-                              : (ns ? launch_cycle_nj##n##_t64_ns1(kargs, block, stream, sub8) : launch_cycle_nj##n##_t64_ns0(kargs, block, stream, sub8));
+        return io_dtype == 32 ? (ns ? launch_cycle_nj##n##_t32_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t32_ns0(kargs, plan, stream))  \
+                              : (ns ? launch_cycle_nj##n##_t64_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t64_ns0(kargs, plan, stream));
         VFIK_NJ_LIST
 #undef X
         default: return hipErrorInvalidValue;
