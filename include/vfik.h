@@ -95,7 +95,8 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
  * task-space weights -> wy[n_arms][6], 'j' + n joint-space weights -> wq[n_arms][n]; either may be NULL
  * (unchanged).  Arms never written use vfik_params.wy / wq; a later vfik_set_params that CHANGES wy or wq
  * is batch-wide again and replaces every arm's own weights.  A call for the WHOLE batch with both arrays whose rows are all equal is a
- * batch-wide setting too (stored in the handle's parameters, the arms' own weights dropped): batch-wide weights keep the launches of an
+ * batch-wide setting too (kept by the handle beside the caller's vfik_params, the arms' own weights dropped; a later vfik_set_params
+ * whose wy / wq equal what the caller passed last leaves them in force): batch-wide weights keep the launches of an
  * all-revolute chain of up to 7 joints on the kernels built for it, per-arm weights take the general variants. */
 int vfik_set_arm_weights(vfik_handle* h, int first_arm, int n_arms, const double* wy, const double* wq);
 
@@ -180,7 +181,10 @@ typedef struct vfik_io {
 
 /* One control cycle for the whole batch -- the loop bodies of vf:311-466, nullspace:162-184,
  * debug_jointlimits:61-73 and command_mixer.py:78-82 (+ bridge:188-195) in ONE kernel launch.
- * Device pointers; asynchronous on the handle's stream. */
+ * Device pointers; asynchronous on the handle's stream.  io->q may have any alignment of its element type: a q that is not
+ * 16-byte aligned is first copied (on the handle's stream) into an aligned buffer of the handle -- the kernels read q in whole
+ * 16-byte pieces.  That buffer is allocated at the first such call: a host that captures vfik_step / vfik_rollout with such a q
+ * makes one call outside the capture first.  The same holds for vfik_rollout. */
 int vfik_step(vfik_handle* h, const vfik_io* io);
 /* Same with host pointers: copies in, runs, copies out, synchronises. */
 int vfik_step_host(vfik_handle* h, const vfik_io* io);
@@ -273,6 +277,12 @@ int vfik_time_steps(vfik_handle* h, const vfik_io* io, int warmup, int steps, fl
  * so far. */
 int vfik_set_small_batch_kernel(vfik_handle* h, int max_batch);
 long vfik_small_batch_launches(vfik_handle* h);
+/* Introspection for tests: the cycle-kernel instantiations the handle's launches took since the last call, each once, as
+ * newline-terminated demangled names without namespace and parameter list (`cycle_kernel_x<float, 7, ...>`; the long chains'
+ * non-lean object adds " [heavy]").  A host-stepped rollout may name two: its intermediate cycles and its last.  Writes them to
+ * buf (len bytes, NUL included) and clears the record; returns the length of the list.  buf == NULL: the length alone, nothing
+ * cleared.  VFIK_E_ARG when len is too small, VFIK_E_STATE when more than 16 distinct kernels were launched since the last call. */
+int vfik_launched_kernels(vfik_handle* h, char* buf, int len);
 
 /* introspection for tests / DESIGN.md: slots in use, bytes of device state */
 int vfik_slots_in_use(vfik_handle* h);

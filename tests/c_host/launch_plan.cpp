@@ -11,35 +11,6 @@
 
 #include "../../vfclik_amd/csrc/vfik_kernel.h"
 
-using vfik::CycleFamily;
-
-static const char* b(bool v) { return v ? "true" : "false"; }
-
-// the demangled name of the instantiation (template arguments in the order the kernels declare them)
-static std::string kernel_name(const vfik::CyclePlan& p, int nj, int io_bits, bool ns) {
-    const char* t = io_bits == 32 ? "float" : "double";
-    char s[256];
-    switch (p.family) {
-        case CycleFamily::Refused: return "refused";
-        case CycleFamily::Sub8:
-            std::snprintf(s, sizeof s, "cycle_sub8_kernel%s<%s, %d, %s, %d>", ns ? "" : "_x", t, nj, b(ns), p.dhp);
-            return s;
-        case CycleFamily::Mixo:
-            std::snprintf(s, sizeof s, "cycle_kernel_m<%s, %d, %s, %d, %s, %d>", t, nj, b(ns), p.lean, b(p.fun), p.dhp);
-            return s;
-        case CycleFamily::Lean:
-        case CycleFamily::LeanPersistent:
-        case CycleFamily::LeanTwoWaves:
-            std::snprintf(s, sizeof s, "cycle_kernel_s<%s, %d, %s, true, false, true, 1, %d, %s, %s, %d, %s, %d>", t, nj, b(ns), p.cf, b(p.pers), b(p.fun), p.waves,
-                          b(p.uni), p.dhp);
-            return s;
-        default:
-            std::snprintf(s, sizeof s, "cycle_kernel_x<%s, %d, %s, %s, %s, %s, %d, %d, %s, %s, %d, %s, false, %d>%s", t, nj, b(ns), b(p.plain), b(p.roll), b(p.fastf),
-                          p.lean, p.cf, b(p.pers), b(p.fun), p.waves, b(p.uni), p.dhp, p.heavy ? " [heavy]" : "");
-            return s;
-    }
-}
-
 int main() {
     std::string line;
     while (std::getline(std::cin, line)) {
@@ -96,7 +67,7 @@ int main() {
         a.waves2 = (int)get("waves2", 0);
         const bool ns = a.flags & VFIK_F_NULLSPACE;
         const vfik::CyclePlan p = vfik::plan_cycle(a, nj, io, ns, block);
-        std::printf("%s grid=%u block=%u lds=%zu\n", kernel_name(p, nj, io, ns).c_str(), p.grid, p.block, p.lds);
+        std::printf("%s grid=%u block=%u lds=%zu\n", vfik::cycle_kernel_name(p, nj, io, ns).c_str(), p.grid, p.block, p.lds);
     }
     return 0;
 }

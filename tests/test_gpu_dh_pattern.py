@@ -3,9 +3,13 @@ that match the built pattern of their joint count take variants in which links w
 arithmetic; every other chain the general DH form.  Both against the oracle, and against each other."""
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_variants as kv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +36,10 @@ def _step(env, chain, params, w, want, nrep, off=False):
     eng.set_fields(w["fields"], w["nfields"])
     pat = eng.dh_pattern
     out = eng.step_host(w["q"], want=want)
+    launched = eng.launched_kernels()
     eng.close()
+    # the kernel that ran carries the pattern exactly when the handle reports it
+    assert launched and all(kv.parse(k).args["D"] & 1 == pat for k in launched), (pat, launched)
     return out, pat
 
 

@@ -51,12 +51,20 @@ def test_persistent_launch_matches_oracle_and_rounds(env, B, nobs):
     params = env.abi.default_params()
     w = env.synth.make_workload(chain, B, nobs, seed=21, io_dtype=np.float32)
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], want=("qdot_out", "status"))
-    outs = {}
+    outs, kernels = {}, {}
     for mode in MODES:
         eng = _engine(env, chain, B, nobs, params, mode)
         eng.set_fields(w["fields"], w["nfields"])
         outs[mode] = eng.step_host(w["q"], want=("qdot_out", "status"))
+        kernels[mode] = eng.launched_kernels()
         eng.close()
+    # each mode took its own kernel: the lean variant of WAVES 1 (rounds), 2, or the persistent one (PERS)
+    for mode in MODES:
+        assert len(kernels[mode]) == 1, (mode, kernels[mode])
+        k = kernels[mode].pop()
+        assert k.startswith("cycle_kernel_s<float, 7, false,"), (mode, k)
+        pers, waves = k.split(", ")[8], k.split(", ")[10]
+        assert (pers, waves) == {"rounds": ("false", "1"), "two": ("false", "2"), "pers": ("true", "1")}[mode], (mode, k)
     for mode in MODES:
         err = np.abs(outs[mode]["qdot_out"].astype(np.float64) - ref["qdot_out"])
         assert err.max() < 1e-6, (mode, float(err.max()), int(np.argmax(err.max(axis=1))))
@@ -77,7 +85,9 @@ def test_two_waves_build_of_the_other_lean_variants(env, robot, flags):
     eng = _engine(env, chain, B, 5, params, "two")
     eng.set_fields(w["fields"], w["nfields"])
     got = eng.step_host(w["q"], want=("qdot_out", "status"))
+    (k,) = eng.launched_kernels()
     eng.close()
+    assert k.startswith("cycle_kernel_s<") and k.split(", ")[10] == "2", k   # (WAVES 2)
     assert np.abs(got["qdot_out"].astype(np.float64) - ref["qdot_out"]).max() < 2e-6
     assert np.array_equal(got["status"], ref["status"])
 
@@ -107,6 +117,8 @@ def test_big_launch_with_the_nullspace_module_keeps_its_state(env, mode):
         st = torch.zeros(B, dtype=torch.int32, device="cuda")
         eng.step(eng.make_io(qd, qdot_out=out, status=st))
         torch.cuda.synchronize()
+        (k,) = eng.launched_kernels()
+        assert k.startswith("cycle_kernel_s<float, 7, true,") and (k.split(", ")[8], k.split(", ")[10]) == (("true", "1") if mode == "pers" else ("false", "2")), k
         ref = env.oc.cycle_batch(chain, params, q32.astype(np.float64), w["fields"], w["nfields"], states=states, want=("qdot_out", "status"))
         err = np.abs(out.cpu().numpy().astype(np.float64) - ref["qdot_out"])
         assert err.max() < 1e-6, (t, float(err.max()))

@@ -3,8 +3,14 @@ arm with a hand on it -- `set tool` of old/README.old:84, scripts/vf:321-332 -- 
 variants.  Parity with the CPU oracle for every kernel family a launch with a tool can reach: lean (qdot_out only), publishing lean
 (every per-cycle row, /pose_no_tool recomposed from the tool pose), with the aux block and with differing decay orders, the
 eight-lanes size (served by one lane per arm: that kernel has no tool), the stepped rollout, both chains, both I/O types."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_variants as kv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +39,18 @@ def _tool(rot=True):
         c, s = np.cos(0.3), np.sin(0.3)
         t[:3, :3] = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) @ np.array([[1, 0, 0], [0, np.cos(0.2), -np.sin(0.2)], [0, np.sin(0.2), np.cos(0.2)]])
     return t.reshape(16)
+
+
+def _ran(eng, bits, general=False):
+    """The launches since the last call took PLAIN variants whose DH-pattern argument carries `bits` (1 pattern, 2 shared tool, 4 shared
+    IK weights) -- or, general=True, the general variants."""
+    launched = [kv.parse(k) for k in eng.launched_kernels()]
+    assert launched
+    for v in launched:
+        if general:
+            assert v.kernel == "cycle_kernel_x" and not v.args["PL"], v.name
+        else:
+            assert v.args.get("PL", True) and v.args["D"] & 7 == bits, (v.name, bits)
 
 
 def _check(got, ref, tol, keys):
@@ -67,12 +85,16 @@ def test_shared_tool_on_the_plain_variants(env, robot, B, nobs, dt, tol, flags, 
     assert eng.field_path == 1
     assert eng.dh_pattern == 1, "a tool must not take the chain off the DH-pattern kernels"
     got = eng.step_host(w["q"], want=want)
+    # float32 I/O: the pattern and the shared tool's variants; float64 I/O has them only on the eight-lanes kernel (v6: not served there)
+    _ran(eng, 3, general=dt == np.float64)
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], tool=tool)
     _check(got, ref, tol, want)
     assert np.linalg.norm(ref["pose"][:, [3, 7, 11]] - ref["pose_nt"][:, [3, 7, 11]], axis=1).min() > 0.15   # (the tool is really on)
     # back to no tool: the same handle, the same kernels
     eng.set_tool(np.eye(4).reshape(16))
     got = eng.step_host(w["q"], want=want)
+    if dt == np.float32:
+        _ran(eng, 1)
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"])
     _check(got, ref, tol, want)
     eng.close()
@@ -146,6 +168,7 @@ def test_equal_per_arm_tools_are_the_shared_tool(env):
     eng.set_tool(np.tile(tool, (B, 1)), per_arm=True)
     assert eng.dh_pattern == 1
     got = eng.step_host(w["q"], want=ALL)
+    _ran(eng, 3)
     t32 = tool.astype(np.float32).astype(np.float64)
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], tool=t32)
     _check(got, ref, 1e-6, ALL)
@@ -154,6 +177,7 @@ def test_equal_per_arm_tools_are_the_shared_tool(env):
     eng.set_tool(tools, per_arm=True)
     assert eng.dh_pattern == 0
     got = eng.step_host(w["q"], want=ALL)
+    _ran(eng, 0, general=True)
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], tool=tools.astype(np.float32).astype(np.float64))
     _check(got, ref, 1e-6, ALL)
     eng.close()
@@ -189,6 +213,8 @@ def test_shared_ik_weights_on_the_plain_variants(env, robot, B, nobs, dt, tol, f
         eng.set_tool(tool)
     assert eng.field_path == 1 and eng.dh_pattern == 1
     got = eng.step_host(w["q"], want=want)
+    if dt == np.float32 and n <= 7:   # (the weights' bit is built for chains of up to 7 joints)
+        _ran(eng, 5 | (2 if with_tool else 0))
     ref = env.oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], tool=tool)
     _check(got, ref, tol, want)
     plain = env.abi.default_params(flags=flags)
@@ -255,6 +281,7 @@ def test_equal_per_arm_weights_and_bridge_state_are_batch_wide(env):
     eng.set_max_vel(np.full(B, 0.25))
     assert eng.dh_pattern == 1
     got = eng.step_host(w["q"], want=want)
+    _ran(eng, 5)
     for k in want:
         assert np.array_equal(got[k], base[k]), k
     # one arm with other joint weights and another mixer row: per arm again (the general variants), same numbers for every other arm
@@ -266,6 +293,7 @@ def test_equal_per_arm_weights_and_bridge_state_are_batch_wide(env):
     eng.set_mixer_weights(mw2)
     assert eng.dh_pattern == 0
     got2 = eng.step_host(w["q"], want=want)
+    _ran(eng, 0, general=True)
     others = np.ones(B, bool)
     others[[17, 99]] = False
     assert np.abs(got2["qdot_out"][others] - base["qdot_out"][others]).max() < 1e-6
@@ -275,6 +303,7 @@ def test_equal_per_arm_weights_and_bridge_state_are_batch_wide(env):
     eng.set_mixer_weights(np.tile(mw, (B, 1)))
     assert eng.dh_pattern == 1
     got3 = eng.step_host(w["q"], want=want)
+    _ran(eng, 5)
     for k in ("qdot_out", "pose", "status"):
         assert np.array_equal(got3[k], base[k]), k
     eng.close()

@@ -62,6 +62,11 @@ struct vfik_handle {
     int sub8_max_batch_ns = 0;       // with the nullspace module and qdot_out only: likewise (32 until round 3)
     int sub8_max_batch_full = 4096;  // launches that publish the per-cycle rows: -4 ... -10 % at every size either way (vfik_set_small_batch_kernel sets all three)
     long sub8_launches = 0;  // how many launches took it (introspection for tests / A/B)
+    // the distinct cycle-kernel instantiations launched since the last vfik_launched_kernels (plans only: names are formatted when asked)
+    static constexpr int LAUNCHED_MAX = 16;
+    struct Launched { vfik::CyclePlan p; bool ns; } launched[LAUNCHED_MAX];
+    int launched_n = 0;
+    bool launched_lost = false;   // more distinct kernels than the record holds
     long epoch = 0;          // moves with every call that can change what a launch bakes in (vfik_launch_epoch)
     int n_simd = 1024;       // 4 per CU of this device
     // Batches beyond one wave per SIMD may take the persistent launch (cycle_kernel PERS; VFIK_PERSISTENT=1).  Off by default:
@@ -102,6 +107,12 @@ struct vfik_handle {
     unsigned long long* d_stamps = nullptr;  // diagnostic build only
     void* d_rollq[2] = {nullptr, nullptr};  // q ping-pong of the stepped rollout (long chains)
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
+    // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
+    // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
+    bool wts_promoted = false;
+    double shared_wy[6] = {1, 1, 1, 1, 1, 1};
+    double shared_wq[VFIK_MAX_JOINTS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+    void* d_qalign = nullptr;   // 16-byte-aligned copy of a vfik_step q that is not (launch_cycles), allocated at the first such call
     // every arm's bridge state (mixer weights, limiter speed) equal: the launch reads them from the batch constants like a handle that
     // never had per-arm bridge state (a.mixw stays NULL, so the lean / publishing-lean variants keep serving it) -- what a port-level caller
     // produces when every arm's handler sends the same /bridge/weight (handlers.py:189-204,481-497)
@@ -350,6 +361,10 @@ int upload_kconst(vfik_handle* h) {
         for (int k = 0; k < VFIK_MIX_CHANNELS; ++k) kp.mix_w[k] = h->bridge_u[k];
         kp.max_vel = h->bridge_u[6];
     }
+    if (h->wts_promoted) {   // (the arms' common IK weights stand in for the caller's)
+        for (int k = 0; k < 6; ++k) kp.wy[k] = h->shared_wy[k];
+        for (int k = 0; k < h->n; ++k) kp.wq[k] = h->shared_wq[k];
+    }
     const double err = vfik::kconst_fill(h->n, img.data(), h->chain, kp, h->tool_shared, &plain, &dhp);
     if (!(err < 1e-9)) return fail(VFIK_E_ARG, "chain: a fixed transform is not a rigid motion (DH recomposition error %.3e)", err);
     std::memcpy(img.data() + VFIK_KCONST_REP_SAFE_OFF(h->n), &h->uni_safe, sizeof(double));   // the batch's uniform repeller pair (vfik_set_fields)
@@ -519,7 +534,8 @@ void vfik_destroy(vfik_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6};
+    void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
+                    h->d_qalign};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -580,6 +596,7 @@ int vfik_set_params(vfik_handle* h, const vfik_params* p) {
     if ((p->flags & VFIK_F_JOINT_LIMIT_TASK) && !(p->flags & VFIK_F_NULLSPACE))
         return fail(VFIK_E_ARG, "VFIK_F_JOINT_LIMIT_TASK needs VFIK_F_NULLSPACE");
     const bool speed_changed = !h->speed_set || p->speed_scale != h->params.speed_scale;
+    // (against what the caller passed last: weights promoted from equal per-arm rows are not the caller's, vfik_set_arm_weights)
     bool weights_changed = false;
     for (int k = 0; k < 6; ++k) weights_changed = weights_changed || p->wy[k] != h->params.wy[k];
     for (int k = 0; k < h->n; ++k) weights_changed = weights_changed || p->wq[k] != h->params.wq[k];
@@ -598,6 +615,7 @@ int vfik_set_params(vfik_handle* h, const vfik_params* p) {
         const int rc = upload_bridge_state(h, 0, h->B);
         if (rc != VFIK_OK) return rc;
     }
+    if (weights_changed) h->wts_promoted = false;
     if (weights_changed && h->d_wts) {  // new batch-wide IK weights replace every arm's own
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -619,7 +637,9 @@ static int ensure_arm_weights(vfik_handle* h) {
     const size_t Bp = h->Bpad, rows = 6 + h->n;
     std::vector<double> img(rows * Bp, 1.0);
     for (size_t r = 0; r < rows; ++r) {
-        const double v = r < 6 ? h->params.wy[r] : h->params.wq[r - 6];
+        const double* wy = h->wts_promoted ? h->shared_wy : h->params.wy;
+        const double* wq = h->wts_promoted ? h->shared_wq : h->params.wq;
+        const double v = r < 6 ? wy[r] : wq[r - 6];
         for (size_t b = 0; b < Bp; ++b) img[r * Bp + b] = v;
     }
     if (dev_alloc(h, (void**)&h->d_wts, img.size() * sizeof(double), false)) return VFIK_E_HIP;
@@ -643,13 +663,15 @@ int vfik_set_arm_weights(vfik_handle* h, int first_arm, int n_arms, const double
     if (first_arm == 0 && n_arms == h->B && wy && wq) {
         // The whole batch, and every arm with the same weights (a port-level caller forwards each arm's /weight bottle): these ARE batch-wide
         // weights -- stored as such, the arms' own dropped, so that the launches stay on the kernels built for plain chains (WTSC) instead
-        // of the general variants.
+        // of the general variants.  Stored beside the caller's vfik_params, not in them: a later vfik_set_params that leaves wy / wq as the
+        // caller last passed them must not write those back over these.
         bool same = true;
         for (int j = 1; j < n_arms && same; ++j)
             same = std::memcmp(wy + (size_t)j * 6, wy, 6 * sizeof(double)) == 0 && std::memcmp(wq + (size_t)j * h->n, wq, h->n * sizeof(double)) == 0;
         if (same) {
-            for (int k = 0; k < 6; ++k) h->params.wy[k] = wy[k];
-            for (int k = 0; k < h->n; ++k) h->params.wq[k] = wq[k];
+            for (int k = 0; k < 6; ++k) h->shared_wy[k] = wy[k];
+            for (int k = 0; k < h->n; ++k) h->shared_wq[k] = wq[k];
+            h->wts_promoted = true;
             if (h->d_wts) {
                 HIP_TRY(hipStreamSynchronize(h->stream));
                 (void)hipFree(h->d_wts);
@@ -920,6 +942,21 @@ int vfik_reset_state(vfik_handle* h) {
     return VFIK_OK;
 }
 
+// the kernel a launch took, into the handle's record (vfik_launched_kernels) when it is not there yet: a few compares, no string, no allocation
+static void note_launch(vfik_handle* h, const vfik::CyclePlan& p, unsigned flags) {
+    const bool ns = flags & VFIK_F_NULLSPACE;
+    for (int i = 0; i < h->launched_n; ++i) {
+        const vfik::CyclePlan& r = h->launched[i].p;
+        if (h->launched[i].ns == ns && r.family == p.family && r.plain == p.plain && r.roll == p.roll && r.fastf == p.fastf && r.lean == p.lean && r.cf == p.cf &&
+            r.pers == p.pers && r.fun == p.fun && r.waves == p.waves && r.uni == p.uni && r.mixo == p.mixo && r.dhp == p.dhp && r.heavy == p.heavy)
+            return;
+    }
+    if (h->launched_n == vfik_handle::LAUNCHED_MAX) { h->launched_lost = true; return; }
+    h->launched[h->launched_n].p = p;
+    h->launched[h->launched_n].ns = ns;
+    ++h->launched_n;
+}
+
 static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp, void* q_out, hipStream_t stream) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!io || !io->q) return fail(VFIK_E_ARG, "a control cycle needs io->q");
@@ -929,6 +966,20 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
     HIP_TRY(hipSetDevice(h->device));
     vfik::KArgs a;
     fill_kargs(h, io, a);
+    if (reinterpret_cast<uintptr_t>(io->q) % 16) {
+        // The kernels fetch q in 16-byte pieces up to its length rounded up to 16 bytes (vfik_kernel.hip, QBLK): from a q that is not 16-byte
+        // aligned the last piece could reach into the next page.  Such a q is staged through an aligned buffer of the handle.
+        const size_t qbytes = (size_t)h->B * h->n * h->esz;
+        if (!h->d_qalign) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+                return fail(VFIK_E_STATE, "io->q is not 16-byte aligned: its staging buffer is allocated at the first such call -- make one before capturing the stream");
+            (void)hipGetLastError();
+            if (dev_alloc(h, &h->d_qalign, (qbytes + 15) / 16 * 16, false)) return VFIK_E_HIP;
+        }
+        HIP_TRY(hipMemcpyAsync(h->d_qalign, io->q, qbytes, hipMemcpyDefault, stream));
+        a.q = h->d_qalign;
+    }
     a.dt = dt;
     a.clamp = clamp ? 1 : 0;
     if (n_cycles > 0 && (io->track_error || io->obj_dist))
@@ -944,7 +995,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
         for (int k = 0; k < 2; ++k)
             if (!h->d_rollq[k] && dev_alloc(h, &h->d_rollq[k], qbytes, false)) return VFIK_E_HIP;
         a.n_cycles = 0;
-        const void* q_in = io->q;
+        const void* q_in = a.q;
         for (int c = 0; c < n_cycles; ++c) {
             const bool last = c == n_cycles - 1;
             vfik::KArgs k = a;
@@ -954,7 +1005,9 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
             if (!last) {  // intermediate cycles produce no outputs but the status bits
                 k.qdot_vf = k.qdot_null = k.qdot_out = k.pose = k.pose_nt = k.v6 = k.qdist = k.goal_dist = k.q_ref_out = nullptr;
             }
-            hipError_t e = vfik::launch_cycle(h->io_dtype, h->n, k, h->block, stream);
+            vfik::CyclePlan plan;
+            hipError_t e = vfik::launch_cycle(h->io_dtype, h->n, k, h->block, stream, &plan);
+            note_launch(h, plan, k.flags);
             if (e != hipSuccess) return fail(VFIK_E_HIP, "kernel launch: %s", hipGetErrorString(e));
             q_in = k.q_out;
         }
@@ -984,9 +1037,10 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
         }
         if (want_track && !h->d_track && dev_alloc(h, (void**)&h->d_track, (size_t)38 * h->B * sizeof(double), true)) return VFIK_E_HIP;
     }
-    int sub8 = 0;
-    hipError_t e = vfik::launch_cycle(h->io_dtype, h->n, a, h->block, stream, &sub8);
-    h->sub8_launches += sub8;
+    vfik::CyclePlan plan;
+    hipError_t e = vfik::launch_cycle(h->io_dtype, h->n, a, h->block, stream, &plan);
+    h->sub8_launches += plan.family == vfik::CycleFamily::Sub8;
+    note_launch(h, plan, a.flags);
     if (e != hipSuccess) return fail(VFIK_E_HIP, "kernel launch: %s", hipGetErrorString(e));
     if (want_track) {
         e = vfik::launch_track(h->io_dtype, a.pose, a.v6, h->d_track, io->track_error, io->active, h->B, stream);
@@ -1442,6 +1496,21 @@ int vfik_set_small_batch_kernel(vfik_handle* h, int max_batch) {
 }
 
 long vfik_small_batch_launches(vfik_handle* h) { return h ? h->sub8_launches : -1; }
+
+int vfik_launched_kernels(vfik_handle* h, char* buf, int len) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (h->launched_lost) return fail(VFIK_E_STATE, "more than %d distinct cycle kernels launched since the last vfik_launched_kernels", vfik_handle::LAUNCHED_MAX);
+    std::string all;
+    for (int i = 0; i < h->launched_n; ++i) {
+        all += vfik::cycle_kernel_name(h->launched[i].p, h->n, h->io_dtype, h->launched[i].ns);
+        all += '\n';
+    }
+    if (!buf) return (int)all.size();
+    if (len < (int)all.size() + 1) return fail(VFIK_E_ARG, "vfik_launched_kernels: %d bytes needed", (int)all.size() + 1);
+    std::memcpy(buf, all.c_str(), all.size() + 1);
+    h->launched_n = 0;
+    return (int)all.size();
+}
 
 size_t vfik_device_bytes(vfik_handle* h) { return h ? h->dev_bytes : 0; }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdio>
+#include <string>
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -447,10 +449,38 @@ inline CyclePlan plan_cycle(const KArgs& a, int nj, int io_bits, bool ns, int bl
     return p;
 }
 
+// The demangled name of the instantiation a plan takes, namespace and parameter list stripped (template arguments in the order the kernels
+// declare them; " [heavy]": the long chains' object of their own).  Host code: tests/c_host/launch_plan.cpp prints it, vfik_launched_kernels
+// reports it -- neither is on the enqueue path.
+inline std::string cycle_kernel_name(const CyclePlan& p, int nj, int io_bits, bool ns) {
+    const char* t = io_bits == 32 ? "float" : "double";
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    char s[256];
+    switch (p.family) {
+        case CycleFamily::Refused: return "refused";
+        case CycleFamily::Sub8:
+            std::snprintf(s, sizeof s, "cycle_sub8_kernel%s<%s, %d, %s, %d>", ns ? "" : "_x", t, nj, b(ns), p.dhp);
+            return s;
+        case CycleFamily::Mixo:
+            std::snprintf(s, sizeof s, "cycle_kernel_m<%s, %d, %s, %d, %s, %d>", t, nj, b(ns), p.lean, b(p.fun), p.dhp);
+            return s;
+        case CycleFamily::Lean:
+        case CycleFamily::LeanPersistent:
+        case CycleFamily::LeanTwoWaves:
+            std::snprintf(s, sizeof s, "cycle_kernel_s<%s, %d, %s, true, false, true, 1, %d, %s, %s, %d, %s, %d>", t, nj, b(ns), p.cf, b(p.pers), b(p.fun), p.waves,
+                          b(p.uni), p.dhp);
+            return s;
+        default:
+            std::snprintf(s, sizeof s, "cycle_kernel_x<%s, %d, %s, %s, %s, %s, %d, %d, %s, %s, %d, %s, false, %d>%s", t, nj, b(ns), b(p.plain), b(p.roll), b(p.fastf),
+                          p.lean, p.cf, b(p.pers), b(p.fun), p.waves, b(p.uni), p.dhp, p.heavy ? " [heavy]" : "");
+            return s;
+    }
+}
+
 // Type-erased launchers (implemented in vfik_kernel.hip).  kargs points to a KArgs<nj>.
 uint32_t supported_joints_mask();
-// *sub8 (may be NULL) is set to 1 when the launch took the eight-lanes-per-arm kernel
-hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, int* sub8 = nullptr);
+// *plan (may be NULL) receives the launch's plan -- which instantiation it took (cycle_kernel_name), the eight-lanes-per-arm kernel among them
+hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan = nullptr);
 hipError_t launch_probe(int io_dtype, const void* pose, const void* goal, const void* slots, int B, long Bp, int slots_used,
                         double rot_slow, double cos_slow, void* out, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);

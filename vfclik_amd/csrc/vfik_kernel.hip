@@ -3318,10 +3318,10 @@ uint32_t supported_joints_mask() {
     return m;
 }
 
-hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, int* sub8) {
+hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan_out) {
     const bool ns = kargs.flags & VFIK_F_NULLSPACE;
     const CyclePlan plan = plan_cycle(kargs, nj, io_dtype, ns, block);
-    if (sub8 && plan.family == CycleFamily::Sub8) *sub8 = 1;
+    if (plan_out) *plan_out = plan;
     switch (nj) {
 #define X(n)                                                                                                                        \
     case n:                                                                                                                         \

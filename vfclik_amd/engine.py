@@ -96,6 +96,7 @@ def load_library(path=None):
         "vfik_set_objects": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_int]),
         "vfik_set_small_batch_kernel": (C.c_int, [H, C.c_int]),
         "vfik_small_batch_launches": (C.c_long, [H]),
+        "vfik_launched_kernels": (C.c_int, [H, C.c_char_p, C.c_int]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match include/vfik.h
@@ -507,6 +508,15 @@ class Engine:
     @property
     def small_batch_launches(self):
         return int(self.lib.vfik_small_batch_launches(self.h))
+
+    def launched_kernels(self):
+        """The set of cycle-kernel instantiations launched since the last call, by demangled name without namespace and parameter list
+        (include/vfik.h: vfik_launched_kernels); the record is cleared."""
+        n = self.lib.vfik_launched_kernels(self.h, None, 0)
+        self._chk(min(n, 0))
+        buf = C.create_string_buffer(n + 1)
+        self._chk(min(self.lib.vfik_launched_kernels(self.h, buf, n + 1), 0))
+        return set(buf.value.decode().splitlines())
 
     def probe_field(self, pose_dev, v6_dev):
         """The field of every arm at a given pose (vf:469-503): device pose[B][16] -> v6[B][6]."""
