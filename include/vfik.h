@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define VFIK_ABI_VERSION 5
+#define VFIK_ABI_VERSION 6
 
 enum {
     VFIK_OK = 0,
@@ -90,6 +90,33 @@ int vfik_set_tool(vfik_handle* h, const double* tool16, int per_arm);
  * message arrived, exactly when the reference rebuilds totalVF (vf:276-293). */
 int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field* fields,
                     int max_fields, const int32_t* counts);
+
+/* ABI 6.  Goals and obstacles that MOVE.  The reference's object feeder re-sends every primitive of an object whenever the object's pose
+ * changes (object_feeder:214-354: the goal attractor, object_feeder:229-241; the point obstacles and the near-goal repeller,
+ * object_feeder:317-334): same ids, types, forces, safe distances and orders, new coordinates.  vfik_move_fields rewrites those
+ * coordinates inside the device images that vfik_set_fields packed, with one small kernel on the handle's stream: no host pack, no
+ * host synchronisation, and no allocation after the first call.  Device pointers, io dtype, asynchronous: the call is ordered after
+ * the launches enqueued before it and before those enqueued after it; like the setters it first waits for outstanding
+ * vfik_submit_host tickets, and has no other host wait.
+ *   goal16 [n_arms][16]  row-major 4x4, the layout of io->pose (a leader's io->pose buffer may be passed as it is), or NULL: goals
+ *          stay.  Rows 0-2 replace the frame of the arm's goal block -- its lowest-id attractor.  Slow-down distance, force, the
+ *          `present` flag and the arm's speedScale are not touched.  An arm without a goal block ignores its row.
+ *   rep4   [n_arms][n_rep][4] = x y z radius, or NULL.  Row k replaces x y z radius of the arm's k-th decay repeller
+ *          (VFIK_FIELD_REPELLER) in ASCENDING-ID order; safe distance, force and order stay.  Rows with k at or beyond the arm's
+ *          repeller count are ignored (unused slots keep what disarms them).
+ *   A goal row or a repeller row whose FIRST element is NaN leaves that primitive as it is (the convention of io->q_ref);
+ *   active [n_arms] (device, may be NULL): active[b] == 0 leaves the whole arm as it is.
+ * The caller keeps radius >= 0 and radius + safe distance >= 0, as the fields it handed to vfik_set_fields did (the uniform repeller
+ * image relies on it).  NOT moved: funnels, hemispheres and attractors beyond the first -- those go through vfik_set_fields.
+ * Every image a later launch may read carries the new values (goal block, uniform, compact and general slot images): lean and
+ * publishing launches, rollouts, launches with per-arm options, vfik_probe_field and io->goal_dist all see the moved scene.  Nothing a
+ * launch decides at enqueue time changes: vfik_field_path, vfik_uniform_repellers, vfik_mixed_orders, vfik_slots_in_use and
+ * vfik_launch_epoch keep their values, and a captured graph that contains vfik_step stays valid.
+ * VFIK_E_ARG: bad arm range, both arrays NULL, n_rep < 0 or n_rep > max_slots; VFIK_E_STATE: no vfik_set_fields call yet. */
+int vfik_move_fields(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active);
+/* The same with HOST arrays of doubles, rounded to the io dtype exactly as vfik_set_fields rounds vfik_field.p[]; copies, launches and
+ * synchronises (a setter, like vfik_set_fields -- at a fraction of its cost: nothing is sorted or packed). */
+int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const double* goal16, const double* rep4, int n_rep);
 
 /* Per-arm IK weights: what each arm's vf process keeps after a /weight message (vf:164-179,295-309): 't' + 6
  * task-space weights -> wy[n_arms][6], 'j' + n joint-space weights -> wq[n_arms][n]; either may be NULL

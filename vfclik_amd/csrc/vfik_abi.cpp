@@ -98,6 +98,10 @@ struct vfik_handle {
     void* d_slots_fast = nullptr;  // compact repeller image for the straight-line path: 3 quad planes per PAIR of slots
     void* d_orders = nullptr;      // order planes: 16 bytes per arm and plane, one byte per compact-image slot (vfik_kernel.h); read when `mixed`
     int mixed = 0;                 // the batch's decay repellers have integer orders that differ (between slots or between arms)
+    unsigned short* d_repmap = nullptr;   // vfik_move_fields: general slot of the arm's k-th decay repeller, 8 entries (16 bytes) per arm and plane (vfik_kernel.h: MoveArgs)
+    bool fields_set = false;       // some vfik_set_fields call succeeded: there are images to move
+    void* d_move_stage = nullptr;  // vfik_move_fields_host: the rounded rows on the device, grown on demand
+    size_t move_stage_bytes = 0;
     void* d_tool = nullptr;    // 3 quad planes (per-arm tools only)
     double tool_shared[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     int tool_per_arm = 0;
@@ -175,11 +179,16 @@ int dev_alloc(vfik_handle* h, void** p, size_t bytes, bool zero) {
 // A setter rewrites device state that kernels of the pipelined host path may still be reading on the
 // side streams: let those drain first (the handle's own stream is synchronised by the setters themselves).
 // (every vfik_set_* / vfik_reset_state call passes through here: the launch epoch moves with them, vfik_launch_epoch)
-int quiesce(vfik_handle* h) {
-    ++h->epoch;
+// (vfik_move_fields drains them too, without moving the epoch: it changes nothing a launch bakes in)
+int drain_side_streams(vfik_handle* h) {
     if (h->s_in) HIP_TRY(hipStreamSynchronize(h->s_in));
     if (h->s_out) HIP_TRY(hipStreamSynchronize(h->s_out));
     return VFIK_OK;
+}
+
+int quiesce(vfik_handle* h) {
+    ++h->epoch;
+    return drain_side_streams(h);
 }
 
 // true when the GPU can dereference p: device memory, or pinned / registered host memory
@@ -204,7 +213,7 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
                  std::vector<char>& goal, std::vector<char>& slots, std::vector<char>& fast, std::vector<int>& used,
                  std::vector<char>& funnel, std::vector<int>& used_fast, std::vector<char>& has_funnel,
                  std::vector<char>& uni, std::vector<char>& pair_state, std::vector<double>& pair_safe, std::vector<double>& pair_force,
-                 std::vector<unsigned char>& ord) {
+                 std::vector<unsigned char>& ord, std::vector<unsigned short>& rmap) {
     funnel.assign((size_t)6 * n_arms * 4 * sizeof(T), 0);  // aux block: funnel planes 0..2, hemisphere planes 3..5
     goal.assign((size_t)4 * n_arms * 4 * sizeof(T), 0);
     slots.assign((size_t)std::max(1, 2 * S) * n_arms * 4 * sizeof(T), 0);
@@ -220,6 +229,8 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
     // order planes: byte (m % 16) of plane (m / 16) = the integer decay order of compact-image slot m; slots an arm does not use
     // repeat the order of its last repeller (5 -- what the feeder sends, object_feeder:302,333 -- for an arm without any)
     ord.assign((size_t)((std::max(1, S) + 15) / 16) * n_arms * 16, 5);
+    // vfik_move_fields' map: entry (m % 8) of plane (m / 8) = the general slot of compact-image slot m, MOVE_NONE behind the arm's last repeller
+    rmap.assign((size_t)((std::max(1, S) + 7) / 8) * n_arms * 8, vfik::MOVE_NONE);
     std::vector<int> order;
     for (int j = 0; j < n_arms; ++j) {
         const vfik_field* f = fields + (size_t)j * max_fields;
@@ -271,6 +282,7 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
                     const double o = fd.p[5];
                     ord[((size_t)(mr >> 4) * n_arms + j) * 16 + (mr & 15)] = (o >= 0.0 && o < 128.0 && (double)(int)o == o) ? (unsigned char)(int)o : 0;
                 }
+                rmap[((size_t)(mr >> 3) * n_arms + j) * 8 + (mr & 7)] = (unsigned short)m;
                 const int pair = mr >> 1, half = mr & 1;
                 ++mr;
                 for (int i = 0; i < 6; ++i) {
@@ -490,6 +502,11 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
         h->d_slots = a0 + sz_goal + sz_kc + sz_lv + sz_sf + sz_su;
         h->d_orders = a0 + sz_goal + sz_kc + sz_lv + sz_sf + sz_su + sz_sl;
     }
+    {   // vfik_move_fields' map, every entry MOVE_NONE until field sets arrive
+        const size_t sz_map = (std::max<size_t>(1, (size_t)max_slots) + 7) / 8 * (size_t)h->Bpad * 16;
+        if (dev_alloc(h, (void**)&h->d_repmap, sz_map, false)) return bail("alloc repeller map");
+        if (hipMemsetAsync(h->d_repmap, 0xFF, sz_map, h->stream) != hipSuccess) return bail("init repeller map");
+    }
     {   // the uniform image starts out with every slot unused (radius -inf), like the zeros (force 0) of the other two images
         std::vector<char> plane((size_t)h->Bpad * 4 * h->esz, 0);
         for (int b = 0; b < h->Bpad; ++b) {
@@ -535,7 +552,7 @@ void vfik_destroy(vfik_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
-                    h->d_qalign};
+                    h->d_qalign, h->d_repmap, h->d_move_stage};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -756,9 +773,10 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
     std::vector<double> psafe(n_arms), pforce(n_arms);
     std::vector<int> used(n_arms), used_fast(n_arms);
     std::vector<unsigned char> ord;
+    std::vector<unsigned short> rmap;
     const int S = h->max_slots;
-    if (h->io_dtype == 32) pack_fields<float>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord);
-    else pack_fields<double>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord);
+    if (h->io_dtype == 32) pack_fields<float>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap);
+    else pack_fields<double>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap);
     const size_t qb = 4 * h->esz, w = (size_t)n_arms * qb, pitch = (size_t)h->Bpad * qb;
     char* dg = static_cast<char*>(h->d_goal) + (size_t)first_arm * qb;
     HIP_TRY(hipMemcpy2DAsync(dg, pitch, goal.data(), w, w, 3, hipMemcpyHostToDevice, h->stream));
@@ -774,8 +792,11 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
         HIP_TRY(hipMemcpy2DAsync(du, pitch, uni.data(), w, w, (size_t)S, hipMemcpyHostToDevice, h->stream));
         char* dor = static_cast<char*>(h->d_orders) + (size_t)first_arm * 16;
         HIP_TRY(hipMemcpy2DAsync(dor, (size_t)h->Bpad * 16, ord.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 15) / 16, hipMemcpyHostToDevice, h->stream));
+        char* dm = reinterpret_cast<char*>(h->d_repmap) + (size_t)first_arm * 16;
+        HIP_TRY(hipMemcpy2DAsync(dm, (size_t)h->Bpad * 16, rmap.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 7) / 8, hipMemcpyHostToDevice, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->fields_set = true;
     for (int j = 0; j < n_arms; ++j) {
         h->slots_per_arm[first_arm + j] = used[j];
         h->fast_slots_per_arm[first_arm + j] = used_fast[j];
@@ -824,6 +845,73 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
         }
     }
     h->uni_ok = uni_ok ? 1 : 0;
+    return VFIK_OK;
+}
+
+// the checks the two forms of vfik_move_fields share
+static int move_check(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep) {
+    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (!goal16 && !rep4) return fail(VFIK_E_ARG, "vfik_move_fields: give goal16, rep4 or both");
+    if (n_rep < 0 || n_rep > h->max_slots) return fail(VFIK_E_ARG, "n_rep %d outside [0, %d]", n_rep, h->max_slots);
+    if (!h->fields_set) return fail(VFIK_E_STATE, "vfik_move_fields before any vfik_set_fields: there is nothing to move");
+    return VFIK_OK;
+}
+
+static int move_launch(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
+    vfik::MoveArgs m{};
+    m.goal = h->d_goal;
+    m.slots = h->d_slots;
+    m.slots_fast = h->d_slots_fast;
+    m.slots_uni = h->d_slots_uni;
+    m.repmap = h->d_repmap;
+    m.goal16 = goal16;
+    m.rep4 = n_rep > 0 ? rep4 : nullptr;
+    m.active = active;
+    m.first_arm = first_arm;
+    m.n_arms = n_arms;
+    m.n_rep = n_rep;
+    m.S = h->max_slots;
+    m.Bpad = h->Bpad;
+    if (!m.goal16 && !m.rep4) return VFIK_OK;   // (rep4 with no rows: nothing to write)
+    hipError_t e = vfik::launch_move(h->io_dtype, m, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "move launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+int vfik_move_fields(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = move_check(h, first_arm, n_arms, goal16, rep4, n_rep);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return move_launch(h, first_arm, n_arms, goal16, rep4, n_rep, active);
+}
+
+int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const double* goal16, const double* rep4, int n_rep) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = move_check(h, first_arm, n_arms, goal16, rep4, n_rep);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (n_rep == 0) rep4 = nullptr;
+    const size_t ng = goal16 ? (size_t)n_arms * 16 : 0, nr = rep4 ? (size_t)n_arms * n_rep * 4 : 0;
+    if (ng + nr == 0) return VFIK_OK;
+    std::vector<char> buf((ng + nr) * h->esz);   // rounded as vfik_set_fields rounds p[] (NaN stays NaN)
+    for (size_t k = 0; k < ng + nr; ++k) {
+        const double v = k < ng ? goal16[k] : rep4[k - ng];
+        if (h->io_dtype == 32) put<float>(buf, k, v); else put<double>(buf, k, v);
+    }
+    if (buf.size() > h->move_stage_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_move_stage) { (void)hipFree(h->d_move_stage); h->dev_bytes -= h->move_stage_bytes; h->d_move_stage = nullptr; h->move_stage_bytes = 0; }
+        if (dev_alloc(h, &h->d_move_stage, buf.size(), false)) return VFIK_E_HIP;
+        h->move_stage_bytes = buf.size();
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_move_stage, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
+    char* d = static_cast<char*>(h->d_move_stage);
+    const int rl = move_launch(h, first_arm, n_arms, goal16 ? d : nullptr, rep4 ? d + ng * h->esz : nullptr, n_rep, nullptr);
+    if (rl != VFIK_OK) return rl;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // `buf` and the stage are reused
     return VFIK_OK;
 }
 

@@ -483,6 +483,24 @@ uint32_t supported_joints_mask();
 hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan = nullptr);
 hipError_t launch_probe(int io_dtype, const void* pose, const void* goal, const void* slots, int B, long Bp, int slots_used,
                         double rot_slow, double cos_slow, void* out, hipStream_t stream);
+// vfik_move_fields (ABI 6): new coordinates for the goal frames and the decay repellers of arms [first_arm, first_arm + n_arms), written into
+// every image vfik_set_fields packed.  repmap: per arm one 16-bit entry per compact-image slot, 16 bytes (8 slots) per arm and plane like the
+// order planes -- entry k = the GENERAL slot of the arm's k-th decay repeller (it differs from k behind a funnel, hemisphere or further
+// attractor), MOVE_NONE from the arm's repeller count on.
+constexpr unsigned short MOVE_NONE = 0xFFFFu;
+struct MoveArgs {
+    void* goal;                 // 4 quad planes
+    void* slots;                // 2 S quad planes
+    void* slots_fast;           // compact image
+    void* slots_uni;            // uniform image (slot m in plane m + 1)
+    const unsigned short* repmap;
+    const void* goal16;         // [n_arms][16] or NULL
+    const void* rep4;           // [n_arms][n_rep][4] or NULL
+    const int* active;          // [n_arms] or NULL
+    int first_arm, n_arms, n_rep, S;
+    long Bpad;
+};
+hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

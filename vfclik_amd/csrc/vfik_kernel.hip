@@ -14,7 +14,7 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel.
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -2529,6 +2529,71 @@ __global__ void __launch_bounds__(256) probe_kernel(const T* pose, const T* goal
 }
 
 // ------------------------------------------------------------------------------------------------
+// vfik_move_fields (ABI 6): goals and obstacles that move (object_feeder:214-354 re-sends an object's primitives with new coordinates
+// whenever its pose changes: the goal frame, object_feeder:229-241; x y z radius of the point obstacles and the near-goal repeller,
+// object_feeder:317-334).  One thread per (arm, primitive): lanes run over arms -- aligned to the planes' 64-quad rows, so that every
+// plane write of a wave is one contiguous 1 KiB (2 KiB at float64 I/O) -- and blockIdx.y over the primitives: the goal frame when
+// one is given, then decay repeller k of the caller's rows.  Every image a later launch may read gets the new numbers:
+//   goal block   rows 0..2 of the frame (plane 3 -- present, slow-down, force, speedScale -- stays),
+//   uniform      plane k + 1: the whole quad (x y z radius),
+//   compact      (x0 y0 z0 r0 | s0 f0 x1 y1 | z1 r1 s1 f1): the even slot's first quad; the odd slot's two half quads (s f stay),
+//   general      first plane of the slot repmap names (p0..p3 = x y z radius; p4 p5 force type stay).
+// Rows from the arm's repeller count on find MOVE_NONE in the map and write nothing: an unused slot keeps its -inf radius / zero force.
+// Plain vector stores, no LDS, no loop, no register array.  VEC: the caller's arrays are 16-byte aligned (whole-quad loads).
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct alignas(16) MoveQuad { T v[4]; };
+template <typename T> struct alignas(2 * sizeof(T)) MovePair { T v[2]; };
+
+template <typename T, bool VEC>
+__device__ __forceinline__ MoveQuad<T> move_load(const T* src) {
+    if (VEC) return *reinterpret_cast<const MoveQuad<T>*>(src);
+    MoveQuad<T> r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r.v[e] = src[e];
+    return r;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
+    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
+    const long j = arm - m.first_arm;
+    if (m.active && !m.active[j]) return;
+    const long Qp = m.Bpad;  // quads per plane
+    int k = (int)blockIdx.y;
+    if (m.goal16) {
+        if (k == 0) {
+            MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(m.goal) + arm;
+            if (g[3 * Qp].v[0] == (T)0) return;   // no goal block: the row is ignored
+            const T* src = static_cast<const T*>(m.goal16) + j * 16;
+            const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
+            if (r0.v[0] != r0.v[0]) return;       // NaN: this goal stays
+            g[0] = r0;
+            g[Qp] = r1;
+            g[2 * Qp] = r2;
+            return;
+        }
+        --k;
+    }
+    if (k >= m.n_rep || k >= m.S) return;
+    const unsigned gs = m.repmap[((long)(k >> 3) * m.Bpad + arm) * 8 + (k & 7)];
+    if (gs >= (unsigned)m.S) return;              // MOVE_NONE: the arm has no k-th decay repeller
+    const MoveQuad<T> r = move_load<T, VEC>(static_cast<const T*>(m.rep4) + (j * m.n_rep + k) * 4);
+    if (r.v[0] != r.v[0]) return;                 // NaN: this repeller stays
+    static_cast<MoveQuad<T>*>(m.slots_uni)[(long)(k + 1) * Qp + arm] = r;
+    static_cast<MoveQuad<T>*>(m.slots)[(long)(2 * gs) * Qp + arm] = r;
+    MoveQuad<T>* const f = static_cast<MoveQuad<T>*>(m.slots_fast) + (long)(3 * (k >> 1)) * Qp + arm;
+    if (!(k & 1)) {
+        f[0] = r;
+    } else {
+        MovePair<T> lo, hi;
+        lo.v[0] = r.v[0]; lo.v[1] = r.v[1]; hi.v[0] = r.v[2]; hi.v[1] = r.v[3];
+        reinterpret_cast<MovePair<T>*>(f + Qp)[1] = lo;
+        reinterpret_cast<MovePair<T>*>(f + 2 * Qp)[0] = hi;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // EIGHT LANES PER ARM (small batches): the mapping BASELINE.json's north_star sketches -- an arm spread over the lanes of
 // a (sub-)wave with cross-lane exchange -- for what vfclik itself runs: a handful of arms (scripts/vfclik:88-105), each
 // with its vf, nullspace and debug process and the bridge's mixer.  Served: revolute chain of up to 7 joints, identity
@@ -3389,6 +3454,20 @@ hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, in
     else
         hipLaunchKernelGGL(monitor_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
                            static_cast<const double*>(frames), O, count, static_cast<double*>(out), active);
+    return hipGetLastError();
+}
+
+hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream) {
+    const int lanes = (m.first_arm & 63) + m.n_arms;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)((m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0))), blk(256);
+    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4) & 15u) == 0;
+    if (io_dtype == 32) {
+        if (vec) hipLaunchKernelGGL((move_kernel<float, true>), grid, blk, 0, stream, m);
+        else hipLaunchKernelGGL((move_kernel<float, false>), grid, blk, 0, stream, m);
+    } else {
+        if (vec) hipLaunchKernelGGL((move_kernel<double, true>), grid, blk, 0, stream, m);
+        else hipLaunchKernelGGL((move_kernel<double, false>), grid, blk, 0, stream, m);
+    }
     return hipGetLastError();
 }
 

@@ -62,6 +62,8 @@ def load_library(path=None):
         "vfik_set_tool": (C.c_int, [H, C.c_void_p, C.c_int]),
         "vfik_set_speed_scale": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
         "vfik_set_fields": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+        "vfik_move_fields": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "vfik_move_fields_host": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
         "vfik_set_mixer_weights": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
         "vfik_set_ext_cmd": (C.c_int, [H, C.c_int, C.c_void_p]),
         "vfik_reset_state": (C.c_int, [H]),
@@ -202,6 +204,62 @@ class Engine:
             raise ValueError("fields must be (n_arms, max_fields)")
         c = np.ascontiguousarray(counts, dtype=np.int32)
         self._chk(self.lib.vfik_set_fields(self.h, int(first_arm), f.shape[0], f.ctypes.data, f.shape[1], c.ctypes.data))
+
+    def move_fields(self, goal=None, repellers=None, active=None, first_arm=0, n_arms=None, n_rep=None):
+        """Goals and obstacles that move, on the device (include/vfik.h: vfik_move_fields): asynchronous on the engine's stream, no
+        host pack, no synchronisation.  ``goal``: (n_arms, 16) or (n_arms, 4, 4) row-major frames of the engine's dtype -- another
+        engine's ``pose`` output as it is -- replacing rows 0-2 of each arm's goal frame; ``repellers``: (n_arms, n_rep, 4) =
+        x y z radius of each arm's k-th decay repeller in ascending-id order; ``active``: int32 (n_arms,), 0 leaves the arm alone.
+        A row whose first element is NaN leaves that primitive alone.  Torch tensors on this device (contiguous, shapes checked), or
+        raw device addresses together with ``n_arms`` (and ``n_rep`` with ``repellers``)."""
+        def tensor(x):
+            return x is not None and not isinstance(x, int)
+        for name, x, tail in (("goal", goal, 16), ("repellers", repellers, 4), ("active", active, 1)):
+            if not tensor(x):
+                continue
+            if not x.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            want = "int32" if name == "active" else self.io_dtype.name
+            if str(x.dtype).split(".")[-1] != want:
+                raise ValueError("%s must be %s, got %s" % (name, want, x.dtype))
+            rows = x.shape[0]
+            if n_arms is None:
+                n_arms = rows
+            per_arm = x.numel() // max(rows, 1)
+            if rows != n_arms or (name != "repellers" and per_arm != tail) or (name == "repellers" and (x.dim() != 3 or x.shape[2] != 4)):
+                raise ValueError("%s: shape %s does not fit %s arms" % (name, tuple(x.shape), n_arms))
+            if name == "repellers":
+                if n_rep is not None and n_rep != x.shape[1]:
+                    raise ValueError("repellers: %d rows per arm, n_rep says %d" % (x.shape[1], n_rep))
+                n_rep = x.shape[1]
+        if n_arms is None:
+            raise ValueError("raw addresses need n_arms")
+        if repellers is not None and n_rep is None:
+            raise ValueError("a raw repellers address needs n_rep")
+        self._chk(self.lib.vfik_move_fields(self.h, int(first_arm), int(n_arms), C.c_void_p(_ptr(goal)), C.c_void_p(_ptr(repellers)),
+                                            int(n_rep or 0), C.c_void_p(_ptr(active))))
+
+    def move_fields_host(self, goal=None, repellers=None, first_arm=0):
+        """The host form (vfik_move_fields_host): NumPy arrays of doubles, rounded to the engine's dtype exactly as ``set_fields``
+        rounds the parameters; (n_arms, 16) / (n_arms, 4, 4) goal frames and / or (n_arms, n_rep, 4) x y z radius.  Synchronous."""
+        g = r = None
+        n_arms, n_rep = None, 0
+        if goal is not None:
+            g = np.ascontiguousarray(goal, dtype=np.float64)
+            if g.ndim < 2 or g.size != g.shape[0] * 16:
+                raise ValueError("goal must be (n_arms, 16) or (n_arms, 4, 4), got %s" % (g.shape,))
+            n_arms = g.shape[0]
+        if repellers is not None:
+            r = np.ascontiguousarray(repellers, dtype=np.float64)
+            if r.ndim != 3 or r.shape[2] != 4:
+                raise ValueError("repellers must be (n_arms, n_rep, 4), got %s" % (r.shape,))
+            if n_arms is not None and r.shape[0] != n_arms:
+                raise ValueError("goal and repellers must cover the same arms")
+            n_arms, n_rep = r.shape[0], r.shape[1]
+        if n_arms is None:
+            raise ValueError("give goal, repellers or both")
+        self._chk(self.lib.vfik_move_fields_host(self.h, int(first_arm), n_arms, None if g is None else g.ctypes.data,
+                                                 None if r is None else r.ctypes.data, n_rep))
 
     def set_objects(self, frames, first_arm=0):
         """Object frames of the distance monitor (monitor_distance:72,111-129): (n_arms, n_objects, 16) doubles, kept on the

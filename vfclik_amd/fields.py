@@ -4,10 +4,12 @@ Each reference ``vf`` process keeps ``vectorFields = {id: [force, type, params]}
 ``/param`` bottles (/root/reference/scripts/vf:145,209-275); on every message it rebuilds the summed
 field (vf:276-293).  Here one :class:`FieldSets` keeps those dictionaries for B arms, applies the same
 acceptance rules to each bottle, and hands the arms whose set changed to ``Engine.set_fields`` -- the
-batched equivalent of the rebuild.  Malformed bottles are reported and ignored, never raised, like the
+batched equivalent of the rebuild -- or, when only a goal frame or obstacle coordinates moved, to
+``Engine.move_fields_host``, which rewrites those numbers on the device without repacking.  Malformed bottles are reported and ignored, never raised, like the
 reference (vf:264-266,275).
 """
 import logging
+import weakref
 
 import numpy as np
 
@@ -25,6 +27,9 @@ class FieldSets:
         self.max_fields = int(max_fields)
         self.sets = [dict() for _ in range(self.batch)]  # id -> [force, type, params]
         self.dirty = set()
+        # per arm the set flushed last ({id: [force, type, params]}, None: never) and the engine it went to: what tells a move from a new structure
+        self._flushed = [None] * self.batch
+        self._flushed_to = None
 
     # -- one /param bottle for one arm (vf:212-275) ---------------------------------------------
     def handle_param(self, arm, bottle):
@@ -92,21 +97,101 @@ class FieldSets:
             cnt[j] = len(self.sets[a])
         return rec, cnt
 
+    # -- what a move carries (Engine.move_fields_host) ---------------------------------------------
+    @staticmethod
+    def _goal_id(fields):
+        """The id of the goal block: the lowest-id attractor (vfik_set_fields packs that one into the goal planes)."""
+        ids = [i for i in sorted(fields) if fields[i][1] == _abi.FIELD_ATTRACTOR]
+        return ids[0] if ids else None
+
+    def _move_of(self, arm):
+        """How the arm's set differs from what was flushed last: None when the structure changed (ids, types, forces, or a
+        parameter a move does not carry -- the arm needs set_fields), else (goal12 or None, {k: [x, y, z, radius]}) with the
+        new goal frame rows 0-2 and the new coordinates of the k-th decay repeller in ascending-id order; both empty when
+        nothing changed at all."""
+        old, new = self._flushed[arm], self.sets[arm]
+        if old is None or sorted(old) != sorted(new):
+            return None
+        goal_id = self._goal_id(new)
+        goal, reps, k = None, {}, 0
+        for vf_id in sorted(new):
+            (f0, t0, p0), (f1, t1, p1) = old[vf_id], new[vf_id]
+            if t0 != t1 or f0 != f1:
+                return None
+            if vf_id == goal_id:
+                if p0[12:] != p1[12:]:      # the frame's last row and the slow-down distance stay
+                    return None
+                if p0[:12] != p1[:12]:
+                    goal = p1[:12]
+            elif t1 == _abi.FIELD_REPELLER:
+                if p0[4:] != p1[4:]:        # safe distance and order stay
+                    return None
+                if p0[:4] != p1[:4]:
+                    reps[k] = p1[:4]
+                k += 1
+            elif p0 != p1:                  # funnels, hemispheres, further attractors are not moved
+                return None
+        return goal, reps
+
+    def forget(self):
+        """Forget what was flushed: the next flush sends every changed arm through set_fields (for a caller that wrote
+        field sets to the engine behind this object's back)."""
+        self._flushed = [None] * self.batch
+        self._flushed_to = None
+
+    @staticmethod
+    def _runs(arms):
+        start = prev = arms[0]
+        for a in arms[1:]:
+            if a != prev + 1:
+                yield start, prev
+                start = a
+            prev = a
+        yield start, prev
+
     def flush(self, engine):
-        """Upload the sets of all arms that changed since the last flush, as contiguous arm ranges."""
+        """Upload the sets of all arms that changed since the last flush, as contiguous arm ranges.  Arms whose change leaves
+        the structure flushed last intact -- a goal frame and / or x y z radius of decay repellers re-sent with new numbers, what
+        the object feeder does for an object that moves (object_feeder:214-354) -- go through ``engine.move_fields_host`` (rows
+        that did not change are NaN: they stay); every other arm, and every arm of an engine without that method, goes through
+        ``engine.set_fields``.  The device holds the same field sets either way."""
         if not self.dirty:
             return 0
         arms = sorted(self.dirty)
         self.dirty.clear()
-        start = prev = arms[0]
-        ranges = []
-        for a in arms[1:]:
-            if a != prev + 1:
-                ranges.append((start, prev))
-                start = a
-            prev = a
-        ranges.append((start, prev))
-        for lo, hi in ranges:
+        if self._flushed_to is None or self._flushed_to() is not engine:
+            self.forget()
+        can_move = hasattr(engine, "move_fields_host")
+        moves, full = {}, []
+        for a in arms:
+            mv = self._move_of(a) if can_move else None
+            if mv is None:
+                full.append(a)
+            elif mv[0] is not None or mv[1]:
+                moves[a] = mv
+        for lo, hi in (self._runs(full) if full else ()):
             rec, cnt = self.records(range(lo, hi + 1))
             engine.set_fields(rec, cnt, first_arm=lo)
+        for lo, hi in (self._runs(sorted(moves)) if moves else ()):
+            n = hi - lo + 1
+            n_rep = max(max(moves[a][1], default=-1) for a in range(lo, hi + 1)) + 1
+            goal = rep = None
+            if any(moves[a][0] is not None for a in range(lo, hi + 1)):
+                goal = np.full((n, 16), np.nan)
+            if n_rep:
+                rep = np.full((n, n_rep, 4), np.nan)
+            for a in range(lo, hi + 1):
+                g, reps = moves[a]
+                if g is not None:
+                    goal[a - lo, :12] = g
+                    goal[a - lo, 12:] = (0.0, 0.0, 0.0, 1.0)
+                for k, xyzr in reps.items():
+                    rep[a - lo, k] = xyzr
+            engine.move_fields_host(goal=goal, repellers=rep, first_arm=lo)
+        try:
+            self._flushed_to = weakref.ref(engine)
+        except TypeError:
+            self._flushed_to = (lambda e=engine: e)
+        for a in arms:
+            self._flushed[a] = {i: [f, t, list(p)] for i, (f, t, p) in self.sets[a].items()}
         return len(arms)

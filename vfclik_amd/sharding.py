@@ -120,6 +120,12 @@ class ShardedEngine:
         for (a, b, e), f, c in zip(self.parts, self._rows(fields, "fields", global_rows), self._rows(counts, "counts", global_rows)):
             e.set_fields(f, c)
 
+    def move_fields_host(self, goal=None, repellers=None, global_rows=True):
+        """Engine.move_fields_host over the shard: goal frames (rows, 16) and / or x y z radius (rows, n_rep, 4) of the whole
+        batch (global_rows) or of this rank's rows, split as :meth:`set_fields` splits its arrays."""
+        for (a, b, e), g, r in zip(self.parts, self._rows(goal, "goal", global_rows), self._rows(repellers, "repellers", global_rows)):
+            e.move_fields_host(goal=g, repellers=r)
+
     # the columns of every output row (Engine._OUT_SHAPES): what a rank without a single arm still has to return
     _COLS = {"qdot_vf": "n", "qdot_null": "n", "qdot_out": "n", "pose": 16, "pose_nt": 16, "v6": 6, "qdist": "n", "goal_dist": 2,
              "q_ref_out": "n", "track_error": 8}
