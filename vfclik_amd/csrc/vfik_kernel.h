@@ -54,6 +54,9 @@ struct KConst {
     // c = crev*cos(q+off) + cprs, s = crev*sin(q+off) + sprs, displacement = qd*q + d: revolute joints have
     // (crev, cprs, sprs, qd) = (1, 0, 0, 0), prismatic ones (0, cos off, sin off, 1) -- arithmetic blends
     struct DH { double off, crev, cprs, sprs, qd, d, a, ca, sa, pad; } dh[NJ];   // dh[0].pad: the batch's uniform repeller FORCE (below)
+    // dh[1].pad: 1 / rot_slow (0: no rotational slow-down), which every wave formed with rcp_nr until round 5.  In a pad, so that no member moves:
+    // as a member of its own behind cos_slow it moved every later member by 8 bytes, and a 14-joint general variant then spilled 52 B per lane.
+    // (That rot_slow lies in (0, pi/8) -- the short arctangent of rot_axis_angle -- the kernels read off cos_slow > cos(pi/8).)
     double tail_c, tail_s, tail_e;  // trailing z-screw of the last fixed transform
     // safe distance of every decay repeller of the batch when they all share one (and one force, dh[0].pad): the uniform repeller
     // image of the straight-line path then carries (x y z radius) per slot only (vfik_abi.cpp: pack_fields, vfik_set_fields)
@@ -85,9 +88,11 @@ struct KConst {
 // ((sin, cos)(k pi/32), k = 0..63) that every wave copies to LDS with the kinematics block.
 // where the host patches the uniform repeller pair into the device image (vfik_abi.cpp: write_uniform_pair)
 #define VFIK_KCONST_REP_FORCE_OFF ((12 + 9) * 8)
+#define VFIK_KCONST_ROT_SLOW_INV_OFF ((12 + 10 + 9) * 8)   // dh[1].pad: 1 / rot_slow
 #define VFIK_KCONST_REP_SAFE_OFF(nj) ((12 + 10 * (nj) + 3) * 8)
 static_assert(offsetof(KConst<7>, rep_safe) == VFIK_KCONST_REP_SAFE_OFF(7) && offsetof(KConst<14>, rep_safe) == VFIK_KCONST_REP_SAFE_OFF(14), "KConst::rep_safe");
 static_assert(offsetof(KConst<7>, dh) + offsetof(KConst<7>::DH, pad) == VFIK_KCONST_REP_FORCE_OFF, "KConst::dh[0].pad");
+static_assert(offsetof(KConst<7>, dh) + sizeof(KConst<7>::DH) + offsetof(KConst<7>::DH, pad) == VFIK_KCONST_ROT_SLOW_INV_OFF && offsetof(KConst<14>, dh) == offsetof(KConst<7>, dh), "KConst::dh[1].pad");
 static_assert(offsetof(KConst<7>, wq) + 7 * 8 == KConst<7>::KIN_BYTES && offsetof(KConst<14>, wq) + 14 * 8 == KConst<14>::KIN_BYTES, "KConst::wq closes the LDS-copied block");
 static_assert(KConst<7>::KIN_BYTES <= 1024 && KConst<6>::KIN_BYTES <= 1024 && KConst<10>::KIN_BYTES <= 2048 && KConst<14>::KIN_BYTES <= 2048, "the copied block keeps its row count");
 template <int NJ> struct KTab { static constexpr int OFFSET = ((int)sizeof(KConst<NJ>) + 1023) / 1024 * 1024; };

@@ -197,14 +197,19 @@ __device__ __forceinline__ void sincos_fast_n(const double* x, double* s, double
 template <int N>
 __device__ __forceinline__ void sincos_tab_n(const double* x, const char* tab, double* s, double* c) {
     typedef double d2 __attribute__((ext_vector_type(2)));
-    double k[N], r[N], z[N], ps[N], pc[N], S[N], C[N];
+    // k = rint(x 32/pi) by the magic-number addition: x 32/pi + 1.5 2^52 rounds to an integer, whose low bits are the low dword of
+    // the sum (two's complement, |k| < 2^31) -- one fma and one and for the table index where rint, cvt_i32 and and were.
+    constexpr double MAGIC = 6755399441055744.0;
+    double k[N], r[N], z[N], ps[N], pc[N], S[N], C[N], km[N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) k[i] = __builtin_rint(x[i] * 10.185916357881302);
+    for (int i = 0; i < N; ++i) km[i] = __builtin_fma(x[i], 10.185916357881302, MAGIC);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        const d2 t = *reinterpret_cast<const d2*>(tab + (((int)k[i]) & 63) * 16);
+        const d2 t = *reinterpret_cast<const d2*>(tab + ((unsigned)__double2loint(km[i]) & 63u) * 16);
         S[i] = t.x; C[i] = t.y;
     }
+#pragma unroll
+    for (int i = 0; i < N; ++i) k[i] = km[i] - MAGIC;
 #pragma unroll
     for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 0.09817477042088285, x[i]);
 #pragma unroll
@@ -280,8 +285,18 @@ __device__ __forceinline__ double pow_order(double x, double order) {
     return isint ? powi_uniform(x, n) : pow(x, order);
 }
 
+// atan(t), |t| <= tan(pi/8): fdlibm's 11-coefficient kernel (s_atan.c, good to < 1 ulp for |t| < 7/16)
+__device__ __forceinline__ double atan_kernel(double t) {
+    const double z = t * t, w = z * z;
+    const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
+                      w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
+    const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
+                      w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
+    return t - t * (s1 + s2);
+}
+
 // atan2(y, x) for y >= 0 (an angle in [0, pi]), branch-free: two reductions bring the argument of the
-// arctangent below tan(pi/8), where fdlibm's 11-coefficient kernel (s_atan.c, |x| < 7/16) is good to < 1 ulp.
+// arctangent below tan(pi/8), where atan_kernel (above) is good to < 1 ulp.
 // ocml's atan2 costs a lone wave ~2 000 cycles (tools/stamps.py: the waves that needed it ended the kernel
 // 0.4 us after the rest); this is ~45 instructions.
 __device__ __forceinline__ double atan2_pos(double y, double x) {
@@ -292,12 +307,7 @@ __device__ __forceinline__ double atan2_pos(double y, double x) {
     const bool upper = t > 0.41421356237309503;        // tan(pi/8): atan(t) = pi/4 + atan((t - 1) / (t + 1))
     const double tr = (t - 1.0) * rcp_nr(t + 1.0);
     t = upper ? tr : t;
-    const double z = t * t, w = z * z;
-    const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
-                      w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
-    const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
-                      w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
-    double a = t - t * (s1 + s2);
+    double a = atan_kernel(t);
     a = upper ? 0.78539816339744830962 + a : a;        // angle from the nearer axis, in [0, pi/4]
     a = steep ? 1.57079632679489661923 - a : a;        // angle from the x axis of (|x|, y)
     return x < 0.0 ? 3.14159265358979323846 - a : a;
@@ -308,6 +318,15 @@ __device__ __forceinline__ double atan2_pos(double y, double x) {
 // where the antisymmetric part vanishes, is fixed up from the symmetric part under a wave-uniform
 // test.  The angle itself is only needed below the slow-down angle: `need_theta` (wave-uniform) says
 // whether any lane can be that close; otherwise theta is reported as pi (any value >= rot_slow does).
+// A slow-down angle below pi/8 (cos_slow > cos(pi/8); the default is 0.3) makes that evaluation short: a lane inside the angle has
+// s / c <= tan(rot_slow) < tan(pi/8), so neither reduction of atan2_pos can fire for it -- its second reciprocal, the selects and
+// the three additions go, the lane's own operations stay as they were (bit for bit); a lane outside the angle keeps pi.  The waves
+// that get here end the launch: one in eleven of a batch of random goals has such a lane, and every launch waits for its slowest wave.
+// This takes s^2 + c^2 = 1, i.e. goal and tool rotations that ARE rotations (float32 rounding of the goal moves s / c by 1e-7).  A scaled
+// or skewed goal matrix can have c > cos_slow with s / c above tan(pi/8): atan_kernel is then off its interval (still < 1 ulp up
+// to 7/16, degrading beyond), where atan2_pos reduced any (s, c); the value feeds min(1, theta / rot_slow) alone.
+// (SHORT = false: without that short evaluation -- the general field path's variants, which sit at their register limit)
+template <bool SHORT>
 __device__ __forceinline__ void rot_axis_angle(const double* R, const double* G, double cos_slow, double* axis, double& theta,
                                                bool& has_axis) {
     double E[9];
@@ -322,7 +341,14 @@ __device__ __forceinline__ void rot_axis_angle(const double* R, const double* G,
     axis[0] = a0 * sinv; axis[1] = a1 * sinv; axis[2] = a2 * sinv;
     has_axis = s >= EPS_LEN;
     theta = 3.14159265358979323846;
-    if (__any(c > cos_slow)) theta = atan2_pos(s, c);  // some lane is within the slow-down angle
+    if (__any(c > cos_slow)) {  // some lane is within the slow-down angle
+        if (SHORT && cos_slow > 0.92387953251128674) {  // cos(pi/8): wave-uniform
+            const double th = atan_kernel(s * rcp_nr(c));
+            theta = c > cos_slow ? th : theta;
+        } else {
+            theta = atan2_pos(s, c);
+        }
+    }
     const bool half_turn = s < 1e-4 && c < 0.0;
     if (__any(half_turn)) {
         // theta near pi (4 arms in 65 536 random goals): the axis comes from the symmetric part,
@@ -341,16 +367,21 @@ __device__ __forceinline__ void rot_axis_angle(const double* R, const double* G,
         if (half_turn) {
             axis[0] = x * k; axis[1] = y * k; axis[2] = z * k;
             has_axis = true;
-            theta = atan2_pos(s, c);
+            // pi - atan(s / |c|), s / |c| < 1.0001e-4: atan(t) = t - t^3 / 3 to 2e-21, within an ulp of pi of atan2_pos(s, c)
+            const double t = s * rcp_nr(-c);
+            theta = 3.14159265358979323846 - t * __builtin_fma(t * t, -3.33333333333333333333e-01, 1.0);
         }
     }
 }
 
 // type 1, point attractor: G = goal rotation (9) + position (3); adds force*vector to tot, scales sc.
 // `on` masks the whole contribution (goal block absent): selects instead of a branch.
+// SHORT (the straight-line variants and the eight-lanes kernel): rot_axis_angle's short arctangent, and 1 / rot_slow from the caller
+// (`rot_slow_inv`: the batch constant); without it the reciprocal is formed here and the argument is not read.
+template <bool SHORT = true>
 __device__ __forceinline__ void attractor(const double* R, const double* p, const double* GR, const double* Gp,
                                           double slow, double force, double rot_slow, double cos_slow, bool on,
-                                          double* tot, double* sc, double* dist = nullptr) {
+                                          double* tot, double* sc, double* dist = nullptr, double rot_slow_inv = 0.0) {
     const double dx = Gp[0] - p[0], dy = Gp[1] - p[1], dz = Gp[2] - p[2];
     double D, Dinv;
     sqrt_rsqrt(dx * dx + dy * dy + dz * dz, D, Dinv);
@@ -358,11 +389,11 @@ __device__ __forceinline__ void attractor(const double* R, const double* p, cons
     tot[0] += dx * kt; tot[1] += dy * kt; tot[2] += dz * kt;
     double ax[3], th;
     bool has_axis;
-    rot_axis_angle(R, GR, cos_slow, ax, th, has_axis);
+    rot_axis_angle<SHORT>(R, GR, cos_slow, ax, th, has_axis);
     const bool rot_on = on && has_axis && th > EPS_LEN;  // selects, not a multiply by 0: an absent goal's axis may be NaN
     tot[3] += rot_on ? ax[0] * force : 0.0; tot[4] += rot_on ? ax[1] * force : 0.0; tot[5] += rot_on ? ax[2] * force : 0.0;
     const double s0 = slow > 0.0 ? fmin(1.0, D * rcp_nr(slow)) : 1.0;
-    const double s1 = rot_slow > 0.0 ? fmin(1.0, th * rcp_nr(rot_slow)) : 1.0;
+    const double s1 = rot_slow > 0.0 ? fmin(1.0, th * (SHORT ? rot_slow_inv : rcp_nr(rot_slow))) : 1.0;
     sc[0] *= on ? s0 : 1.0;
     sc[1] *= on ? s1 : 1.0;
     if (dist) { dist[0] = D; dist[1] = th; }
@@ -432,7 +463,7 @@ __device__ void eval_slot(const RD& rd, int m, const double* Rt, const double* p
         GR[5] = rd(m + 1, 0); Gp[1] = rd(m + 1, 1);
         GR[6] = rd(m + 1, 2); GR[7] = rd(m + 1, 3); GR[8] = rd(m + 1, 4);
         Gp[2] = rd(m + 1, 5);
-        attractor(Rt, pt, GR, Gp, rd(m + 2, 4), force, rot_slow, cos_slow, true, tot, sc);
+        attractor<false>(Rt, pt, GR, Gp, rd(m + 2, 4), force, rot_slow, cos_slow, true, tot, sc);
     }
 }
 
@@ -1467,23 +1498,29 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                 A[r][r] += HOTK(lambda2);
             }
         }
-        // LDL^T (unit lower L stored in A's strict lower part, d on the diagonal)
+        // LDL^T (unit lower L stored in A's strict lower part, d on the diagonal).  v_k = L_jk d_k is the entry of row j as it stood
+        // BEFORE column k scaled it by 1 / d_k: kept (U) instead of multiplied back -- 15 multiplications less, and the exact value
+        // instead of one that went through a rounded reciprocal and back.
+        // (the long chains have no registers to keep them in: they multiply back, as every chain did until round 5)
+        constexpr bool KEEPU = NJ <= 8;
+        double U[6][6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            double v[6];  // v_k = L_jk d_k
+            if constexpr (!KEEPU) {
 #pragma unroll
-            for (int k = 0; k < j; ++k) v[k] = A[j][k] * A[k][k];
+                for (int k = 0; k < j; ++k) U[j][k] = A[j][k] * A[k][k];
+            }
             double dj = A[j][j];
 #pragma unroll
-            for (int k = 0; k < j; ++k) dj = __builtin_fma(-A[j][k], v[k], dj);
+            for (int k = 0; k < j; ++k) dj = __builtin_fma(-A[j][k], U[j][k], dj);
             A[j][j] = dj;
             dinv[j] = rcp_1nr(dj);
 #pragma unroll
             for (int k = 0; k < j; ++k)  // rows below j, one k at a time: the rows are independent chains
 #pragma unroll
-                for (int i = j + 1; i < 6; ++i) A[i][j] = __builtin_fma(-A[i][k], v[k], A[i][j]);
+                for (int i = j + 1; i < 6; ++i) A[i][j] = __builtin_fma(-A[i][k], U[j][k], A[i][j]);
 #pragma unroll
-            for (int i = j + 1; i < 6; ++i) A[i][j] *= dinv[j];
+            for (int i = j + 1; i < 6; ++i) { if constexpr (KEEPU) U[i][j] = A[i][j]; A[i][j] *= dinv[j]; }
         }
     };
     if constexpr (EARLY_FACTOR) ik_factor();
@@ -1511,7 +1548,10 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                 Gp[r] = gq[4 * r + 3];
             }
             // a.goal_dist requested: the angle is needed whatever its size (cos_slow = -2 forces atan2)
-            attractor(Rt, pt, GR, Gp, gq[13], gq[14], HOTK(rot_slow), a.goal_dist ? -2.0 : HOTK(cos_slow), gq[12] != 0.0, tot, sc, gdist);
+            // 1 / rot_slow (read by the straight-line variants only): the batch constant, KConst::dh[1].pad; the long chains, at their register
+            // limit, form it here as every wave did until round 5
+            const double rot_slow_inv = NJ >= 10 ? (HOTK(rot_slow) > 0.0 ? rcp_nr(HOTK(rot_slow)) : 0.0) : kc->dh[1].pad;
+            attractor<FASTF>(Rt, pt, GR, Gp, gq[13], gq[14], HOTK(rot_slow), a.goal_dist ? -2.0 : HOTK(cos_slow), gq[12] != 0.0, tot, sc, gdist, rot_slow_inv);
         }
     }
     if constexpr (FUN) {
@@ -1745,10 +1785,20 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                     }
                 }
                 }
+                if constexpr (UNI) {   // one force for every slot: it multiplies the chunk's sum, not each term
+                    double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int m = 0; m < PRE; ++m) {
+                        const double k = fmin(rp[m], MAG_CAP) * di[m];
+                        acc[0] += dx[m] * k; acc[1] += dy[m] * k; acc[2] += dz[m] * k;
+                    }
+                    tot[0] = __builtin_fma(fk[0], acc[0], tot[0]); tot[1] = __builtin_fma(fk[0], acc[1], tot[1]); tot[2] = __builtin_fma(fk[0], acc[2], tot[2]);
+                } else {
 #pragma unroll
                 for (int m = 0; m < PRE; ++m) {
                     const double k = fk[m] * fmin(rp[m], MAG_CAP) * di[m];
                     tot[0] += dx[m] * k; tot[1] += dy[m] * k; tot[2] += dz[m] * k;
+                }
                 }
             };
             // the first chunk (requested during the kinematics, or -- PERS -- at the start of the launch / under the previous
@@ -2415,7 +2465,7 @@ __global__ void __launch_bounds__(256) track_kernel(const T* pose, const T* v6, 
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c) { Ra[3 * r + c] = P[4 * r + c]; Rb[3 * r + c] = F[4 * r + c]; }
-        rot_axis_angle(Ra, Rb, -2.0, ax, th, has_axis);
+        rot_axis_angle<false>(Ra, Rb, -2.0, ax, th, has_axis);
         const double ext_vel_mag = sqrt(ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2]);
         const double ext_rot_mag = has_axis ? th : 0.0;
         // the command issued check_delay = 4 cycles ago is the oldest entry of the full buffer (vf:363)
@@ -2511,7 +2561,7 @@ __global__ void __launch_bounds__(256) probe_kernel(const T* pose, const T* goal
         for (int c = 0; c < 3; ++c) GR[3 * r + c] = gq[4 * r + c];
         Gp[r] = gq[4 * r + 3];
     }
-    attractor(Rt, pt, GR, Gp, gq[13], gq[14], rot_slow, cos_slow, gq[12] != 0.0, tot, sc, nullptr);
+    attractor<false>(Rt, pt, GR, Gp, gq[13], gq[14], rot_slow, cos_slow, gq[12] != 0.0, tot, sc, nullptr);
     const T* sq = slots + (long)arm * 4;
     const SlotGlobal<T> rg{sq, Qp};
     for (int m = 0; m < slots_used; ++m) eval_slot(rg, m, Rt, pt, rot_slow, cos_slow, tot, sc);
@@ -2777,7 +2827,7 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
             for (int c = 0; c < 3; ++c) GR[3 * r + c] = gq[4 * r + c];
             Gp[r] = gq[4 * r + 3];
         }
-        attractor(R, p, GR, Gp, gq[13], gq[14], kc->rot_slow, kc->cos_slow, gq[12] != 0.0, tot, sc, gdist);
+        attractor(R, p, GR, Gp, gq[13], gq[14], kc->rot_slow, kc->cos_slow, gq[12] != 0.0, tot, sc, gdist, kc->dh[1].pad);
     }
 #pragma unroll
     for (int l = 0; l < 8; ++l) { tot[0] += L[64 + 4 * l]; tot[1] += L[64 + 4 * l + 1]; tot[2] += L[64 + 4 * l + 2]; }
@@ -2828,22 +2878,20 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
 #pragma unroll
             for (int c = 0; c <= r; ++c) A[r][c] = __builtin_fma(kc->wy[r] * kc->wy[c], A[r][c], r == c ? kc->lambda2 : 0.0);
     }
+    double U[6][6];   // the entries before their column's scaling (v_k = L_jk d_k), as cycle_body's ik_factor keeps them
 #pragma unroll
     for (int jj = 0; jj < 6; ++jj) {
-        double v[6];
-#pragma unroll
-        for (int k = 0; k < jj; ++k) v[k] = A[jj][k] * A[k][k];
         double dj = A[jj][jj];
 #pragma unroll
-        for (int k = 0; k < jj; ++k) dj = __builtin_fma(-A[jj][k], v[k], dj);
+        for (int k = 0; k < jj; ++k) dj = __builtin_fma(-A[jj][k], U[jj][k], dj);
         A[jj][jj] = dj;
         dinv[jj] = rcp_nr(dj);
 #pragma unroll
         for (int k = 0; k < jj; ++k)
 #pragma unroll
-            for (int i = jj + 1; i < 6; ++i) A[i][jj] = __builtin_fma(-A[i][k], v[k], A[i][jj]);
+            for (int i = jj + 1; i < 6; ++i) A[i][jj] = __builtin_fma(-A[i][k], U[jj][k], A[i][jj]);
 #pragma unroll
-        for (int i = jj + 1; i < 6; ++i) A[i][jj] *= dinv[jj];
+        for (int i = jj + 1; i < 6; ++i) { U[i][jj] = A[i][jj]; A[i][jj] *= dinv[jj]; }
     }
     double y[6];
 #pragma unroll
@@ -3325,6 +3373,8 @@ double kconst_fill_t(void* dst, const vfik_chain& ch, const vfik_params& p, cons
     c.lambda2 = p.lambda * p.lambda;
     c.rot_slow = p.rot_slowdown;
     c.cos_slow = p.rot_slowdown > 0.0 && p.rot_slowdown < 3.14159265358979323846 ? std::cos(p.rot_slowdown) : -2.0;  // -2: always evaluate the angle
+    // (the kernels' rcp_nr(rot_slow) of old is this value: its last Newton step rounds (1 - e^2) / rot_slow with e < 2^-48 once)
+    c.dh[1].pad = p.rot_slowdown > 0.0 ? 1.0 / p.rot_slowdown : 0.0;   // (KConst: 1 / rot_slow)
     c.null_gain = p.null_gain;
     c.lookahead = p.lookahead;
     c.max_vel = p.max_vel;
