@@ -1,0 +1,339 @@
+"""A high-precision restatement of the kinematics and the damped-least-squares solve, and the poses of the conditioning sweep.
+
+A helper of the suite, not a conftest.py: tests/test_oracle_conditioning.py holds the C oracle to it on the CPU, tests/test_gpu_conditioning.py
+and tests/test_gpu_set_params.py hold the HIP kernels to it on the GPU.
+
+The reference.  From a Chain, rows of q, a twist per arm, lambda, wy, wq, in 50-digit arithmetic (mpmath; numpy.longdouble with a 64-bit
+mantissa where mpmath cannot be imported):
+
+  * forward kinematics in chain.py's z-normal form, T = B[0] Jz(q_1) B[1] ... Jz(q_n) B[n], the doubles of chain.B and of q taken as exact;
+  * the geometric Jacobian about the flange origin in the base frame, rows (v, w) as oracle_c.jacobian orders them;
+  * qdot = Wq Jw^T (Jw Jw^T + lambda^2 I)^-1 Wy tw with Jw = Wy J Wq (identity tool: the twist is taken at the flange).
+
+The twist is an INPUT (the oracle's v6 for the same, already rounded inputs): the field evaluation is well conditioned and has tests of its
+own; what is held here is the kinematics and the solve.  Per arm the helper also returns cond = (s1^2 + lambda^2) / (s6^2 + lambda^2), s the
+singular values of Jw (numpy.linalg.svd of the rounded high-precision Jw), and the solve's own relative residual |A y - Wy tw| / |Wy tw|.
+
+Results are returned as pairs of doubles (hi, lo) with hi + lo = the high-precision value to ~32 digits, so that `error` does not add the
+half ulp a reference rounded to one double would carry.
+
+The kinematics of a pose set and each solve are cached at module level: the kernel-family runs of one case share one reference.
+
+The poses (make_case).  B = 192 arms = three waves = twenty-four groups of eight; arm b has pattern index p = b mod 24, kind p mod 6 and
+offset eps = EPS[p div 6], so that every eight consecutive arms hold every kind:
+
+  kind 0  every odd-indexed joint = +-eps     shoulder, elbow and wrist singular together
+  kind 1  joint 3 = +-eps                     elbow stretched
+  kind 2  joint n-2 = +-eps                   wrist
+  kind 3  every joint = +-eps                 the zero pose
+  kind 4  q_i = (k_i + (b mod 2)/2) pi/32, integer k_i in [-20, 20], clipped to 0.95 of the limits:
+          the nodes of the sin / cos table and the midpoints between them, where the rounding to a node is a tie
+  kind 5  the regular pose of synth.make_workload
+
+(joint indices from 0).  q is rounded to the I/O type before either side sees it.  The `regular` pose set is make_workload's own (kind 5
+throughout): lambda = 0, and the chain whose limits of +-64 rad put the angles up to eight turns away."""
+import math
+
+import numpy as np
+
+try:
+    import mpmath as _mpm
+    _mpm.mp.dps = 50
+    BACKEND = "mpmath"
+    _num, _sin, _cos = _mpm.mpf, _mpm.sin, _mpm.cos
+    RESIDUAL_BAR = 1e-30
+except ImportError:   # the fall-back: a 64-bit mantissa, u_ref = 2^-64 = u / 2048.  Anything shorter is no reference: fail, do not skip.
+    assert np.finfo(np.longdouble).eps < 1.2e-19, "no mpmath, and numpy.longdouble is no wider than double here"
+    BACKEND = "longdouble"
+    _num, _sin, _cos = np.longdouble, np.sin, np.cos
+    RESIDUAL_BAR = 64 * float(np.finfo(np.longdouble).eps)
+
+U = 2.0 ** -53
+B_ARMS = 192
+EPS = (0.0, 1e-9, 1e-6, 1e-3)
+N_KINDS = 6
+ROBOTS = ("powercube6", "lwr", "lwr_dual14", "lwr_wide")
+LAMBDAS = (0.1, 1e-2, 1e-3)
+WY = (1.0, 1.0, 1.0, 0.3, 0.3, 0.1)
+WQ_HEAD = (1.0, 0.5, 1.0, 0.7, 1.0, 0.4)
+S_BAR = {np.float32: 1e-6, np.float64: 1e-9}   # the suite's bars (tests/test_gpu_parity.py)
+K_MARGIN = 8.0
+
+
+def weights(name, n):
+    """(wy, wq): `unit`, or the sweep's weights (wq = 1, 0.5, 1, 0.7, 1, 0.4, 1, 1, ...)."""
+    if name == "unit":
+        return (1.0,) * 6, (1.0,) * n
+    assert name == "weighted"
+    return WY, tuple((WQ_HEAD + (1.0,) * n)[:n])
+
+
+def chain_of(robot):
+    from vfclik_amd import chain, robots
+    if robot == "lwr_wide":   # the LWR's DH table (the same pattern, hence the same lean kernels) with limits of +-64 rad
+        lim = np.full(7, 64.0)
+        return chain.Chain.from_dh(robots._LWR_DH, -lim, lim, name="lwr_wide")
+    return robots.by_name(robot)
+
+
+def pattern(B=B_ARMS):
+    """(kind, index into EPS) per arm"""
+    p = np.arange(B) % (N_KINDS * len(EPS))
+    return p % N_KINDS, p // N_KINDS
+
+
+def make_case(robot, io_dtype, poses="mixed"):
+    """(chain, workload, kinds, eps) -- B_ARMS arms of make_workload(seed 3, two obstacles); `mixed`: the joints overwritten by kind."""
+    from vfclik_amd import synth
+    chain = chain_of(robot)
+    n, B = chain.n, B_ARMS
+    w = synth.make_workload(chain, B, 2, seed=3, io_dtype=io_dtype)
+    if poses == "regular":
+        return chain, w, np.full(B, 5), np.zeros(B)
+    assert poses == "mixed" and robot != "lwr_wide"
+    kinds, ie = pattern(B)
+    eps = np.asarray(EPS)[ie]
+    rng = np.random.default_rng(31)
+    sign = rng.choice([-1.0, 1.0], size=(B, n))
+    knode = rng.integers(-20, 21, size=(B, n))
+    q = w["q"]
+    for b in range(B):
+        k = kinds[b]
+        if k == 0:
+            q[b, 1::2] = eps[b] * sign[b, 1::2]
+        elif k == 1:
+            q[b, 3] = eps[b] * sign[b, 3]
+        elif k == 2:
+            q[b, n - 2] = eps[b] * sign[b, n - 2]
+        elif k == 3:
+            q[b, :] = eps[b] * sign[b, :]
+        elif k == 4:
+            q[b, :] = np.clip((knode[b] + 0.5 * (b % 2)) * (math.pi / 32), 0.95 * chain.q_lo, 0.95 * chain.q_hi)
+    w["q"] = q.astype(io_dtype).astype(np.float64)
+    return chain, w, kinds, eps
+
+
+# ---- the arithmetic ----------------------------------------------------------------------------------------------------------------
+def _frame(B12):
+    return [[_num(float(B12[r, c])) for c in range(4)] for r in range(3)]
+
+
+def _mul(X, Y):
+    """3x4 frames with the implicit last row (0 0 0 1)"""
+    Z = [[None] * 4 for _ in range(3)]
+    for i in range(3):
+        for j in range(4):
+            s = X[i][0] * Y[0][j] + X[i][1] * Y[1][j] + X[i][2] * Y[2][j]
+            Z[i][j] = s + X[i][3] if j == 3 else s
+    return Z
+
+
+def _fk_jac(chain, q):
+    """one arm: (T 3x4, J 6 x n) in the high-precision type"""
+    n = chain.n
+    X = _frame(chain.B[0])
+    z, o = [], []
+    for i in range(n):
+        z.append([X[0][2], X[1][2], X[2][2]])
+        o.append([X[0][3], X[1][3], X[2][3]])
+        qi = _num(float(q[i]))
+        if chain.jtype[i] == 0:   # X Jz(q): columns 0 and 1 turn
+            c, s = _cos(qi), _sin(qi)
+            for r in range(3):
+                X[r][0], X[r][1] = X[r][0] * c + X[r][1] * s, X[r][1] * c - X[r][0] * s
+        else:                     # a shift along z
+            for r in range(3):
+                X[r][3] = X[r][3] + X[r][2] * qi
+        X = _mul(X, _frame(chain.B[i + 1]))
+    pe = [X[0][3], X[1][3], X[2][3]]
+    J = [[_num(0)] * n for _ in range(6)]
+    for i in range(n):
+        if chain.jtype[i] == 0:
+            r = [pe[k] - o[i][k] for k in range(3)]
+            zi = z[i]
+            v = [zi[1] * r[2] - zi[2] * r[1], zi[2] * r[0] - zi[0] * r[2], zi[0] * r[1] - zi[1] * r[0]]
+            for k in range(3):
+                J[k][i], J[3 + k][i] = v[k], zi[k]
+        else:
+            for k in range(3):
+                J[k][i] = z[i][k]
+    return X, J
+
+
+def _solve(J, n, tw, lam, wy, wq):
+    """one arm: (qdot [n], relative residual, Jw as doubles)"""
+    wy = [_num(float(x)) for x in wy]
+    wq = [_num(float(x)) for x in wq]
+    Jw = [[wy[r] * J[r][i] * wq[i] for i in range(n)] for r in range(6)]
+    lam2 = _num(float(lam)) * _num(float(lam))
+    A = [[None] * 6 for _ in range(6)]
+    for r in range(6):
+        for c in range(r + 1):
+            s = _num(0)
+            for i in range(n):
+                s = s + Jw[r][i] * Jw[c][i]
+            A[r][c] = A[c][r] = s + lam2 if r == c else s
+    rhs = [wy[r] * _num(float(tw[r])) for r in range(6)]
+    # LDL^T (A is symmetric positive definite, or semi-definite with a positive pivot sequence at lambda = 0 off the singularities)
+    L = [[_num(0)] * 6 for _ in range(6)]
+    d = [None] * 6
+    for j in range(6):
+        s = A[j][j]
+        for k in range(j):
+            s = s - L[j][k] * L[j][k] * d[k]
+        d[j] = s
+        for i in range(j + 1, 6):
+            t = A[i][j]
+            for k in range(j):
+                t = t - L[i][k] * L[j][k] * d[k]
+            L[i][j] = t / s
+    y = [None] * 6
+    for i in range(6):
+        s = rhs[i]
+        for k in range(i):
+            s = s - L[i][k] * y[k]
+        y[i] = s
+    for i in range(6):
+        y[i] = y[i] / d[i]
+    for i in range(5, -1, -1):
+        s = y[i]
+        for k in range(i + 1, 6):
+            s = s - L[k][i] * y[k]
+        y[i] = s
+    res2 = nrm2 = _num(0)
+    for r in range(6):
+        s = -rhs[r]
+        for c in range(6):
+            s = s + A[r][c] * y[c]
+        res2, nrm2 = res2 + s * s, nrm2 + rhs[r] * rhs[r]
+    qd = []
+    for i in range(n):
+        s = _num(0)
+        for r in range(6):
+            s = s + Jw[r][i] * y[r]
+        qd.append(wq[i] * s)
+    resid = math.sqrt(float(res2 / nrm2)) if nrm2 != 0 else 0.0
+    return qd, resid, [[float(x) for x in row] for row in Jw]
+
+
+def _hilo(x):
+    hi = float(x)
+    return hi, float(x - _num(hi))
+
+
+# ---- cached, batched ---------------------------------------------------------------------------------------------------------------
+_KIN, _SOL = {}, {}
+
+
+def kinematics(key, chain, q):
+    """[(T, J) per arm] of the pose set `key` (any hashable: robot, I/O type, pose set), computed once."""
+    if key not in _KIN:
+        _KIN[key] = (np.array(q, dtype=np.float64), [_fk_jac(chain, row) for row in np.asarray(q, dtype=np.float64)])
+    q0, kin = _KIN[key]
+    assert np.array_equal(q0, q), "kinematics(%r): another q under the same key" % (key,)
+    return kin
+
+
+def reference(key, chain, q, tw, lam, wy, wq, wkey):
+    """The reference of one case.  key: the pose set's (see kinematics); tw (B, 6); wy (6,) or (B, 6), wq (n,) or (B, n); wkey names
+    the weights in the cache.  Returns dict(qdot, qdot_lo (B, n), pose, pose_lo (B, 16), cond (B,), resid (B,)), not to be written to."""
+    ck = (key, float(lam), wkey)
+    if ck in _SOL:
+        tw0, out = _SOL[ck]
+        assert np.array_equal(tw0, tw), "reference(%r): another twist under the same key" % (ck,)
+        return out
+    kin = kinematics(key, chain, q)
+    B, n = len(kin), chain.n
+    wy = np.broadcast_to(np.asarray(wy, dtype=np.float64), (B, 6))
+    wq = np.broadcast_to(np.asarray(wq, dtype=np.float64)[..., :n], (B, n))
+    out = dict(qdot=np.zeros((B, n)), qdot_lo=np.zeros((B, n)), pose=np.zeros((B, 16)), pose_lo=np.zeros((B, 16)),
+               cond=np.zeros(B), resid=np.zeros(B))
+    out["pose"][:, 15] = 1.0
+    for b, (T, J) in enumerate(kin):
+        qd, out["resid"][b], Jw = _solve(J, n, tw[b], lam, wy[b], wq[b])
+        for i in range(n):
+            out["qdot"][b, i], out["qdot_lo"][b, i] = _hilo(qd[i])
+        for r in range(3):
+            for c in range(4):
+                out["pose"][b, 4 * r + c], out["pose_lo"][b, 4 * r + c] = _hilo(T[r][c])
+        s = np.linalg.svd(np.array(Jw), compute_uv=False)
+        out["cond"][b] = (s[0] ** 2 + lam * lam) / (s[5] ** 2 + lam * lam)
+    for v in out.values():
+        v.setflags(write=False)
+    _SOL[ck] = (np.array(tw, dtype=np.float64), out)
+    return out
+
+
+def error(got, ref, name):
+    """|got - reference| per element, the reference taken as hi + lo"""
+    return np.abs((np.asarray(got, dtype=np.float64) - ref[name]) - ref[name + "_lo"])
+
+
+def ratio(got_qdot, ref):
+    """per arm: max_i |got - reference| / (cond u max_i |qdot|) -- the error in units of what the conditioning allows"""
+    err = error(got_qdot, ref, "qdot").max(axis=1)
+    scale = ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1)
+    return err / scale, err
+
+
+# ---- the bar of the GPU tests (tests/test_gpu_conditioning.py documents it) -----------------------------------------------------------
+def bars(ref, io_dtype, R):
+    """(B, n) bar of qdot against the reference of one case; R: the oracle's worst ratio on it"""
+    K = K_MARGIN * max(1.0, R)
+    arm = np.maximum(S_BAR[io_dtype], K * ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1))
+    bar = np.repeat(arm[:, None], ref["qdot"].shape[1], axis=1)
+    if io_dtype == np.float32:
+        bar = bar + 2.0 ** -24 * np.abs(ref["qdot"])
+    return bar
+
+
+def check_qdot(got, ref, io_dtype, R, what, kinds, eps, failures, row=None):
+    """Compares one (B, n) output with the reference; appends to `failures`; returns (worst ratio, its arm).  The ratio is
+    err / (cond u |qdot|) with float32's half ulp of the store taken off the error first."""
+    got = np.asarray(got, dtype=np.float64)
+    err = error(got, ref, "qdot")
+    bar = bars(ref, io_dtype, R)
+    store = 2.0 ** -24 * np.abs(ref["qdot"]) if io_dtype == np.float32 else 0.0
+    rat = (np.maximum(err - store, 0.0)).max(axis=1) / (ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1))
+    b = int(np.argmax(rat))
+    over = err / bar
+    wb = int(np.argmax(over.max(axis=1)))
+    print("    %-28s ratio %9.3f (arm %3d kind %d eps %-5g cond %.2e)  worst err / bar %.3f (arm %d kind %d eps %g: err %.3e)"
+          % (what, rat[b], b, kinds[b], eps[b], ref["cond"][b], over.max(), wb, kinds[wb], eps[wb], err[wb].max()))
+    if row is not None:
+        row.append((what, rat[b], kinds[b], eps[b], over.max()))
+    if not np.all(np.isfinite(got)):
+        failures.append("%s: %d values are not finite" % (what, int((~np.isfinite(got)).sum())))
+    elif not np.all(err <= bar):
+        failures.append("%s: err / bar = %.2f on arm %d (kind %d, eps %g, cond %.2e): ratio %.1f against K = %.1f"
+                        % (what, over.max(), wb, kinds[wb], eps[wb], ref["cond"][wb], rat[wb], K_MARGIN * max(1.0, R)))
+    return rat[b], b
+
+
+def oracle_case(oc, robot, io_dtype, lam, wname, poses):
+    """One case on the C oracle and its reference: (chain, params, workload, kinds, eps, oracle outputs, reference, R) with R the oracle's
+    worst ratio of the case."""
+    from vfclik_amd import _abi
+    chain, w, kinds, eps = make_case(robot, io_dtype, poses)
+    wy, wq = weights(wname, chain.n)
+    params = _abi.default_params(wy=wy, wq=list(wq) + [1.0] * (_abi.MAX_JOINTS - chain.n), **{"lambda": lam})
+    orc = oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], want=("qdot_vf", "qdot_out", "pose", "v6", "status"))
+    ref = reference((robot, np.dtype(io_dtype).name, poses), chain, w["q"], orc["v6"], lam, wy, wq, wname)
+    R = float(ratio(orc["qdot_vf"], ref)[0].max())
+    return chain, params, w, kinds, eps, orc, ref, R
+
+
+def cases():
+    """(robot, lambda, weights, pose set) of the sweep: the three dampings on the mixed poses, lambda = 0 on the regular poses alone (at a
+    singular pose it divides by a zero pivot on both sides), every damping on the wide-limits chain's regular poses."""
+    out = []
+    for robot in ROBOTS:
+        for wname in ("unit", "weighted"):
+            for lam in LAMBDAS:
+                out.append((robot, lam, wname, "regular" if robot == "lwr_wide" else "mixed"))
+            out.append((robot, 0.0, wname, "regular"))
+    return out
+
+
+def case_id(c):
+    return "%s-lam%g-%s-%s" % c

@@ -70,8 +70,12 @@ __device__ __forceinline__ double rsqrt_1nr_pos(double x) {   // ... for x > 0 k
     return __builtin_fma(0.5 * y, e, y);
 }
 
-// 1/x from ONE Newton step on v_rcp_f64 (relative error ~1e-14, like rsqrt_1nr): the LDL^T pivots of the IK's normal matrix, whose
-// condition number is bounded by (sigma_max^2 + lambda^2) / lambda^2 ~ 1e3 -- 1e-11 in the joint velocities against a 1e-9 test bar.
+// 1/x from ONE Newton step on v_rcp_f64: the LDL^T pivots of the IK's normal matrix.  Measured on gfx950 (profiles/conditioning_accuracy.txt),
+// not assumed: the raw v_rcp_f64 is off by ~5e-9 relative (with it alone the joint velocities miss the reference by 5e7 cond u), so one step
+// leaves ~3e-17, under the rounding of its own last fma -- against the 50-digit reference (tests/test_gpu_conditioning.py) the joint
+// velocities are within 2.5 cond u at lambda = 0.1 and 2.1 cond u at lambda = 1e-2 and 1e-3 (cond up to 1.4e7, singular poses included),
+// cond = (sigma_1^2 + lambda^2) / (sigma_6^2 + lambda^2), u = 2^-53; rcp_nr's second step gives 2.1 at every lambda, the C oracle's
+// plain-double solve 0.5 - 1.5.  No bound on lambda or on cond enters: the test holds every lambda >= 0 it runs to 8 cond u.
 __device__ __forceinline__ double rcp_1nr(double x) {
     const double y = __builtin_amdgcn_rcp(x);
     return __builtin_fma(y, __builtin_fma(-x, y, 1.0), y);
