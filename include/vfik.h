@@ -107,7 +107,7 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
  *   A goal row or a repeller row whose FIRST element is NaN leaves that primitive as it is (the convention of io->q_ref);
  *   active [n_arms] (device, may be NULL): active[b] == 0 leaves the whole arm as it is.
  * The caller keeps radius >= 0 and radius + safe distance >= 0, as the fields it handed to vfik_set_fields did (the uniform repeller
- * image relies on it).  NOT moved: funnels, hemispheres and attractors beyond the first -- those go through vfik_set_fields.
+ * image relies on it).  NOT moved by this call: funnels, hemispheres and attractors beyond the first -- those move with vfik_move_scene.
  * Every image a later launch may read carries the new values (goal block, uniform, compact and general slot images): lean and
  * publishing launches, rollouts, launches with per-arm options, vfik_probe_field and io->goal_dist all see the moved scene.  Nothing a
  * launch decides at enqueue time changes: vfik_field_path, vfik_uniform_repellers, vfik_mixed_orders, vfik_slots_in_use and
@@ -117,6 +117,38 @@ int vfik_move_fields(vfik_handle* h, int first_arm, int n_arms, const void* goal
 /* The same with HOST arrays of doubles, rounded to the io dtype exactly as vfik_set_fields rounds vfik_field.p[]; copies, launches and
  * synchronises (a setter, like vfik_set_fields -- at a fraction of its cost: nothing is sorted or packed). */
 int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const double* goal16, const double* rep4, int n_rep);
+
+/* The whole scene of a moving object.  `set goalAndNormal` (object_feeder:248-303) re-sends the goal attractor, the approach FUNNEL and the
+ * near-goal repeller when the target's pose changes; `set ObstacleH` (object_feeder:335-354) re-sends a HEMISPHERE, a surface with its
+ * normal.  vfik_move_scene is vfik_move_fields -- the same ordering on the handle's stream, the same wait for vfik_submit_host tickets and
+ * no other, no allocation, the same NaN / active / ragged-row rules, and nothing a launch decides at enqueue time changes -- for all of:
+ *   goal16, rep4, n_rep, active   as vfik_move_fields.
+ *   fun6   [n_arms][n_fun][6] = x y z ax ay az: apex and axis of the arm's k-th funnel (VFIK_FIELD_FUNNEL) in ascending-id order.  Cut
+ *          angle, angle order, cut distance, distance order and force stay.
+ *   hem6   [n_arms][n_hem][6] = x y z nx ny nz: plane point and normal of the arm's k-th hemisphere (VFIK_FIELD_HEMISPHERE) in
+ *          ascending-id order.  Safe distance, order and force stay.
+ *   att16  [n_arms][n_att][16]  row-major 4x4: rows 0-2 replace the frame of the arm's k-th attractor AFTER the goal block (ascending
+ *          id).  The frame's last row, the slow-down distance and the force stay.
+ * Any array may be NULL: that class stays.  A row whose first element is NaN leaves its primitive as it is; rows at or beyond the arm's
+ * count of that class are ignored.  The general slot image carries every row; the straight-line path's aux block carries the arm's first
+ * funnel and first hemisphere, so row 0 of fun6 / hem6 is written there too.
+ * VFIK_E_ARG: bad arm range, all five arrays NULL, a count < 0 or > max_slots (or, host form, `active` given); VFIK_E_STATE: no
+ * vfik_set_fields call yet. */
+typedef struct vfik_scene_move {
+    const void* goal16;
+    const void* rep4;
+    const void* fun6;
+    const void* hem6;
+    const void* att16;
+    const int32_t* active;
+    int32_t n_rep, n_fun, n_hem, n_att;
+} vfik_scene_move;
+/* sizeof(vfik_scene_move) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_scene_move_size(void);
+int vfik_move_scene(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv);
+/* The same with HOST arrays of doubles (mv->active must be NULL), rounded to the io dtype exactly as vfik_set_fields rounds
+ * vfik_field.p[]; copies, launches and synchronises, like vfik_move_fields_host. */
+int vfik_move_scene_host(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv);
 
 /* Per-arm IK weights: what each arm's vf process keeps after a /weight message (vf:164-179,295-309): 't' + 6
  * task-space weights -> wy[n_arms][6], 'j' + n joint-space weights -> wq[n_arms][n]; either may be NULL

@@ -43,6 +43,12 @@ class Params(C.Structure):
                 ("jp_kp", C.c_double), ("jp_delta", C.c_double)]
 
 
+class SceneMove(C.Structure):
+    """``struct vfik_scene_move`` (include/vfik.h: vfik_move_scene)."""
+    _fields_ = [("goal16", C.c_void_p), ("rep4", C.c_void_p), ("fun6", C.c_void_p), ("hem6", C.c_void_p), ("att16", C.c_void_p),
+                ("active", C.c_void_p), ("n_rep", C.c_int32), ("n_fun", C.c_int32), ("n_hem", C.c_int32), ("n_att", C.c_int32)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

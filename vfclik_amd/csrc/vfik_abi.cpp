@@ -99,6 +99,7 @@ struct vfik_handle {
     void* d_orders = nullptr;      // order planes: 16 bytes per arm and plane, one byte per compact-image slot (vfik_kernel.h); read when `mixed`
     int mixed = 0;                 // the batch's decay repellers have integer orders that differ (between slots or between arms)
     unsigned short* d_repmap = nullptr;   // vfik_move_fields: general slot of the arm's k-th decay repeller, 8 entries (16 bytes) per arm and plane (vfik_kernel.h: MoveArgs)
+    unsigned short* d_scenemap = nullptr; // vfik_move_scene: the same for its k-th funnel, hemisphere and attractor behind the goal block, three maps in a row (vfik_kernel.h: SceneMoveArgs)
     bool fields_set = false;       // some vfik_set_fields call succeeded: there are images to move
     void* d_move_stage = nullptr;  // vfik_move_fields_host: the rounded rows on the device, grown on demand
     size_t move_stage_bytes = 0;
@@ -213,7 +214,7 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
                  std::vector<char>& goal, std::vector<char>& slots, std::vector<char>& fast, std::vector<int>& used,
                  std::vector<char>& funnel, std::vector<int>& used_fast, std::vector<char>& has_funnel,
                  std::vector<char>& uni, std::vector<char>& pair_state, std::vector<double>& pair_safe, std::vector<double>& pair_force,
-                 std::vector<unsigned char>& ord, std::vector<unsigned short>& rmap) {
+                 std::vector<unsigned char>& ord, std::vector<unsigned short>& rmap, std::vector<unsigned short>& smap) {
     funnel.assign((size_t)6 * n_arms * 4 * sizeof(T), 0);  // aux block: funnel planes 0..2, hemisphere planes 3..5
     goal.assign((size_t)4 * n_arms * 4 * sizeof(T), 0);
     slots.assign((size_t)std::max(1, 2 * S) * n_arms * 4 * sizeof(T), 0);
@@ -231,6 +232,11 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
     ord.assign((size_t)((std::max(1, S) + 15) / 16) * n_arms * 16, 5);
     // vfik_move_fields' map: entry (m % 8) of plane (m / 8) = the general slot of compact-image slot m, MOVE_NONE behind the arm's last repeller
     rmap.assign((size_t)((std::max(1, S) + 7) / 8) * n_arms * 8, vfik::MOVE_NONE);
+    // vfik_move_scene's maps, three of that layout in a row: entry k of class c (funnel, hemisphere, attractor behind the goal block) = the
+    // general slot of the arm's k-th primitive of that class, MOVE_NONE from the arm's count on
+    const size_t map_planes = (size_t)(std::max(1, S) + 7) / 8;
+    smap.assign(3 * map_planes * n_arms * 8, vfik::MOVE_NONE);
+    auto sm = [&](int cls, int j, int k) -> unsigned short& { return smap[((cls * map_planes + (size_t)(k >> 3)) * n_arms + j) * 8 + (k & 7)]; };
     std::vector<int> order;
     for (int j = 0; j < n_arms; ++j) {
         const vfik_field* f = fields + (size_t)j * max_fields;
@@ -240,6 +246,7 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
         bool have_goal = false, have_funnel = false, have_hemi = false;
         pair_state[j] = 0; pair_safe[j] = 0.0; pair_force[j] = 0.0;
         int m = 0, mr = 0;  // general slots used; compact-image slots used (repellers only, packed densely)
+        int n_fun = 0, n_hem = 0, n_att = 0;   // funnels, hemispheres, attractors behind the goal block seen so far
         auto gq = [&](int e) { return ((size_t)(e >> 2) * n_arms + j) * 4 + (e & 3); };
         for (int k : order) {
             const vfik_field& fd = f[k];
@@ -257,6 +264,9 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
             for (int e = 0; e < 6; ++e) put<T>(slots, at(0, e), fd.p[e]);
             put<T>(slots, at(0, 6), fd.force);
             put<T>(slots, at(0, 7), (double)fd.type);
+            if (fd.type == VFIK_FIELD_FUNNEL) sm(vfik::SCENE_FUN, j, n_fun++) = (unsigned short)m;
+            if (fd.type == VFIK_FIELD_HEMISPHERE) sm(vfik::SCENE_HEM, j, n_hem++) = (unsigned short)m;
+            if (fd.type == VFIK_FIELD_ATTRACTOR) sm(vfik::SCENE_ATT, j, n_att++) = (unsigned short)m;
             if (fd.type == VFIK_FIELD_FUNNEL && !have_funnel) {
                 // the straight-line path's funnel block (used only when this funnel is the arm's one non-repeller entry)
                 have_funnel = true;
@@ -506,6 +516,8 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
         const size_t sz_map = (std::max<size_t>(1, (size_t)max_slots) + 7) / 8 * (size_t)h->Bpad * 16;
         if (dev_alloc(h, (void**)&h->d_repmap, sz_map, false)) return bail("alloc repeller map");
         if (hipMemsetAsync(h->d_repmap, 0xFF, sz_map, h->stream) != hipSuccess) return bail("init repeller map");
+        if (dev_alloc(h, (void**)&h->d_scenemap, 3 * sz_map, false)) return bail("alloc scene maps");
+        if (hipMemsetAsync(h->d_scenemap, 0xFF, 3 * sz_map, h->stream) != hipSuccess) return bail("init scene maps");
     }
     {   // the uniform image starts out with every slot unused (radius -inf), like the zeros (force 0) of the other two images
         std::vector<char> plane((size_t)h->Bpad * 4 * h->esz, 0);
@@ -552,7 +564,7 @@ void vfik_destroy(vfik_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
-                    h->d_qalign, h->d_repmap, h->d_move_stage};
+                    h->d_qalign, h->d_repmap, h->d_scenemap, h->d_move_stage};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -773,10 +785,10 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
     std::vector<double> psafe(n_arms), pforce(n_arms);
     std::vector<int> used(n_arms), used_fast(n_arms);
     std::vector<unsigned char> ord;
-    std::vector<unsigned short> rmap;
+    std::vector<unsigned short> rmap, smap;
     const int S = h->max_slots;
-    if (h->io_dtype == 32) pack_fields<float>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap);
-    else pack_fields<double>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap);
+    if (h->io_dtype == 32) pack_fields<float>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap, smap);
+    else pack_fields<double>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap, smap);
     const size_t qb = 4 * h->esz, w = (size_t)n_arms * qb, pitch = (size_t)h->Bpad * qb;
     char* dg = static_cast<char*>(h->d_goal) + (size_t)first_arm * qb;
     HIP_TRY(hipMemcpy2DAsync(dg, pitch, goal.data(), w, w, 3, hipMemcpyHostToDevice, h->stream));
@@ -794,6 +806,8 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
         HIP_TRY(hipMemcpy2DAsync(dor, (size_t)h->Bpad * 16, ord.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 15) / 16, hipMemcpyHostToDevice, h->stream));
         char* dm = reinterpret_cast<char*>(h->d_repmap) + (size_t)first_arm * 16;
         HIP_TRY(hipMemcpy2DAsync(dm, (size_t)h->Bpad * 16, rmap.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 7) / 8, hipMemcpyHostToDevice, h->stream));
+        char* dsm = reinterpret_cast<char*>(h->d_scenemap) + (size_t)first_arm * 16;   // (the three maps' planes follow each other on both sides)
+        HIP_TRY(hipMemcpy2DAsync(dsm, (size_t)h->Bpad * 16, smap.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, 3 * ((size_t)(S + 7) / 8), hipMemcpyHostToDevice, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->fields_set = true;
@@ -878,6 +892,16 @@ static int move_launch(vfik_handle* h, int first_arm, int n_arms, const void* go
     return VFIK_OK;
 }
 
+// the host forms' staging buffer, grown on demand
+static int move_stage_reserve(vfik_handle* h, size_t bytes) {
+    if (bytes <= h->move_stage_bytes) return VFIK_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->d_move_stage) { (void)hipFree(h->d_move_stage); h->dev_bytes -= h->move_stage_bytes; h->d_move_stage = nullptr; h->move_stage_bytes = 0; }
+    if (dev_alloc(h, &h->d_move_stage, bytes, false)) return VFIK_E_HIP;
+    h->move_stage_bytes = bytes;
+    return VFIK_OK;
+}
+
 int vfik_move_fields(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
@@ -901,15 +925,103 @@ int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const doubl
         const double v = k < ng ? goal16[k] : rep4[k - ng];
         if (h->io_dtype == 32) put<float>(buf, k, v); else put<double>(buf, k, v);
     }
-    if (buf.size() > h->move_stage_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_move_stage) { (void)hipFree(h->d_move_stage); h->dev_bytes -= h->move_stage_bytes; h->d_move_stage = nullptr; h->move_stage_bytes = 0; }
-        if (dev_alloc(h, &h->d_move_stage, buf.size(), false)) return VFIK_E_HIP;
-        h->move_stage_bytes = buf.size();
-    }
+    if (move_stage_reserve(h, buf.size()) != VFIK_OK) return VFIK_E_HIP;
     HIP_TRY(hipMemcpyAsync(h->d_move_stage, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
     char* d = static_cast<char*>(h->d_move_stage);
     const int rl = move_launch(h, first_arm, n_arms, goal16 ? d : nullptr, rep4 ? d + ng * h->esz : nullptr, n_rep, nullptr);
+    if (rl != VFIK_OK) return rl;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // `buf` and the stage are reused
+    return VFIK_OK;
+}
+
+size_t vfik_scene_move_size(void) { return sizeof(vfik_scene_move); }
+
+// the checks the two forms of vfik_move_scene share
+static int scene_check(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv) {
+    if (!mv) return fail(VFIK_E_ARG, "vfik_move_scene: null vfik_scene_move");
+    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (!mv->goal16 && !mv->rep4 && !mv->fun6 && !mv->hem6 && !mv->att16) return fail(VFIK_E_ARG, "vfik_move_scene: give at least one of goal16, rep4, fun6, hem6, att16");
+    const struct { const char* name; int v; } counts[] = {{"n_rep", mv->n_rep}, {"n_fun", mv->n_fun}, {"n_hem", mv->n_hem}, {"n_att", mv->n_att}};
+    for (const auto& c : counts)
+        if (c.v < 0 || c.v > h->max_slots) return fail(VFIK_E_ARG, "%s %d outside [0, %d]", c.name, c.v, h->max_slots);
+    if (!h->fields_set) return fail(VFIK_E_STATE, "vfik_move_scene before any vfik_set_fields: there is nothing to move");
+    return VFIK_OK;
+}
+
+// (an array with no rows is no array; a move of goal and repellers alone is vfik_move_fields' launch)
+static int scene_launch(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move& mv) {
+    const void* rep4 = mv.n_rep > 0 ? mv.rep4 : nullptr;
+    vfik::SceneMoveArgs s{};
+    s.fun6 = mv.n_fun > 0 ? mv.fun6 : nullptr;
+    s.hem6 = mv.n_hem > 0 ? mv.hem6 : nullptr;
+    s.att16 = mv.n_att > 0 ? mv.att16 : nullptr;
+    if (!s.fun6 && !s.hem6 && !s.att16) return move_launch(h, first_arm, n_arms, mv.goal16, rep4, rep4 ? mv.n_rep : 0, mv.active);
+    s.m.goal = h->d_goal;
+    s.m.slots = h->d_slots;
+    s.m.slots_fast = h->d_slots_fast;
+    s.m.slots_uni = h->d_slots_uni;
+    s.m.repmap = h->d_repmap;
+    s.m.goal16 = mv.goal16;
+    s.m.rep4 = rep4;
+    s.m.active = mv.active;
+    s.m.first_arm = first_arm;
+    s.m.n_arms = n_arms;
+    s.m.n_rep = rep4 ? mv.n_rep : 0;
+    s.m.S = h->max_slots;
+    s.m.Bpad = h->Bpad;
+    s.aux = h->d_funnel;
+    s.scenemap = h->d_scenemap;
+    s.n_fun = s.fun6 ? mv.n_fun : 0;
+    s.n_hem = s.hem6 ? mv.n_hem : 0;
+    s.n_att = s.att16 ? mv.n_att : 0;
+    s.map_planes = (std::max(1, h->max_slots) + 7) / 8;
+    hipError_t e = vfik::launch_move_scene(h->io_dtype, s, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "scene move launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+int vfik_move_scene(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = scene_check(h, first_arm, n_arms, mv);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return scene_launch(h, first_arm, n_arms, *mv);
+}
+
+int vfik_move_scene_host(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = scene_check(h, first_arm, n_arms, mv);
+    if (rc != VFIK_OK) return rc;
+    if (mv->active) return fail(VFIK_E_ARG, "vfik_move_scene_host takes no active mask: give NaN rows");
+    HIP_TRY(hipSetDevice(h->device));
+    // the rows of 4 and 16 first: every part of the stage then starts as aligned as its loads want (rows of six: pairs)
+    const double* src[5] = {static_cast<const double*>(mv->goal16), static_cast<const double*>(mv->rep4), static_cast<const double*>(mv->att16),
+                            static_cast<const double*>(mv->fun6), static_cast<const double*>(mv->hem6)};
+    const size_t per_arm[5] = {16, (size_t)mv->n_rep * 4, (size_t)mv->n_att * 16, (size_t)mv->n_fun * 6, (size_t)mv->n_hem * 6};
+    size_t off[6] = {0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 5; ++c) {
+        if (per_arm[c] == 0) src[c] = nullptr;
+        off[c + 1] = off[c] + (src[c] ? (size_t)n_arms * per_arm[c] : 0);
+    }
+    if (off[5] == 0) return VFIK_OK;
+    std::vector<char> buf(off[5] * h->esz);   // rounded as vfik_set_fields rounds p[] (NaN stays NaN)
+    for (int c = 0; c < 5; ++c)
+        for (size_t k = off[c]; k < off[c + 1]; ++k) {
+            const double v = src[c][k - off[c]];
+            if (h->io_dtype == 32) put<float>(buf, k, v); else put<double>(buf, k, v);
+        }
+    if (move_stage_reserve(h, buf.size()) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipMemcpyAsync(h->d_move_stage, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
+    char* d = static_cast<char*>(h->d_move_stage);
+    vfik_scene_move dv = *mv;
+    dv.goal16 = src[0] ? d + off[0] * h->esz : nullptr;
+    dv.rep4 = src[1] ? d + off[1] * h->esz : nullptr;
+    dv.att16 = src[2] ? d + off[2] * h->esz : nullptr;
+    dv.fun6 = src[3] ? d + off[3] * h->esz : nullptr;
+    dv.hem6 = src[4] ? d + off[4] * h->esz : nullptr;
+    const int rl = scene_launch(h, first_arm, n_arms, dv);
     if (rl != VFIK_OK) return rl;
     HIP_TRY(hipStreamSynchronize(h->stream));   // `buf` and the stage are reused
     return VFIK_OK;

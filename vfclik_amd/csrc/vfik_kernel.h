@@ -506,6 +506,24 @@ struct MoveArgs {
     long Bpad;
 };
 hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream);
+// vfik_move_scene: the same, and new coordinates for funnels, hemispheres and the attractors behind the goal block.  scenemap: THREE maps
+// of repmap's layout one after the other -- class c (SCENE_FUN, SCENE_HEM, SCENE_ATT) owns planes [c * map_planes, (c + 1) * map_planes),
+// map_planes = (max(1, S) + 7) / 8 of 16 bytes (8 entries) per arm -- so entry k of class c of arm b is
+//   scenemap[((c * map_planes + (k >> 3)) * Bpad + b) * 8 + (k & 7)]
+// = the GENERAL slot of the arm's k-th funnel / hemisphere / attractor after the goal block in ascending-id order (the first of a funnel's or a
+// hemisphere's two slots, of an attractor's three), MOVE_NONE from the arm's count of that class on.  aux: the 6 quad planes behind the goal
+// block (funnel 0..2, hemisphere 3..5), which hold the arm's FIRST funnel and FIRST hemisphere: row k = 0 goes there too.
+enum { SCENE_FUN = 0, SCENE_HEM = 1, SCENE_ATT = 2 };
+struct SceneMoveArgs {
+    MoveArgs m;
+    void* aux;                  // 6 quad planes
+    const unsigned short* scenemap;
+    const void* fun6;           // [n_arms][n_fun][6] or NULL
+    const void* hem6;           // [n_arms][n_hem][6] or NULL
+    const void* att16;          // [n_arms][n_att][16] or NULL
+    int n_fun, n_hem, n_att, map_planes;
+};
+hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

@@ -14,7 +14,7 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel.
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -2607,28 +2607,24 @@ __device__ __forceinline__ MoveQuad<T> move_load(const T* src) {
     return r;
 }
 
+// the goal frame of one arm: rows 0..2 into the goal block's first three planes
 template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
-    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
-    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
-    const long j = arm - m.first_arm;
-    if (m.active && !m.active[j]) return;
+__device__ __forceinline__ void move_goal_row(const MoveArgs& m, int arm, long j) {
     const long Qp = m.Bpad;  // quads per plane
-    int k = (int)blockIdx.y;
-    if (m.goal16) {
-        if (k == 0) {
-            MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(m.goal) + arm;
-            if (g[3 * Qp].v[0] == (T)0) return;   // no goal block: the row is ignored
-            const T* src = static_cast<const T*>(m.goal16) + j * 16;
-            const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
-            if (r0.v[0] != r0.v[0]) return;       // NaN: this goal stays
-            g[0] = r0;
-            g[Qp] = r1;
-            g[2 * Qp] = r2;
-            return;
-        }
-        --k;
-    }
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(m.goal) + arm;
+    if (g[3 * Qp].v[0] == (T)0) return;   // no goal block: the row is ignored
+    const T* src = static_cast<const T*>(m.goal16) + j * 16;
+    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
+    if (r0.v[0] != r0.v[0]) return;       // NaN: this goal stays
+    g[0] = r0;
+    g[Qp] = r1;
+    g[2 * Qp] = r2;
+}
+
+// decay repeller k of one arm: x y z radius into the uniform, the compact and the general image
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_rep_row(const MoveArgs& m, int arm, long j, int k) {
+    const long Qp = m.Bpad;
     if (k >= m.n_rep || k >= m.S) return;
     const unsigned gs = m.repmap[((long)(k >> 3) * m.Bpad + arm) * 8 + (k & 7)];
     if (gs >= (unsigned)m.S) return;              // MOVE_NONE: the arm has no k-th decay repeller
@@ -2645,6 +2641,131 @@ __global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
         reinterpret_cast<MovePair<T>*>(f + Qp)[1] = lo;
         reinterpret_cast<MovePair<T>*>(f + 2 * Qp)[0] = hi;
     }
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
+    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
+    const long j = arm - m.first_arm;
+    if (m.active && !m.active[j]) return;
+    int k = (int)blockIdx.y;
+    if (m.goal16) {
+        if (k == 0) {
+            move_goal_row<T, VEC>(m, arm, j);
+            return;
+        }
+        --k;
+    }
+    move_rep_row<T, VEC>(m, arm, j, k);
+}
+
+// ------------------------------------------------------------------------------------------------
+// vfik_move_scene: the rest of what the object feeder re-sends for an object that moves -- the approach funnel of `set goalAndNormal`
+// (object_feeder:248-303), the surface of `set ObstacleH` (object_feeder:335-354) -- and attractors behind the goal block.  The same
+// thread mapping as move_kernel; blockIdx.y runs over the goal frame, the caller's repeller rows, then its funnel, hemisphere and attractor
+// rows (the class of a block is uniform: scalar branches).  Goal and repellers: move_kernel's stores.  The new classes live in the general
+// image (and the aux block), whose slots keep p0..p5 | force type in two planes:
+//   funnel / hemisphere k, general slot gs   plane 2 gs <- the quad x y z ax; plane 2 gs + 1 <- its FIRST pair ay az (force, type stay);
+//                                            k = 0 also aux planes 0, 1 (funnel) or 3, 4 (hemisphere), laid out alike (cutAngle
+//                                            angleOrder / safe order in the second pair stay);
+//   attractor k, general slot gs             planes 2 gs, 2 gs + 1 (pair), 2 gs + 2, 2 gs + 3 (pair) <- p0..p11; slot gs + 2 (frame row 3,
+//                                            slow-down distance) stays.
+// A wave's pair stores cover the first 8 of every 16 bytes of one contiguous 1-KiB row (2 KiB at float64 I/O): every 128-byte line of the row
+// is touched by ONE instruction -- byte-masked in L2, no line split between instructions -- as move_kernel's odd compact-image slots already are.
+// Rows of six are 8-byte aligned at float32: pair loads (VEC: the caller's 6-rows are pair aligned, its 4- and 16-rows quad aligned).
+// ------------------------------------------------------------------------------------------------
+template <typename T, bool VEC>
+__device__ __forceinline__ MovePair<T> move_load_pair(const T* src) {
+    if (VEC) return *reinterpret_cast<const MovePair<T>*>(src);
+    MovePair<T> r;
+    r.v[0] = src[0]; r.v[1] = src[1];
+    return r;
+}
+
+__device__ __forceinline__ unsigned scene_slot(const SceneMoveArgs& s, int cls, int arm, int k) {
+    return s.scenemap[((long)(cls * s.map_planes + (k >> 3)) * s.m.Bpad + arm) * 8 + (k & 7)];
+}
+
+// funnel / hemisphere k of one arm: six scalars into the slot's first quad and the first pair of its second
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_six_row(const SceneMoveArgs& s, int arm, int cls, const T* src, int k, int aux_plane) {
+    const long Qp = s.m.Bpad;
+    if (k >= s.m.S) return;
+    const unsigned gs = scene_slot(s, cls, arm, k);
+    if (gs + 1 >= (unsigned)s.m.S) return;        // MOVE_NONE: the arm has no k-th primitive of this class (a real one owns slots gs, gs + 1)
+    const MovePair<T> a = move_load_pair<T, VEC>(src), b = move_load_pair<T, VEC>(src + 2), c = move_load_pair<T, VEC>(src + 4);
+    if (a.v[0] != a.v[0]) return;                 // NaN: this primitive stays
+    MoveQuad<T> q;
+    q.v[0] = a.v[0]; q.v[1] = a.v[1]; q.v[2] = b.v[0]; q.v[3] = b.v[1];
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
+    g[0] = q;
+    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = c;
+    if (k == 0) {   // the arm's first funnel / hemisphere: the straight-line path reads it from the aux block
+        MoveQuad<T>* const x = static_cast<MoveQuad<T>*>(s.aux) + (long)aux_plane * Qp + arm;
+        x[0] = q;
+        reinterpret_cast<MovePair<T>*>(x + Qp)[0] = c;
+    }
+}
+
+// attractor k behind the goal block: rows 0..2 of its frame, p0..p11 of the general image's three slots
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_att_row(const SceneMoveArgs& s, int arm, const T* src, int k) {
+    const long Qp = s.m.Bpad;
+    if (k >= s.m.S) return;
+    const unsigned gs = scene_slot(s, SCENE_ATT, arm, k);
+    if (gs + 2 >= (unsigned)s.m.S) return;        // MOVE_NONE (a real one owns slots gs .. gs + 2)
+    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
+    if (r0.v[0] != r0.v[0]) return;               // NaN: this attractor stays
+    MoveQuad<T> q;
+    MovePair<T> p45, p1011;
+    p45.v[0] = r1.v[0]; p45.v[1] = r1.v[1];
+    q.v[0] = r1.v[2]; q.v[1] = r1.v[3]; q.v[2] = r2.v[0]; q.v[3] = r2.v[1];
+    p1011.v[0] = r2.v[2]; p1011.v[1] = r2.v[3];
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
+    g[0] = r0;
+    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = p45;
+    g[2 * Qp] = q;
+    reinterpret_cast<MovePair<T>*>(g + 3 * Qp)[0] = p1011;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) move_scene_kernel(const SceneMoveArgs s) {
+    const MoveArgs& m = s.m;
+    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
+    const long j = arm - m.first_arm;
+    if (m.active && !m.active[j]) return;
+    int k = (int)blockIdx.y;
+    if (m.goal16) {
+        if (k == 0) {
+            move_goal_row<T, VEC>(m, arm, j);
+            return;
+        }
+        --k;
+    }
+    if (m.rep4) {
+        if (k < m.n_rep) {
+            move_rep_row<T, VEC>(m, arm, j, k);
+            return;
+        }
+        k -= m.n_rep;
+    }
+    if (s.fun6) {
+        if (k < s.n_fun) {
+            move_six_row<T, VEC>(s, arm, SCENE_FUN, static_cast<const T*>(s.fun6) + (j * s.n_fun + k) * 6, k, 0);
+            return;
+        }
+        k -= s.n_fun;
+    }
+    if (s.hem6) {
+        if (k < s.n_hem) {
+            move_six_row<T, VEC>(s, arm, SCENE_HEM, static_cast<const T*>(s.hem6) + (j * s.n_hem + k) * 6, k, 3);
+            return;
+        }
+        k -= s.n_hem;
+    }
+    if (s.att16 && k < s.n_att) move_att_row<T, VEC>(s, arm, static_cast<const T*>(s.att16) + (j * s.n_att + k) * 16, k);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3521,6 +3642,24 @@ hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream) {
     } else {
         if (vec) hipLaunchKernelGGL((move_kernel<double, true>), grid, blk, 0, stream, m);
         else hipLaunchKernelGGL((move_kernel<double, false>), grid, blk, 0, stream, m);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream) {
+    const MoveArgs& m = s.m;
+    const int lanes = (m.first_arm & 63) + m.n_arms;
+    const int rows = (m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0) + (s.fun6 ? s.n_fun : 0) + (s.hem6 ? s.n_hem : 0) + (s.att16 ? s.n_att : 0);
+    if (rows < 1) return hipSuccess;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)rows), blk(256);
+    const size_t pair = io_dtype == 32 ? 8 : 16;
+    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4 | (uintptr_t)s.att16) & 15u) == 0 && (((uintptr_t)s.fun6 | (uintptr_t)s.hem6) & (pair - 1)) == 0;
+    if (io_dtype == 32) {
+        if (vec) hipLaunchKernelGGL((move_scene_kernel<float, true>), grid, blk, 0, stream, s);
+        else hipLaunchKernelGGL((move_scene_kernel<float, false>), grid, blk, 0, stream, s);
+    } else {
+        if (vec) hipLaunchKernelGGL((move_scene_kernel<double, true>), grid, blk, 0, stream, s);
+        else hipLaunchKernelGGL((move_scene_kernel<double, false>), grid, blk, 0, stream, s);
     }
     return hipGetLastError();
 }

@@ -64,6 +64,9 @@ def load_library(path=None):
         "vfik_set_fields": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_move_fields": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_move_fields_host": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+        "vfik_scene_move_size": (C.c_size_t, []),
+        "vfik_move_scene": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(_abi.SceneMove)]),
+        "vfik_move_scene_host": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(_abi.SceneMove)]),
         "vfik_set_mixer_weights": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
         "vfik_set_ext_cmd": (C.c_int, [H, C.c_int, C.c_void_p]),
         "vfik_reset_state": (C.c_int, [H]),
@@ -111,6 +114,9 @@ def load_library(path=None):
     mine = [C.sizeof(_abi.Field), C.sizeof(_abi.Chain), C.sizeof(_abi.Params), C.sizeof(IO)]
     if list(sizes) != mine:
         raise VfikError("struct layout mismatch: library %s, Python mirrors %s" % (list(sizes), mine))
+    if lib.vfik_scene_move_size() != C.sizeof(_abi.SceneMove):
+        raise VfikError("struct layout mismatch: vfik_scene_move is %d bytes in the library, %d in the Python mirror"
+                        % (lib.vfik_scene_move_size(), C.sizeof(_abi.SceneMove)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
         _lib = lib
     return lib
@@ -260,6 +266,76 @@ class Engine:
             raise ValueError("give goal, repellers or both")
         self._chk(self.lib.vfik_move_fields_host(self.h, int(first_arm), n_arms, None if g is None else g.ctypes.data,
                                                  None if r is None else r.ctypes.data, n_rep))
+
+    # (name, vfik_scene_move member, its count member, elements per row; None: one row per arm)
+    _SCENE_ROWS = (("goal", "goal16", None, 16), ("repellers", "rep4", "n_rep", 4), ("funnels", "fun6", "n_fun", 6),
+                   ("hemispheres", "hem6", "n_hem", 6), ("attractors", "att16", "n_att", 16))
+
+    def move_scene(self, goal=None, repellers=None, funnels=None, hemispheres=None, attractors=None, active=None, first_arm=0, n_arms=None,
+                   n_rep=None, n_fun=None, n_hem=None, n_att=None):
+        """The whole scene of a moving object, on the device (include/vfik.h: vfik_move_scene): ``move_fields`` and, with the same
+        rules, ``funnels`` (n_arms, n_fun, 6) = x y z ax ay az of each arm's k-th funnel, ``hemispheres`` (n_arms, n_hem, 6) =
+        x y z nx ny nz of its k-th hemisphere, ``attractors`` (n_arms, n_att, 16) or (n_arms, n_att, 4, 4) = the frame of its k-th
+        attractor behind the goal, all in ascending-id order.  Asynchronous on the engine's stream.  Torch tensors on this device
+        (contiguous, the engine's dtype, shapes checked), or raw device addresses together with ``n_arms`` and the class's count."""
+        given = {"goal": goal, "repellers": repellers, "funnels": funnels, "hemispheres": hemispheres, "attractors": attractors}
+        counts = {"n_rep": n_rep, "n_fun": n_fun, "n_hem": n_hem, "n_att": n_att}
+        mv = _abi.SceneMove()
+        for name, member, cnt, tail in self._SCENE_ROWS + (("active", "active", None, 1),):
+            x = active if name == "active" else given[name]
+            if x is None:
+                continue
+            if not isinstance(x, int):
+                if not x.is_contiguous():
+                    raise ValueError("%s must be contiguous" % name)
+                want = "int32" if name == "active" else self.io_dtype.name
+                if str(x.dtype).split(".")[-1] != want:
+                    raise ValueError("%s must be %s, got %s" % (name, want, x.dtype))
+                rows = x.shape[0]
+                if n_arms is None:
+                    n_arms = rows
+                if rows != n_arms or (cnt is None and x.numel() != rows * tail) or \
+                        (cnt is not None and (x.dim() < 3 or x.numel() != rows * x.shape[1] * tail)):
+                    raise ValueError("%s: shape %s does not fit %s arms" % (name, tuple(x.shape), n_arms))
+                if cnt is not None:
+                    if counts[cnt] is not None and counts[cnt] != x.shape[1]:
+                        raise ValueError("%s: %d rows per arm, %s says %d" % (name, x.shape[1], cnt, counts[cnt]))
+                    counts[cnt] = x.shape[1]
+            elif cnt is not None and counts[cnt] is None:
+                raise ValueError("a raw %s address needs %s" % (name, cnt))
+            setattr(mv, member, _ptr(x))
+        if n_arms is None:
+            raise ValueError("raw addresses need n_arms")
+        for cnt, v in counts.items():
+            setattr(mv, cnt, int(v or 0))
+        self._chk(self.lib.vfik_move_scene(self.h, int(first_arm), int(n_arms), C.byref(mv)))
+
+    def move_scene_host(self, goal=None, repellers=None, funnels=None, hemispheres=None, attractors=None, first_arm=0):
+        """The host form (vfik_move_scene_host): NumPy arrays of doubles, rounded to the engine's dtype exactly as ``set_fields``
+        rounds the parameters.  Synchronous."""
+        given = {"goal": goal, "repellers": repellers, "funnels": funnels, "hemispheres": hemispheres, "attractors": attractors}
+        mv = _abi.SceneMove()
+        keep, n_arms = [], None
+        for name, member, cnt, tail in self._SCENE_ROWS:
+            if given[name] is None:
+                continue
+            a = np.ascontiguousarray(given[name], dtype=np.float64)
+            if cnt is None:
+                ok = a.ndim >= 2 and a.size == a.shape[0] * tail
+            else:
+                ok = a.ndim >= 3 and a.size == a.shape[0] * a.shape[1] * tail
+            if not ok:
+                raise ValueError("%s must be (n_arms, %s%d), got %s" % (name, "" if cnt is None else "rows, ", tail, a.shape))
+            if n_arms is not None and a.shape[0] != n_arms:
+                raise ValueError("every array of a scene move must cover the same arms")
+            n_arms = a.shape[0]
+            keep.append(a)
+            setattr(mv, member, a.ctypes.data)
+            if cnt is not None:
+                setattr(mv, cnt, a.shape[1])
+        if n_arms is None:
+            raise ValueError("give at least one of goal, repellers, funnels, hemispheres, attractors")
+        self._chk(self.lib.vfik_move_scene_host(self.h, int(first_arm), n_arms, C.byref(mv)))
 
     def set_objects(self, frames, first_arm=0):
         """Object frames of the distance monitor (monitor_distance:72,111-129): (n_arms, n_objects, 16) doubles, kept on the

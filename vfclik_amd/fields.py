@@ -5,7 +5,8 @@ Each reference ``vf`` process keeps ``vectorFields = {id: [force, type, params]}
 field (vf:276-293).  Here one :class:`FieldSets` keeps those dictionaries for B arms, applies the same
 acceptance rules to each bottle, and hands the arms whose set changed to ``Engine.set_fields`` -- the
 batched equivalent of the rebuild -- or, when only a goal frame or obstacle coordinates moved, to
-``Engine.move_fields_host``, which rewrites those numbers on the device without repacking.  Malformed bottles are reported and ignored, never raised, like the
+``Engine.move_fields_host`` (with a funnel, a hemisphere or a further attractor among them: ``Engine.move_scene_host``), which
+rewrites those numbers on the device without repacking.  Malformed bottles are reported and ignored, never raised, like the
 reference (vf:264-266,275).
 """
 import logging
@@ -104,16 +105,20 @@ class FieldSets:
         ids = [i for i in sorted(fields) if fields[i][1] == _abi.FIELD_ATTRACTOR]
         return ids[0] if ids else None
 
-    def _move_of(self, arm):
+    def _move_of(self, arm, scene=False):
         """How the arm's set differs from what was flushed last: None when the structure changed (ids, types, forces, or a
-        parameter a move does not carry -- the arm needs set_fields), else (goal12 or None, {k: [x, y, z, radius]}) with the
-        new goal frame rows 0-2 and the new coordinates of the k-th decay repeller in ascending-id order; both empty when
-        nothing changed at all."""
+        parameter a move does not carry -- the arm needs set_fields), else (goal12 or None, {k: [x, y, z, radius]}, scene rows) with
+        the new goal frame rows 0-2 and the new coordinates of the k-th decay repeller in ascending-id order; all empty when
+        nothing changed at all.  scene (an engine with ``move_scene_host``): new coordinates of a funnel, a hemisphere or an
+        attractor behind the goal are a move too -- scene rows = ({k: p[:6]} funnels, {k: p[:6]} hemispheres, {k: p[:12]}
+        attractors), k counting that class in ascending-id order; without it they are structure and the three stay empty."""
         old, new = self._flushed[arm], self.sets[arm]
         if old is None or sorted(old) != sorted(new):
             return None
         goal_id = self._goal_id(new)
         goal, reps, k = None, {}, 0
+        rows = {_abi.FIELD_FUNNEL: {}, _abi.FIELD_HEMISPHERE: {}, _abi.FIELD_ATTRACTOR: {}}
+        seen = {_abi.FIELD_FUNNEL: 0, _abi.FIELD_HEMISPHERE: 0, _abi.FIELD_ATTRACTOR: 0}
         for vf_id in sorted(new):
             (f0, t0, p0), (f1, t1, p1) = old[vf_id], new[vf_id]
             if t0 != t1 or f0 != f1:
@@ -129,9 +134,16 @@ class FieldSets:
                 if p0[:4] != p1[:4]:
                     reps[k] = p1[:4]
                 k += 1
-            elif p0 != p1:                  # funnels, hemispheres, further attractors are not moved
+            elif scene and t1 in rows:
+                head = 12 if t1 == _abi.FIELD_ATTRACTOR else 6
+                if p0[head:] != p1[head:]:  # cut angle, orders, distances; the frame's last row and the slow-down distance stay
+                    return None
+                if p0[:head] != p1[:head]:
+                    rows[t1][seen[t1]] = p1[:head]
+                seen[t1] += 1
+            elif p0 != p1:                  # funnels, hemispheres, further attractors: moved by move_scene_host only
                 return None
-        return goal, reps
+        return goal, reps, (rows[_abi.FIELD_FUNNEL], rows[_abi.FIELD_HEMISPHERE], rows[_abi.FIELD_ATTRACTOR])
 
     def forget(self):
         """Forget what was flushed: the next flush sends every changed arm through set_fields (for a caller that wrote
@@ -154,7 +166,10 @@ class FieldSets:
         the structure flushed last intact -- a goal frame and / or x y z radius of decay repellers re-sent with new numbers, what
         the object feeder does for an object that moves (object_feeder:214-354) -- go through ``engine.move_fields_host`` (rows
         that did not change are NaN: they stay); every other arm, and every arm of an engine without that method, goes through
-        ``engine.set_fields``.  The device holds the same field sets either way."""
+        ``engine.set_fields``.  An engine that also has ``move_scene_host`` gets the arms whose funnel (the approach direction of
+        `set goalAndNormal`, object_feeder:248-303), hemisphere (`set ObstacleH`, object_feeder:335-354) or further attractor came
+        with new coordinates through that method, their goal and repeller rows in the same call.  The device holds the same field
+        sets either way."""
         if not self.dirty:
             return 0
         arms = sorted(self.dirty)
@@ -162,11 +177,14 @@ class FieldSets:
         if self._flushed_to is None or self._flushed_to() is not engine:
             self.forget()
         can_move = hasattr(engine, "move_fields_host")
-        moves, full = {}, []
+        can_scene = can_move and hasattr(engine, "move_scene_host")
+        moves, scenes, full = {}, {}, []
         for a in arms:
-            mv = self._move_of(a) if can_move else None
+            mv = self._move_of(a, scene=can_scene) if can_move else None
             if mv is None:
                 full.append(a)
+            elif any(mv[2]):
+                scenes[a] = mv
             elif mv[0] is not None or mv[1]:
                 moves[a] = mv
         for lo, hi in (self._runs(full) if full else ()):
@@ -181,13 +199,38 @@ class FieldSets:
             if n_rep:
                 rep = np.full((n, n_rep, 4), np.nan)
             for a in range(lo, hi + 1):
-                g, reps = moves[a]
+                g, reps, _ = moves[a]
                 if g is not None:
                     goal[a - lo, :12] = g
                     goal[a - lo, 12:] = (0.0, 0.0, 0.0, 1.0)
                 for k, xyzr in reps.items():
                     rep[a - lo, k] = xyzr
             engine.move_fields_host(goal=goal, repellers=rep, first_arm=lo)
+        for lo, hi in (self._runs(sorted(scenes)) if scenes else ()):
+            n = hi - lo + 1
+            run = [scenes[a] for a in range(lo, hi + 1)]
+            kw = {}
+            if any(mv[0] is not None for mv in run):
+                kw["goal"] = np.full((n, 16), np.nan)
+            for name, width, pick in (("repellers", 4, lambda mv: mv[1]), ("funnels", 6, lambda mv: mv[2][0]),
+                                      ("hemispheres", 6, lambda mv: mv[2][1]), ("attractors", 16, lambda mv: mv[2][2])):
+                rows = max(max(pick(mv), default=-1) for mv in run) + 1
+                if rows:
+                    kw[name] = np.full((n, rows, width), np.nan)
+            for j, mv in enumerate(run):
+                if mv[0] is not None:
+                    kw["goal"][j, :12] = mv[0]
+                    kw["goal"][j, 12:] = (0.0, 0.0, 0.0, 1.0)
+                for k, xyzr in mv[1].items():
+                    kw["repellers"][j, k] = xyzr
+                for k, p6 in mv[2][0].items():
+                    kw["funnels"][j, k] = p6
+                for k, p6 in mv[2][1].items():
+                    kw["hemispheres"][j, k] = p6
+                for k, p12 in mv[2][2].items():
+                    kw["attractors"][j, k, :12] = p12
+                    kw["attractors"][j, k, 12:] = (0.0, 0.0, 0.0, 1.0)
+            engine.move_scene_host(first_arm=lo, **kw)
         try:
             self._flushed_to = weakref.ref(engine)
         except TypeError:

@@ -126,6 +126,13 @@ class ShardedEngine:
         for (a, b, e), g, r in zip(self.parts, self._rows(goal, "goal", global_rows), self._rows(repellers, "repellers", global_rows)):
             e.move_fields_host(goal=g, repellers=r)
 
+    def move_scene_host(self, goal=None, repellers=None, funnels=None, hemispheres=None, attractors=None, global_rows=True):
+        """Engine.move_scene_host over the shard, every array split as :meth:`set_fields` splits its arrays."""
+        given = (("goal", goal), ("repellers", repellers), ("funnels", funnels), ("hemispheres", hemispheres), ("attractors", attractors))
+        split = {name: self._rows(arr, name, global_rows) for name, arr in given}
+        for k, (a, b, e) in enumerate(self.parts):
+            e.move_scene_host(**{name: rows[k] for name, rows in split.items()})
+
     # the columns of every output row (Engine._OUT_SHAPES): what a rank without a single arm still has to return
     _COLS = {"qdot_vf": "n", "qdot_null": "n", "qdot_out": "n", "pose": 16, "pose_nt": 16, "v6": 6, "qdist": "n", "goal_dist": 2,
              "q_ref_out": "n", "track_error": 8}
