@@ -276,6 +276,51 @@ int vfik_wait(vfik_handle* h, long ticket);
 int vfik_rollout(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp_to_limits, void* q_out);
 int vfik_rollout_host(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp_to_limits, void* q_out);
 
+/* Batched goto.  Every user-level motion call of the reference is "send a goal, then wait until the arm is there" (handlers.py:346-440:
+ * gotoFrame(frame, wait, goal_precision) -> (result, [pos_dist, orient_dist]); gotThere, gotoPosBlocking; set_ref_js(..., wait,
+ * goal_precision), handlers.py:544-576): the handler reads the object-0 entry of /dmonitor/distOut -- io->goal_dist -- until
+ * pos_dist < goal_precision[0] and orient_dist * pi / 180 < goal_precision[1] (handlers.py:374-381) or the time is up.  vfik_goto is that wait
+ * for the batch, on the device: n_cycles / stride BLOCKS of `stride` control cycles each -- a vfik_rollout of `stride` cycles, with the kernels
+ * and the integration of vfik_rollout -- and after every block one small kernel that checks each arm's goal_dist row against the precision
+ * (both compares strict, in double; NaN never arrives), notes the cycle of the first success in arrived[], counts the arms still under
+ * way in pending[k] and sets the gate of the next block.  The whole sequence is enqueued on the handle's stream with no host round trip.
+ *   arrived[b]   = (k + 1) * stride - 1 for the first check k the arm passed: the 0-based index of the cycle whose tool pose was measured
+ *                  (forward kinematics of the joint angles after that many integrations); -1: not within n_cycles.
+ *   hold         1: an arm that arrived takes no further cycle -- its joint angles, its rows of the io outputs and its nullspace sign memory
+ *                  stay as its arrival block left them (the handler returns and sends nothing more); 0: it keeps tracking its goal.
+ *   io->active   the caller's gate: such arms never run, never arrive, are not counted in pending[], and their q rows carry io->q.
+ *   An arm WITHOUT a goal block never arrives: the check reads the goal block's `present` flag (its goal_dist row is measured against the
+ *   zero frame of an empty block, which a tool near the origin would pass).
+ *   io outputs   passed to every block: every arm's rows are those of its last evaluated cycle; status ORs over the blocks.  io->goal_dist,
+ *                when given, receives the distances of the last check (an arm that did not run its block: of its last).  io->q is never written.
+ *   q_traj rows  are the q ping-pong of the blocks when given (block k reads row k - 1, block 0 io->q); else two buffers of the handle.
+ * Device pointers, io dtype, asynchronous; like the setters the call first waits for outstanding vfik_submit_host tickets and has no other
+ * host wait.  It changes no vfik_set_* state, vfik_launch_epoch does not move, and it launches the cycle kernels vfik_rollout launches.  The
+ * handle's own buffers (gate, pending, a distance row, the q pair, the staging of a q row that is not 16-byte aligned) are allocated at the
+ * first call that needs them: a host that CAPTURES vfik_goto makes one such call outside the capture first (VFIK_E_STATE otherwise).
+ * VFIK_E_ARG, nothing enqueued: o or o->arrived NULL, stride < 1, n_cycles outside [1, 1000000] or no multiple of stride, dt not finite, a
+ * precision negative or NaN, io->q_cmded / io->track_error / io->obj_dist given (as vfik_rollout); VFIK_E_STATE: no chain set. */
+typedef struct vfik_goto_opts {
+    int32_t n_cycles;          /* time-out in control cycles, 1..1000000, a multiple of stride */
+    int32_t stride;            /* cycles between two arrival checks, >= 1; n_checks = n_cycles / stride */
+    double  dt;                /* as vfik_rollout */
+    int32_t clamp_to_limits;   /* as vfik_rollout */
+    int32_t hold;              /* 1: an arm that arrived takes no further cycle (its q, its output rows and its nullspace memory stay) */
+    double  pos_prec, rot_prec;/* metres, RADIANS: goal_precision of handlers.py:346-387 */
+    int32_t* arrived;          /* out [B]  cycle index of the arm's first successful check, -1 = not within n_cycles.  Required */
+    int32_t* pending;          /* out [n_checks]  arms still under way after check k; may be NULL (the handle keeps its own) */
+    void*   q_out;             /* out [B][n]  joint angles after the last block (held arms: at arrival); may be NULL */
+    void*   q_traj;            /* out [n_checks][B][n]  every arm's joint angles after block k; may be NULL */
+    void*   dist_traj;         /* out [n_checks][B][2]  goal_dist at check k; may be NULL */
+} vfik_goto_opts;
+/* sizeof(vfik_goto_opts) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_goto_opts_size(void);
+int vfik_goto(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o);
+/* The same with HOST pointers (io and o alike); copies in, enqueues, copies out, synchronises.  After every poll_checks checks (>= 1;
+ * 0 = never) it reads pending[k] back and stops enqueuing once that is 0: a 20 s time-out then costs the time the slowest arm needs.
+ * *checks_run (may be NULL) = the number of checks executed; rows of pending, q_traj and dist_traj beyond it are not written. */
+int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, int poll_checks, int* checks_run);
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

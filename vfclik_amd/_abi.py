@@ -49,6 +49,13 @@ class SceneMove(C.Structure):
                 ("active", C.c_void_p), ("n_rep", C.c_int32), ("n_fun", C.c_int32), ("n_hem", C.c_int32), ("n_att", C.c_int32)]
 
 
+class GotoOpts(C.Structure):
+    """``struct vfik_goto_opts`` (include/vfik.h: vfik_goto)."""
+    _fields_ = [("n_cycles", C.c_int32), ("stride", C.c_int32), ("dt", C.c_double), ("clamp_to_limits", C.c_int32), ("hold", C.c_int32),
+                ("pos_prec", C.c_double), ("rot_prec", C.c_double), ("arrived", C.c_void_p), ("pending", C.c_void_p), ("q_out", C.c_void_p),
+                ("q_traj", C.c_void_p), ("dist_traj", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

@@ -111,6 +111,16 @@ struct vfik_handle {
     double* d_mixw = nullptr;  // [16]
     unsigned long long* d_stamps = nullptr;  // diagnostic build only
     void* d_rollq[2] = {nullptr, nullptr};  // q ping-pong of the stepped rollout (long chains)
+    // vfik_goto, each allocated at the first call that needs it: the gate its blocks run under, pending[] when the caller keeps none, a
+    // goal_dist row when the caller names none, the blocks' q pair without q_traj (not d_rollq: a stepped block's own intermediate cycles
+    // ping-pong there, and its first would write the row it reads), the device side of vfik_goto_host
+    int* d_goto_gate = nullptr;
+    int* d_goto_pending = nullptr;
+    int goto_pending_cap = 0;
+    void* d_goto_dist = nullptr;
+    void* d_gotoq[2] = {nullptr, nullptr};
+    void* d_goto_stage = nullptr;
+    size_t goto_stage_bytes = 0;
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -564,7 +574,8 @@ void vfik_destroy(vfik_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
-                    h->d_qalign, h->d_repmap, h->d_scenemap, h->d_move_stage};
+                    h->d_qalign, h->d_repmap, h->d_scenemap, h->d_move_stage, h->d_goto_gate, h->d_goto_pending, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
+                    h->d_goto_stage};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -1157,7 +1168,8 @@ static void note_launch(vfik_handle* h, const vfik::CyclePlan& p, unsigned flags
     ++h->launched_n;
 }
 
-static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp, void* q_out, hipStream_t stream) {
+// status_or: the launch ORs its status bits into what io->status holds (block 2.. of a goto), as cycle 2.. of a stepped rollout does
+static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp, void* q_out, hipStream_t stream, int status_or = 0) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!io || !io->q) return fail(VFIK_E_ARG, "a control cycle needs io->q");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
@@ -1201,7 +1213,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
             vfik::KArgs k = a;
             k.q = q_in;
             k.q_out = (last && q_out) ? q_out : h->d_rollq[c & 1];
-            k.status_or = c > 0;
+            k.status_or = c > 0 || status_or;
             if (!last) {  // intermediate cycles produce no outputs but the status bits
                 k.qdot_vf = k.qdot_null = k.qdot_out = k.pose = k.pose_nt = k.v6 = k.qdist = k.goal_dist = k.q_ref_out = nullptr;
             }
@@ -1215,6 +1227,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
     }
     a.n_cycles = n_cycles;
     a.q_out = q_out;
+    a.status_or = status_or ? 1 : 0;
     // observers of the cycle (ABI 4): they read the cycle's own pose / twist on the device
     const bool want_track = io->track_error != nullptr, want_dist = io->obj_dist != nullptr;
     if (want_track || want_dist) {
@@ -1399,6 +1412,209 @@ int vfik_step_host(vfik_handle* h, const vfik_io* io) { return cycles_host(h, io
 int vfik_rollout_host(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp_to_limits, void* q_out) {
     if (n_cycles < 1) return fail(VFIK_E_ARG, "n_cycles must be >= 1");
     return cycles_host(h, io, n_cycles, dt, clamp_to_limits, q_out);
+}
+
+// ---- batched goto (handlers.py:346-440) ------------------------------------------------------------
+size_t vfik_goto_opts_size(void) { return sizeof(vfik_goto_opts); }
+
+namespace {
+// one goto between its checks and its last block: the caller's io and options (device pointers) and the buffers that stand in for those it left out
+struct GotoRun {
+    const vfik_io* io;
+    vfik_goto_opts o;
+    int n_checks;
+    int32_t* pending;
+    size_t qrow, drow;   // bytes of a q row [B][n] and of a distance row [B][2]
+    bool gated;          // the blocks run under the handle's gate (hold, or the caller gates): else every arm runs every block
+};
+
+// everything that can refuse the call, before anything is enqueued
+int goto_check(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!io || !io->q) return fail(VFIK_E_ARG, "a goto needs io->q");
+    if (!o || !o->arrived) return fail(VFIK_E_ARG, "vfik_goto: the options and their arrived[B] are required");
+    if (o->stride < 1) return fail(VFIK_E_ARG, "stride %d: at least one cycle between two checks", o->stride);
+    if (o->n_cycles < 1 || o->n_cycles > 1000000) return fail(VFIK_E_ARG, "n_cycles %d outside [1, 1e6]", o->n_cycles);
+    if (o->n_cycles % o->stride) return fail(VFIK_E_ARG, "n_cycles %d is no multiple of stride %d", o->n_cycles, o->stride);
+    if (!std::isfinite(o->dt)) return fail(VFIK_E_ARG, "dt must be finite");
+    if (!(o->pos_prec >= 0.0) || !(o->rot_prec >= 0.0)) return fail(VFIK_E_ARG, "goal precision (%g m, %g rad) must not be negative or NaN", o->pos_prec, o->rot_prec);
+    if (io->q_cmded) return fail(VFIK_E_ARG, "io->q_cmded (LWR position command form) is for vfik_step only");
+    if (io->track_error || io->obj_dist) return fail(VFIK_E_ARG, "io->track_error / io->obj_dist are per control cycle: vfik_step only, not a goto");
+    if (!io->q_lo != !io->q_hi) return fail(VFIK_E_ARG, "io->q_lo and io->q_hi come together (both or neither)");
+    if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
+    return VFIK_OK;
+}
+
+// the handle's buffers this goto needs (first call: never under stream capture), pending[] zeroed, arrived[] and the gate set
+int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r) {
+    r.io = io;
+    r.o = *o;
+    r.n_checks = o->n_cycles / o->stride;
+    r.qrow = (size_t)h->B * h->n * h->esz;
+    r.drow = (size_t)h->B * 2 * h->esz;
+    r.gated = o->hold || io->active;
+    const bool need_pending = !o->pending && h->goto_pending_cap < r.n_checks;
+    const bool need_dist = !o->dist_traj && !io->goal_dist && !h->d_goto_dist;
+    const bool need_q = !o->q_traj && !h->d_gotoq[0];
+    // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
+    const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
+                       (o->q_traj && r.n_checks > 1 && (reinterpret_cast<uintptr_t>(o->q_traj) % 16 || r.qrow % 16));
+    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign)) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return fail(VFIK_E_STATE, "vfik_goto: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such vfik_goto call before capturing the stream");
+        (void)hipGetLastError();
+        if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
+        if (need_pending) {
+            HIP_TRY(hipStreamSynchronize(h->stream));   // (an earlier goto may still count into the smaller array)
+            if (h->d_goto_pending) { (void)hipFree(h->d_goto_pending); h->dev_bytes -= (size_t)h->goto_pending_cap * sizeof(int); h->d_goto_pending = nullptr; h->goto_pending_cap = 0; }
+            if (dev_alloc(h, (void**)&h->d_goto_pending, (size_t)r.n_checks * sizeof(int), false)) return VFIK_E_HIP;
+            h->goto_pending_cap = r.n_checks;
+        }
+        if (need_dist && dev_alloc(h, &h->d_goto_dist, r.drow, false)) return VFIK_E_HIP;
+        for (int k = 0; need_q && k < 2; ++k)
+            if (!h->d_gotoq[k] && dev_alloc(h, &h->d_gotoq[k], (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
+        if (odd_q && !h->d_qalign && dev_alloc(h, &h->d_qalign, (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
+    }
+    r.pending = o->pending ? o->pending : h->d_goto_pending;
+    HIP_TRY(hipMemsetAsync(r.pending, 0, (size_t)r.n_checks * sizeof(int), h->stream));
+    vfik::ArriveArgs g{};
+    g.arrived = o->arrived;
+    g.gate = h->d_goto_gate;
+    g.active = io->active;
+    g.B = h->B;
+    g.k = -1;
+    hipError_t e = vfik::launch_arrive(h->io_dtype, g, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+void* goto_q_row(const vfik_handle* h, const GotoRun& r, int k) {
+    return r.o.q_traj ? static_cast<char*>(r.o.q_traj) + (size_t)k * r.qrow : h->d_gotoq[k & 1];
+}
+
+// block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
+int goto_block(vfik_handle* h, const GotoRun& r, int k) {
+    vfik_io b = *r.io;
+    const void* const q_prev = k == 0 ? r.io->q : goto_q_row(h, r, k - 1);
+    void* const q_now = goto_q_row(h, r, k);
+    void* const dist = r.o.dist_traj ? static_cast<char*>(r.o.dist_traj) + (size_t)k * r.drow : (r.io->goal_dist ? r.io->goal_dist : h->d_goto_dist);
+    b.q = q_prev;
+    b.goal_dist = dist;
+    b.active = r.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
+    const int rc = launch_cycles(h, &b, r.o.stride, r.o.dt, r.o.clamp_to_limits, q_now, h->stream, k > 0);
+    if (rc != VFIK_OK) return rc;
+    vfik::ArriveArgs g{};
+    g.arrived = r.o.arrived;
+    g.gate = h->d_goto_gate;
+    g.active = r.io->active;
+    g.dist = dist;
+    g.dist_prev = (r.o.dist_traj && k > 0) ? static_cast<char*>(r.o.dist_traj) + (size_t)(k - 1) * r.drow : nullptr;
+    g.q_prev = q_prev;
+    g.q_now = q_now;
+    g.goal = h->d_goal;
+    g.pending = r.pending + k;
+    g.pos_prec = r.o.pos_prec;
+    g.rot_prec = r.o.rot_prec;
+    g.B = h->B; g.n = h->n; g.k = k; g.stride = r.o.stride; g.hold = r.o.hold ? 1 : 0;
+    g.Bpad = h->Bpad;
+    hipError_t e = vfik::launch_arrive(h->io_dtype, g, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+// q_out: the row the last executed block wrote; io->goal_dist beside a trace: the trace's last row
+int goto_end(vfik_handle* h, const GotoRun& r, int checks_run) {
+    if (r.o.q_out && checks_run > 0) HIP_TRY(hipMemcpyAsync(r.o.q_out, goto_q_row(h, r, checks_run - 1), r.qrow, hipMemcpyDeviceToDevice, h->stream));
+    if (r.o.dist_traj && r.io->goal_dist && checks_run > 0)
+        HIP_TRY(hipMemcpyAsync(r.io->goal_dist, static_cast<char*>(r.o.dist_traj) + (size_t)(checks_run - 1) * r.drow, r.drow, hipMemcpyDeviceToDevice, h->stream));
+    return VFIK_OK;
+}
+}  // namespace
+
+int vfik_goto(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
+    int rc = goto_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    GotoRun r;
+    if ((rc = goto_begin(h, io, o, r)) != VFIK_OK) return rc;
+    for (int k = 0; k < r.n_checks; ++k)
+        if ((rc = goto_block(h, r, k)) != VFIK_OK) return rc;
+    return goto_end(h, r, r.n_checks);
+}
+
+// Host-pointer form: every member of io and of the options in ONE device buffer of the handle (grown on demand, members 256-byte aligned),
+// copied in before the first block and out after the last one executed.
+int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, int poll_checks, int* checks_run) {
+    int rc = goto_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    const int n_checks = o->n_cycles / o->stride;
+    const HostIo x = host_io(h, io, o->q_out);
+    const size_t qrow = (size_t)h->B * h->n * h->esz, drow = (size_t)h->B * 2 * h->esz;
+    // beside io's members: arrived, pending (always: the early exit reads it), the two traces
+    void* const hx[4] = {o->arrived, o->pending, o->q_traj, o->dist_traj};
+    const size_t bx[4] = {(size_t)h->B * sizeof(int32_t), (size_t)n_checks * sizeof(int32_t), (size_t)n_checks * qrow, (size_t)n_checks * drow};
+    const size_t per_check[4] = {0, sizeof(int32_t), qrow, drow};
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off_in[N_HIN], off_out[N_HOUT], off_x[4], total = 0;
+    for (int i = 0; i < N_HIN; ++i) { off_in[i] = total; if (x.hin[i]) total += up(x.bin[i]); }
+    for (int i = 0; i < N_HOUT; ++i) { off_out[i] = total; if (x.hout[i]) total += up(x.bout[i]); }
+    for (int i = 0; i < 4; ++i) { off_x[i] = total; if (hx[i] || i == 1) total += up(bx[i]); }
+    if (h->goto_stage_bytes < total) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_goto_stage) { (void)hipFree(h->d_goto_stage); h->dev_bytes -= h->goto_stage_bytes; h->d_goto_stage = nullptr; h->goto_stage_bytes = 0; }
+        if (dev_alloc(h, &h->d_goto_stage, total, false)) return VFIK_E_HIP;
+        h->goto_stage_bytes = total;
+    }
+    char* const dev = static_cast<char*>(h->d_goto_stage);
+    void* din[N_HIN] = {};
+    void* dout[N_HOUT] = {};
+    for (int i = 0; i < N_HIN; ++i)
+        if (x.hin[i]) {
+            din[i] = dev + off_in[i];
+            HIP_TRY(hipMemcpyAsync(din[i], x.hin[i], x.bin[i], hipMemcpyHostToDevice, h->stream));
+        }
+    for (int i = 0; i < N_HOUT; ++i)
+        if (x.hout[i]) {
+            dout[i] = dev + off_out[i];
+            // arms the gate keeps out store nothing: their rows of the caller's arrays must come back as they went in
+            if (io->active && i != 8) HIP_TRY(hipMemcpyAsync(dout[i], x.hout[i], x.bout[i], hipMemcpyHostToDevice, h->stream));
+        }
+    // (a gated arm's rows of the distance trace are never written either; its q rows are: they repeat its start)
+    if (io->active && o->dist_traj) HIP_TRY(hipMemcpyAsync(dev + off_x[3], o->dist_traj, bx[3], hipMemcpyHostToDevice, h->stream));
+    vfik_io d;
+    device_io(din, dout, d);
+    vfik_goto_opts od = *o;
+    od.arrived = reinterpret_cast<int32_t*>(dev + off_x[0]);
+    od.pending = reinterpret_cast<int32_t*>(dev + off_x[1]);
+    od.q_out = dout[8];
+    od.q_traj = o->q_traj ? dev + off_x[2] : nullptr;
+    od.dist_traj = o->dist_traj ? dev + off_x[3] : nullptr;
+    GotoRun r;
+    if ((rc = goto_begin(h, &d, &od, r)) != VFIK_OK) return rc;
+    int done = 0;
+    while (done < n_checks) {
+        if ((rc = goto_block(h, r, done)) != VFIK_OK) return rc;
+        ++done;
+        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
+            int32_t left = -1;
+            HIP_TRY(hipMemcpyAsync(&left, r.pending + (done - 1), sizeof left, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (left == 0) break;   // everybody the caller lets run is there
+        }
+    }
+    if ((rc = goto_end(h, r, done)) != VFIK_OK) return rc;
+    for (int i = 0; i < N_HOUT; ++i)
+        if (x.hout[i]) HIP_TRY(hipMemcpyAsync(x.hout[i], dout[i], x.bout[i], hipMemcpyDeviceToHost, h->stream));
+    for (int i = 0; i < 4; ++i)
+        if (hx[i]) HIP_TRY(hipMemcpyAsync(hx[i], dev + off_x[i], i == 0 ? bx[0] : (size_t)done * per_check[i], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (checks_run) *checks_run = done;
+    return VFIK_OK;
 }
 
 // ---- pipelined host path -------------------------------------------------------------------------

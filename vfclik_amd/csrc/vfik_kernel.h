@@ -524,6 +524,23 @@ struct SceneMoveArgs {
     int n_fun, n_hem, n_att, map_planes;
 };
 hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream);
+// vfik_goto: the arrival check that runs after block k of a goto (arrive_kernel, vfik_kernel.hip).  k < 0: the pass in front of block 0 --
+// arrived[b] = -1, gate[b] = the caller's gate -- and nothing else.
+struct ArriveArgs {
+    int* arrived;               // [B] cycle index of the arm's first successful check, -1 = not yet
+    int* gate;                  // [B] the handle's gate: what block k ran under on entry, what block k + 1 runs under on exit
+    const int* active;          // [B] the caller's gate, or NULL = every arm
+    void* dist;                 // [B][2] goal_dist of block k (metres, degrees)
+    const void* dist_prev;      // [B][2] the trace's row k - 1, or NULL (no trace, or k = 0): what an arm that did not run repeats
+    const void* q_prev;         // [B][n] the q row block k read
+    void* q_now;                // [B][n] the q row block k wrote
+    const void* goal;           // the goal block's 4 quad planes: plane 3, component 0 is its `present` flag
+    int* pending;               // &pending[k]: zeroed on the stream in front of the goto
+    double pos_prec, rot_prec;  // metres, radians
+    int B, n, k, stride, hold;
+    long Bpad;
+};
+hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

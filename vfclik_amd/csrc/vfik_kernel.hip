@@ -2504,6 +2504,59 @@ __global__ void __launch_bounds__(256) track_kernel(const T* pose, const T* v6, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// vfik_goto: the arrival check of the reference's "send a goal, then wait until the arm is there" calls (handlers.py:346-440: gotoFrame
+// reads the object-0 entry of /dmonitor/distOut until pos_dist < goal_precision[0] and orient_dist * pi / 180 < goal_precision[1],
+// handlers.py:374-381), batched: one thread per arm after block k of a goto -- `stride` control cycles that ran under gate[] and left
+// their goal_dist row in `dist` and the integrated joint angles in q_now.
+//   the arm did not run (gate[b] == 0): the cycle kernel stored nothing for it -- its q row and, in a trace, its distance row repeat;
+//   it ran and has not arrived yet: arrived when both STRICT compares hold in double (NaN never arrives), at cycle (k + 1) * stride - 1,
+//     the 0-based cycle whose tool pose the distances were measured at.  An arm without a goal block never arrives: its goal_dist is
+//     measured against the zero frame of an empty block (a tool near the origin would pass), so the block's `present` flag decides;
+//   next block's gate: the caller's, and with `hold` not once the arm arrived;
+//   pending[k]: the arms the caller lets run that have not arrived -- a wave ballot, one atomic add per wave.
+// Rows of n elements per lane, as the cycle kernel's q_out store; no LDS, no scratch.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) arrive_kernel(const ArriveArgs g) {
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool under_way = false;
+    if (b < g.B) {
+        const bool ua = !g.active || g.active[b] != 0;
+        if (g.k < 0) {   // (uniform: the pass in front of block 0)
+            g.arrived[b] = -1;
+            g.gate[b] = ua ? 1 : 0;
+            return;
+        }
+        int arr = g.arrived[b];
+        T* const dn = static_cast<T*>(g.dist) + (long)b * 2;
+        if (g.gate[b] == 0) {
+            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
+            T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
+            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
+            if (g.dist_prev) {
+                const T* const dp = static_cast<const T*>(g.dist_prev) + (long)b * 2;
+                dn[0] = dp[0];
+                dn[1] = dp[1];
+            }
+        } else if (arr < 0) {
+            const bool present = static_cast<const T*>(g.goal)[(3 * g.Bpad + b) * 4] != (T)0;
+            const double d = (double)dn[0];
+            const double a = ((double)dn[1] * M_PI) / 180.0;
+            if (present && d < g.pos_prec && a < g.rot_prec) {
+                arr = (g.k + 1) * g.stride - 1;
+                g.arrived[b] = arr;
+            }
+        }
+        g.gate[b] = (ua && !(g.hold && arr >= 0)) ? 1 : 0;
+        under_way = ua && arr < 0;
+    } else if (g.k < 0) {
+        return;
+    }
+    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Distance monitor of scripts/monitor_distance (monitor_distance:76-84,148-167), batched: for every arm
 // and every object frame it was told about (/dmonitor/objectsIn: the goal is object 0, obstacles
 // follow), the xyz distance between the tool pose and the object and the rotation angle between their
@@ -3673,6 +3726,13 @@ hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* 
     else
         hipLaunchKernelGGL(track_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
                            static_cast<const double*>(v6), state, static_cast<double*>(out), active, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream) {
+    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
+    if (io_dtype == 32) hipLaunchKernelGGL(arrive_kernel<float>, grid, blk, 0, stream, g);
+    else hipLaunchKernelGGL(arrive_kernel<double>, grid, blk, 0, stream, g);
     return hipGetLastError();
 }
 }  // namespace vfik

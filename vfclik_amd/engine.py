@@ -75,6 +75,9 @@ def load_library(path=None):
         "vfik_sync": (C.c_int, [H]),
         "vfik_rollout": (C.c_int, [H, C.POINTER(IO), C.c_int, C.c_double, C.c_int, C.c_void_p]),
         "vfik_rollout_host": (C.c_int, [H, C.POINTER(IO), C.c_int, C.c_double, C.c_int, C.c_void_p]),
+        "vfik_goto_opts_size": (C.c_size_t, []),
+        "vfik_goto": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoOpts)]),
+        "vfik_goto_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoOpts), C.c_int, C.POINTER(C.c_int)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -117,6 +120,9 @@ def load_library(path=None):
     if lib.vfik_scene_move_size() != C.sizeof(_abi.SceneMove):
         raise VfikError("struct layout mismatch: vfik_scene_move is %d bytes in the library, %d in the Python mirror"
                         % (lib.vfik_scene_move_size(), C.sizeof(_abi.SceneMove)))
+    if lib.vfik_goto_opts_size() != C.sizeof(_abi.GotoOpts):
+        raise VfikError("struct layout mismatch: vfik_goto_opts is %d bytes in the library, %d in the Python mirror"
+                        % (lib.vfik_goto_opts_size(), C.sizeof(_abi.GotoOpts)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
         _lib = lib
     return lib
@@ -554,6 +560,88 @@ class Engine:
     def rollout(self, io, n_cycles, dt, q_out=None, clamp=False):
         """Asynchronous device-pointer form of :meth:`rollout_host`."""
         self._chk(self.lib.vfik_rollout(self.h, C.byref(io), int(n_cycles), float(dt), 1 if clamp else 0, C.c_void_p(_ptr(q_out))))
+
+    # -- batched goto (vfik_goto: handlers.py:346-440 for the batch) --------------------------------
+    def _goto_opts(self, n_cycles, dt, precision, stride, hold, clamp):
+        pos, rot = precision
+        o = _abi.GotoOpts()
+        o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
+        o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
+        o.pos_prec, o.rot_prec = float(pos), float(rot)
+        return o
+
+    def goto(self, io, n_cycles, dt, precision, stride=1, hold=False, clamp=False, arrived=None, pending=None, q_out=None, q_traj=None,
+             dist_traj=None):
+        """Drive the arms to their goals and report arrival, asynchronously on the engine's stream (include/vfik.h: vfik_goto):
+        ``n_cycles / stride`` blocks of ``stride`` control cycles from ``io.q`` (``io`` from :meth:`make_io`), after each block one
+        arrival check against ``precision`` = (metres, radians) -- gotoFrame's goal_precision.  ``arrived``: int32 (B,), required, the
+        cycle index of each arm's first successful check or -1; ``pending``: int32 (n_checks,), arms still under way after every check;
+        ``q_out`` (B, n); ``q_traj`` (n_checks, B, n); ``dist_traj`` (n_checks, B, 2).  Torch tensors on this device or raw addresses.
+        ``hold``: an arm that arrived takes no further cycle."""
+        if arrived is None:
+            raise ValueError("goto needs arrived, an int32 (batch,) device array")
+        n_checks = int(n_cycles) // max(int(stride), 1)
+        for name, x, shape, dt_name in (("arrived", arrived, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
+                                        ("q_out", q_out, (self.batch, self.n), self.io_dtype.name),
+                                        ("q_traj", q_traj, (n_checks, self.batch, self.n), self.io_dtype.name),
+                                        ("dist_traj", dist_traj, (n_checks, self.batch, 2), self.io_dtype.name)):
+            if x is None or isinstance(x, int):
+                continue
+            if not x.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            if str(x.dtype).split(".")[-1] != dt_name or tuple(x.shape) != shape:
+                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
+        o = self._goto_opts(n_cycles, dt, precision, stride, hold, clamp)
+        o.arrived, o.pending, o.q_out, o.q_traj, o.dist_traj = _ptr(arrived), _ptr(pending), _ptr(q_out), _ptr(q_traj), _ptr(dist_traj)
+        self._chk(self.lib.vfik_goto(self.h, C.byref(io), C.byref(o)))
+
+    def goto_host(self, q, n_cycles, dt, precision, stride=1, hold=False, clamp=False, trajectory=False, poll=0, want=("qdot_out",),
+                  null_control=None, active=None, q_lo=None, q_hi=None, q_ref=None):
+        """Host arrays in, host arrays out (vfik_goto_host; synchronous).  Returns a dict with ``q`` (joint angles after the last block
+        executed; held arms: at arrival), ``arrived`` (B,), ``pending`` (checks_run,), ``checks_run``, the rows named in ``want`` (every
+        arm's: those of its last evaluated cycle) and, with ``trajectory``, ``q_traj`` (checks_run, B, n) and ``dist_traj``
+        (checks_run, B, 2).  ``poll`` > 0: after every ``poll`` checks the count of arms still under way is read back and the goto ends
+        once it is 0 -- ``checks_run`` then tells how far it went.  Arms gated off by ``active`` never run and never arrive."""
+        q = np.ascontiguousarray(q, dtype=self.io_dtype)
+        if q.shape != (self.batch, self.n):
+            raise ValueError("q must be (%d, %d), got %s" % (self.batch, self.n, q.shape))
+        io = IO()
+        io.q = q.ctypes.data
+        keep = [q]
+        self._host_inputs(io, keep, active, q_lo, q_hi)
+        if q_ref is not None:
+            a = np.ascontiguousarray(q_ref, dtype=self.io_dtype)
+            if a.shape != (self.batch, self.n):
+                raise ValueError("q_ref must be (%d, %d), got %s" % (self.batch, self.n, a.shape))
+            io.q_ref = a.ctypes.data
+            keep.append(a)
+        if null_control is not None:
+            nc = np.ascontiguousarray(null_control, dtype=self.io_dtype)
+            if nc.shape != (self.batch, _abi.NULL_CONTROLS):
+                raise ValueError("null_control must be (batch, 4)")
+            io.null_control = nc.ctypes.data
+            keep.append(nc)
+        o = self._goto_opts(n_cycles, dt, precision, stride, hold, clamp)
+        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
+        out = {}
+        for k in want:
+            out[k] = np.zeros(self.batch, dtype=np.int32) if k == "status" else np.zeros(self._shape(k), dtype=self.io_dtype)
+            setattr(io, k, out[k].ctypes.data)
+        out["q"] = q.copy()
+        out["arrived"] = np.full(self.batch, -1, dtype=np.int32)
+        out["pending"] = np.zeros(n_checks, dtype=np.int32)
+        o.q_out, o.arrived, o.pending = out["q"].ctypes.data, out["arrived"].ctypes.data, out["pending"].ctypes.data
+        if trajectory:
+            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
+            out["dist_traj"] = np.zeros((n_checks, self.batch, 2), dtype=self.io_dtype)
+            o.q_traj, o.dist_traj = out["q_traj"].ctypes.data, out["dist_traj"].ctypes.data
+        ran = C.c_int(0)
+        self._chk(self.lib.vfik_goto_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
+        out["checks_run"] = int(ran.value)
+        for k in ("pending", "q_traj", "dist_traj"):
+            if k in out:
+                out[k] = out[k][:out["checks_run"]]
+        return out
 
     def make_io(self, q, null_control=None, q_ref=None, q_cmded=None, active=None, q_lo=None, q_hi=None, **outs):
         """IO block from device pointers (torch tensors on this device, or raw addresses).  active: int32 [B]."""

@@ -223,6 +223,43 @@ class ShardedEngine:
                 f.result()
         return full
 
+    def goto_host(self, q, n_cycles, dt, precision, global_rows=True, **kw):
+        """Engine.goto_host over this rank's arms: host arrays in (global or local rows), this rank's rows out, concatenated in arm
+        order -- ``q``, ``arrived``, the rows named in ``want`` and, with ``trajectory``, ``q_traj`` / ``dist_traj`` (along their arm
+        axis).  Per-arm keyword arrays (null_control, active, q_lo, q_hi, q_ref) are sliced as :meth:`step_host` slices them.  Every
+        part's goto is enqueued before any is waited for: a goto with ``poll`` reads its counts back while it runs, so each device is
+        driven by a thread of its own around the blocking call (the stand-in path of :meth:`step_host`), and the devices work
+        concurrently.  With ``poll`` each part ends when ITS arms are there: ``checks_run`` is the largest count, ``pending`` the sum over
+        the parts (a part that ended early adds 0), and the traces of a part that ended early repeat its last row."""
+        import numpy as np
+        per_arm = ("null_control", "active", "q_lo", "q_hi", "q_ref")
+        qs = self._rows(q, "q", global_rows)
+        kws = {k: self._rows(kw.pop(k), k, global_rows) for k in per_arm if kw.get(k) is not None}
+        for k in per_arm:
+            kw.pop(k, None)
+        if not self.parts:
+            raise ValueError("this rank owns no arm: there is nothing to drive")
+
+        def run(i):
+            return self.engines[i].goto_host(qs[i], n_cycles, dt, precision, **dict(kw, **{k: v[i] for k, v in kws.items()}))
+        if len(self.parts) == 1:
+            return run(0)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=len(self.parts)) as pool:
+            outs = list(pool.map(run, range(len(self.parts))))
+        ran = max(o["checks_run"] for o in outs)
+        full = {"checks_run": ran}
+        for k in outs[0]:
+            if k == "checks_run":
+                continue
+            if k == "pending":
+                full[k] = np.sum([np.pad(o[k], (0, ran - len(o[k]))) for o in outs], axis=0).astype(np.int32)
+            elif k in ("q_traj", "dist_traj"):
+                full[k] = np.concatenate([np.concatenate([o[k]] + [o[k][-1:]] * (ran - len(o[k])), axis=0) for o in outs], axis=1)
+            else:
+                full[k] = np.concatenate([o[k] for o in outs], axis=0)
+        return full
+
     def gather(self, local_rows, dist=None):
         """The rows of every rank, in arm order, on every rank (torch tensor in, torch tensor out)."""
         if self.world == 1:
