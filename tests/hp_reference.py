@@ -10,8 +10,10 @@ mantissa where mpmath cannot be imported):
   * the geometric Jacobian about the flange origin in the base frame, rows (v, w) as oracle_c.jacobian orders them;
   * qdot = Wq Jw^T (Jw Jw^T + lambda^2 I)^-1 Wy tw with Jw = Wy J Wq (identity tool: the twist is taken at the flange).
 
-The twist is an INPUT (the oracle's v6 for the same, already rounded inputs): the field evaluation is well conditioned and has tests of its
-own; what is held here is the kinematics and the solve.  Per arm the helper also returns cond = (s1^2 + lambda^2) / (s6^2 + lambda^2), s the
+The twist is an INPUT (the oracle's v6 for the same, already rounded inputs): what is held here is the kinematics and the solve.  The field
+evaluation is NOT well conditioned everywhere (decay orders up to 127, cancelling forces, normCart, the 1e-9 floors) and is held to a
+50-digit reference of its own at its decision edges by tests/hp_field.py, tests/test_oracle_field_edges.py and
+tests/test_gpu_field_edges.py.  Per arm the helper also returns cond = (s1^2 + lambda^2) / (s6^2 + lambda^2), s the
 singular values of Jw (numpy.linalg.svd of the rounded high-precision Jw), and the solve's own relative residual |A y - Wy tw| / |Wy tw|.
 
 Results are returned as pairs of doubles (hi, lo) with hi + lo = the high-precision value to ~32 digits, so that `error` does not add the

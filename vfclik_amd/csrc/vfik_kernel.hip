@@ -55,9 +55,11 @@ __device__ __forceinline__ double rcp_nr(double x) {  // 1/x, ~1 ulp, x normal a
     return __builtin_fma(y, e, y);
 }
 
-// 1/sqrt(x) from ONE Newton step on v_rsq_f64 (5 instructions, relative error ~1e-14): enough for the decay repellers,
-// whose magnitude ((radius + safe) / D)^order feeds a vector that is normalised afterwards; sqrt_rsqrt's two
-// Goldschmidt steps (10 instructions, ~1 ulp) stay where the value itself is published.  x = 0 gives a large finite value.
+// 1/sqrt(x) from ONE Newton step on v_rsq_f64 (5 instructions): the decay repellers' 1 / D, which is raised to the decay order (up to 127).
+// The step's error is measured directly by tools/ubench_rsqrt.hip (figures in DESIGN 6.2).  An error COMMON to the slots of one order is
+// a common factor of their terms and leaves a normalised sum unchanged but for the goal's share; tests/test_gpu_field_edges.py bounds
+// what the twist sees of it.  sqrt_rsqrt's two Goldschmidt steps (10 instructions) stay where the value itself is published.
+// x = 0 gives a large finite value.
 __device__ __forceinline__ double rsqrt_1nr(double x) {
     const double y = __builtin_amdgcn_rsq(fmax(x, 1e-300));
     const double e = __builtin_fma(-(x * y), y, 1.0);
@@ -1652,7 +1654,9 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                         dx[m] = v[6 * hf] - pt[0];
                         dy[m] = v[6 * hf + 1] - pt[1];
                         dz[m] = v[6 * hf + 2] - pt[2];
-                        rs[m] = v[6 * hf + 3] + v[6 * hf + 4];
+                        // A slot past the batch's last is masked in its base as well as its force: its quads repeat plane 0, and a negative
+                        // "radius + safe" read from there overflows to -inf at high orders near that obstacle's centre -- 0 * -inf.
+                        rs[m] = m < ncur ? v[6 * hf + 3] + v[6 * hf + 4] : 0.0;
                         fk[m] = m < ncur ? v[6 * hf + 5] : 0.0;
                     }
                 }
