@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/vfik.h"
+#include "vfik_io_layout.h"
 #include "vfik_kernel.h"
 
 namespace {
@@ -101,8 +102,8 @@ struct vfik_handle {
     unsigned short* d_repmap = nullptr;   // vfik_move_fields: general slot of the arm's k-th decay repeller, 8 entries (16 bytes) per arm and plane (vfik_kernel.h: MoveArgs)
     unsigned short* d_scenemap = nullptr; // vfik_move_scene: the same for its k-th funnel, hemisphere and attractor behind the goal block, three maps in a row (vfik_kernel.h: SceneMoveArgs)
     bool fields_set = false;       // some vfik_set_fields call succeeded: there are images to move
-    void* d_move_stage = nullptr;  // vfik_move_fields_host: the rounded rows on the device, grown on demand
-    size_t move_stage_bytes = 0;
+    struct DevBuf { void* p = nullptr; size_t bytes = 0; };   // a device buffer grown on demand (reserve)
+    DevBuf move_stage;             // vfik_move_fields_host / vfik_move_scene_host: the rounded rows on the device
     void* d_tool = nullptr;    // 3 quad planes (per-arm tools only)
     double tool_shared[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     int tool_per_arm = 0;
@@ -115,12 +116,10 @@ struct vfik_handle {
     // goal_dist row when the caller names none, the blocks' q pair without q_traj (not d_rollq: a stepped block's own intermediate cycles
     // ping-pong there, and its first would write the row it reads), the device side of vfik_goto_host
     int* d_goto_gate = nullptr;
-    int* d_goto_pending = nullptr;
-    int goto_pending_cap = 0;
+    DevBuf goto_pending;
     void* d_goto_dist = nullptr;
     void* d_gotoq[2] = {nullptr, nullptr};
-    void* d_goto_stage = nullptr;
-    size_t goto_stage_bytes = 0;
+    DevBuf goto_stage;
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -140,6 +139,7 @@ struct vfik_handle {
     // dtype, and the cycle's pose / field twist when the caller did not ask for them itself
     void* d_objects = nullptr;
     int n_objects = 0;
+    vfik::IoDims io_dims() const { return {(size_t)n, esz, (size_t)n_objects}; }   // what the sizes of vfik_io's members depend on (vfik_io_layout.h)
     void* d_obs_pose = nullptr;
     void* d_obs_v6 = nullptr;
     size_t dev_bytes = 0;
@@ -163,13 +163,12 @@ struct vfik_handle {
     void* arena_host_dev = nullptr;   // the device's address of the pinned host arena (zero-copy calls)
     size_t arena_bytes = 0;
     size_t zero_copy_max = (size_t)64 << 10;   // calls of at most this many bytes: the kernel reads / writes the pinned arena itself (VFIK_ZERO_COPY_MAX)
-    struct Scratch { void* p = nullptr; size_t bytes = 0; };
-    Scratch sc[20];  // ... and per-member device buffers for calls of few large members
+    DevBuf sc[vfik::N_STAGED];  // ... and per-member device buffers for calls of few large members (not part of vfik_device_bytes, like the arenas)
     // pipelined host path (vfik_submit_host / vfik_wait): up to PIPE submissions in flight, each slot with
     // its own device staging buffers and events; s_in / s_out are the side streams
     static constexpr int PIPE = 3;
     struct PipeSlot {
-        Scratch sc[20];
+        DevBuf sc[vfik::N_STAGED];
         hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;
         long ticket = -1;  // submission living in this slot, -1 = free
     };
@@ -180,10 +179,37 @@ struct vfik_handle {
 
 namespace {
 
-int dev_alloc(vfik_handle* h, void** p, size_t bytes, bool zero) {
+// counted: the allocation is part of vfik_device_bytes
+int dev_alloc(vfik_handle* h, void** p, size_t bytes, bool zero, bool counted = true) {
     HIP_TRY(hipMalloc(p, bytes));
-    h->dev_bytes += bytes;
+    if (counted) h->dev_bytes += bytes;
     if (zero) HIP_TRY(hipMemsetAsync(*p, 0, bytes, h->stream));
+    return VFIK_OK;
+}
+
+// Grow-on-demand device buffer: at least `bytes`, the old content lost.  counted: the buffer is part of vfik_device_bytes; sync: work on the
+// handle's stream may still use the old buffer.
+int reserve(vfik_handle* h, vfik_handle::DevBuf& b, size_t bytes, bool counted, bool sync) {
+    if (bytes <= b.bytes) return VFIK_OK;
+    if (sync) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (b.p) { (void)hipFree(b.p); if (counted) h->dev_bytes -= b.bytes; }
+    b = {};
+    if (dev_alloc(h, &b.p, bytes, false, counted)) return VFIK_E_HIP;
+    b.bytes = bytes;
+    return VFIK_OK;
+}
+
+// Buffers of the handle are allocated at the first call that needs them, never while `stream` is being captured (the allocation would be part
+// of the captured work or fail it): the caller's message tells which call to make outside the capture first.
+int refuse_capture(hipStream_t stream, const char* msg) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return fail(VFIK_E_STATE, "%s", msg);
+    (void)hipGetLastError();
+    return VFIK_OK;
+}
+
+int check_arms(const vfik_handle* h, int first_arm, int n_arms) {
+    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
     return VFIK_OK;
 }
 
@@ -215,6 +241,11 @@ bool gpu_visible(const void* p) {
 template <typename T>
 void put(std::vector<char>& buf, size_t idx, double v) {
     reinterpret_cast<T*>(buf.data())[idx] = static_cast<T>(v);
+}
+
+// ... rounded to the handle's I/O type
+void put_io(const vfik_handle* h, std::vector<char>& buf, size_t idx, double v) {
+    if (h->io_dtype == 32) put<float>(buf, idx, v); else put<double>(buf, idx, v);
 }
 
 // Pack the field sets of n_arms arms into quad-plane staging images (plane P, arm j, component c ->
@@ -531,10 +562,7 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
     }
     {   // the uniform image starts out with every slot unused (radius -inf), like the zeros (force 0) of the other two images
         std::vector<char> plane((size_t)h->Bpad * 4 * h->esz, 0);
-        for (int b = 0; b < h->Bpad; ++b) {
-            if (io_dtype == 32) put<float>(plane, (size_t)b * 4 + 3, -std::numeric_limits<double>::infinity());
-            else put<double>(plane, (size_t)b * 4 + 3, -std::numeric_limits<double>::infinity());
-        }
+        for (int b = 0; b < h->Bpad; ++b) put_io(h, plane, (size_t)b * 4 + 3, -std::numeric_limits<double>::infinity());
         for (int sidx = 0; sidx < std::max(1, max_slots) + 1; ++sidx)   // (plane 0 stays like this for good: the slot every out-of-range quad reads)
             if (hipMemcpyAsync(static_cast<char*>(h->d_slots_uni) + (size_t)sidx * plane.size(), plane.data(), plane.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess)
                 return bail("init uniform image");
@@ -574,8 +602,8 @@ void vfik_destroy(vfik_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
-                    h->d_qalign, h->d_repmap, h->d_scenemap, h->d_move_stage, h->d_goto_gate, h->d_goto_pending, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->d_goto_stage};
+                    h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
+                    h->goto_stage.p};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -691,7 +719,7 @@ static int ensure_arm_weights(vfik_handle* h) {
 int vfik_set_arm_weights(vfik_handle* h, int first_arm, int n_arms, const double* wy, const double* wq) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (!wy && !wq) return fail(VFIK_E_ARG, "vfik_set_arm_weights: give wy, wq or both");
     for (int j = 0; j < n_arms; ++j) {
         for (int k = 0; wy && k < 6; ++k)
@@ -761,7 +789,7 @@ int vfik_set_tool(vfik_handle* h, const double* tool16, int per_arm) {
         for (int k = 0; k < 12; ++k) {  // rows 0..2 of the 4x4 -> 3 quad planes
             const double v = tool16[b * 16 + k];
             const size_t idx = ((size_t)(k >> 2) * Bp + b) * 4 + (k & 3);
-            if (h->io_dtype == 32) put<float>(buf, idx, v); else put<double>(buf, idx, v);
+            put_io(h, buf, idx, v);
         }
     if (!h->d_tool && dev_alloc(h, &h->d_tool, buf.size(), false)) return VFIK_E_HIP;
     HIP_TRY(hipMemcpyAsync(h->d_tool, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
@@ -775,7 +803,7 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
     if (check_handle(h)) return VFIK_E_ARG;
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
     if (!fields || !counts) return fail(VFIK_E_ARG, "null fields / counts");
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (max_fields < 0) return fail(VFIK_E_ARG, "negative max_fields");
     // validate everything before touching device state
     for (int j = 0; j < n_arms; ++j) {
@@ -875,14 +903,15 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
 
 // the checks the two forms of vfik_move_fields share
 static int move_check(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep) {
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (!goal16 && !rep4) return fail(VFIK_E_ARG, "vfik_move_fields: give goal16, rep4 or both");
     if (n_rep < 0 || n_rep > h->max_slots) return fail(VFIK_E_ARG, "n_rep %d outside [0, %d]", n_rep, h->max_slots);
     if (!h->fields_set) return fail(VFIK_E_STATE, "vfik_move_fields before any vfik_set_fields: there is nothing to move");
     return VFIK_OK;
 }
 
-static int move_launch(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
+// the images of the handle and the rows to write into them (an array with no rows is no array)
+static vfik::MoveArgs move_args(const vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
     vfik::MoveArgs m{};
     m.goal = h->d_goal;
     m.slots = h->d_slots;
@@ -897,19 +926,14 @@ static int move_launch(vfik_handle* h, int first_arm, int n_arms, const void* go
     m.n_rep = n_rep;
     m.S = h->max_slots;
     m.Bpad = h->Bpad;
+    return m;
+}
+
+static int move_launch(vfik_handle* h, int first_arm, int n_arms, const void* goal16, const void* rep4, int n_rep, const int32_t* active) {
+    const vfik::MoveArgs m = move_args(h, first_arm, n_arms, goal16, rep4, n_rep, active);
     if (!m.goal16 && !m.rep4) return VFIK_OK;   // (rep4 with no rows: nothing to write)
     hipError_t e = vfik::launch_move(h->io_dtype, m, h->stream);
     if (e != hipSuccess) return fail(VFIK_E_HIP, "move launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-// the host forms' staging buffer, grown on demand
-static int move_stage_reserve(vfik_handle* h, size_t bytes) {
-    if (bytes <= h->move_stage_bytes) return VFIK_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->d_move_stage) { (void)hipFree(h->d_move_stage); h->dev_bytes -= h->move_stage_bytes; h->d_move_stage = nullptr; h->move_stage_bytes = 0; }
-    if (dev_alloc(h, &h->d_move_stage, bytes, false)) return VFIK_E_HIP;
-    h->move_stage_bytes = bytes;
     return VFIK_OK;
 }
 
@@ -934,11 +958,11 @@ int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const doubl
     std::vector<char> buf((ng + nr) * h->esz);   // rounded as vfik_set_fields rounds p[] (NaN stays NaN)
     for (size_t k = 0; k < ng + nr; ++k) {
         const double v = k < ng ? goal16[k] : rep4[k - ng];
-        if (h->io_dtype == 32) put<float>(buf, k, v); else put<double>(buf, k, v);
+        put_io(h, buf, k, v);
     }
-    if (move_stage_reserve(h, buf.size()) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipMemcpyAsync(h->d_move_stage, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
-    char* d = static_cast<char*>(h->d_move_stage);
+    if (reserve(h, h->move_stage, buf.size(), true, true) != VFIK_OK) return VFIK_E_HIP;
+    char* d = static_cast<char*>(h->move_stage.p);
+    HIP_TRY(hipMemcpyAsync(d, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
     const int rl = move_launch(h, first_arm, n_arms, goal16 ? d : nullptr, rep4 ? d + ng * h->esz : nullptr, n_rep, nullptr);
     if (rl != VFIK_OK) return rl;
     HIP_TRY(hipStreamSynchronize(h->stream));   // `buf` and the stage are reused
@@ -950,7 +974,7 @@ size_t vfik_scene_move_size(void) { return sizeof(vfik_scene_move); }
 // the checks the two forms of vfik_move_scene share
 static int scene_check(vfik_handle* h, int first_arm, int n_arms, const vfik_scene_move* mv) {
     if (!mv) return fail(VFIK_E_ARG, "vfik_move_scene: null vfik_scene_move");
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (!mv->goal16 && !mv->rep4 && !mv->fun6 && !mv->hem6 && !mv->att16) return fail(VFIK_E_ARG, "vfik_move_scene: give at least one of goal16, rep4, fun6, hem6, att16");
     const struct { const char* name; int v; } counts[] = {{"n_rep", mv->n_rep}, {"n_fun", mv->n_fun}, {"n_hem", mv->n_hem}, {"n_att", mv->n_att}};
     for (const auto& c : counts)
@@ -967,19 +991,7 @@ static int scene_launch(vfik_handle* h, int first_arm, int n_arms, const vfik_sc
     s.hem6 = mv.n_hem > 0 ? mv.hem6 : nullptr;
     s.att16 = mv.n_att > 0 ? mv.att16 : nullptr;
     if (!s.fun6 && !s.hem6 && !s.att16) return move_launch(h, first_arm, n_arms, mv.goal16, rep4, rep4 ? mv.n_rep : 0, mv.active);
-    s.m.goal = h->d_goal;
-    s.m.slots = h->d_slots;
-    s.m.slots_fast = h->d_slots_fast;
-    s.m.slots_uni = h->d_slots_uni;
-    s.m.repmap = h->d_repmap;
-    s.m.goal16 = mv.goal16;
-    s.m.rep4 = rep4;
-    s.m.active = mv.active;
-    s.m.first_arm = first_arm;
-    s.m.n_arms = n_arms;
-    s.m.n_rep = rep4 ? mv.n_rep : 0;
-    s.m.S = h->max_slots;
-    s.m.Bpad = h->Bpad;
+    s.m = move_args(h, first_arm, n_arms, mv.goal16, rep4, rep4 ? mv.n_rep : 0, mv.active);
     s.aux = h->d_funnel;
     s.scenemap = h->d_scenemap;
     s.n_fun = s.fun6 ? mv.n_fun : 0;
@@ -1021,11 +1033,11 @@ int vfik_move_scene_host(vfik_handle* h, int first_arm, int n_arms, const vfik_s
     for (int c = 0; c < 5; ++c)
         for (size_t k = off[c]; k < off[c + 1]; ++k) {
             const double v = src[c][k - off[c]];
-            if (h->io_dtype == 32) put<float>(buf, k, v); else put<double>(buf, k, v);
+            put_io(h, buf, k, v);
         }
-    if (move_stage_reserve(h, buf.size()) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipMemcpyAsync(h->d_move_stage, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
-    char* d = static_cast<char*>(h->d_move_stage);
+    if (reserve(h, h->move_stage, buf.size(), true, true) != VFIK_OK) return VFIK_E_HIP;
+    char* d = static_cast<char*>(h->move_stage.p);
+    HIP_TRY(hipMemcpyAsync(d, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
     vfik_scene_move dv = *mv;
     dv.goal16 = src[0] ? d + off[0] * h->esz : nullptr;
     dv.rep4 = src[1] ? d + off[1] * h->esz : nullptr;
@@ -1042,12 +1054,12 @@ int vfik_set_speed_scale(vfik_handle* h, int first_arm, int n_arms, const double
     if (check_handle(h)) return VFIK_E_ARG;
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
     if (!values) return fail(VFIK_E_ARG, "null values");
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     for (int j = 0; j < n_arms; ++j)
         if (!(values[j] >= 0.0) || !std::isfinite(values[j])) return fail(VFIK_E_ARG, "arm %d: speedScale must be finite and >= 0", first_arm + j);
     HIP_TRY(hipSetDevice(h->device));
     std::vector<char> buf((size_t)n_arms * h->esz);
-    for (int j = 0; j < n_arms; ++j) { if (h->io_dtype == 32) put<float>(buf, j, values[j]); else put<double>(buf, j, values[j]); }
+    for (int j = 0; j < n_arms; ++j) put_io(h, buf, j, values[j]);
     const size_t qb = 4 * h->esz;
     char* dst = static_cast<char*>(h->d_goal) + 3 * (size_t)h->Bpad * qb + (size_t)first_arm * qb + 3 * h->esz;
     HIP_TRY(hipMemcpy2DAsync(dst, qb, buf.data(), h->esz, h->esz, n_arms, hipMemcpyHostToDevice, h->stream));
@@ -1077,7 +1089,7 @@ static int upload_bridge_state(vfik_handle* h, int first_arm, int n_arms) {
         for (int k = 0; k < 8; ++k) {
             const size_t idx = ((size_t)(k >> 2) * n_arms + j) * 4 + (k & 3);
             const double v = h->bridge_host[(size_t)(first_arm + j) * 8 + k];
-            if (h->io_dtype == 32) put<float>(buf, idx, v); else put<double>(buf, idx, v);
+            put_io(h, buf, idx, v);
         }
     char* dst = static_cast<char*>(h->d_mixw_arm) + (size_t)first_arm * qb;
     HIP_TRY(hipMemcpy2DAsync(dst, plane, buf.data(), (size_t)n_arms * qb, (size_t)n_arms * qb, 2, hipMemcpyHostToDevice, h->stream));
@@ -1103,7 +1115,7 @@ int vfik_set_mixer_weights(vfik_handle* h, int first_arm, int n_arms, const doub
             for (int k = 0; k < VFIK_MIX_CHANNELS; ++k) h->bridge_host[(size_t)b * 8 + k] = h->params.mix_w[k];
         return upload_bridge_state(h, 0, h->B);
     }
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (ensure_bridge_state(h) != VFIK_OK) return VFIK_E_HIP;
     for (int j = 0; j < n_arms; ++j)
         for (int k = 0; k < VFIK_MIX_CHANNELS; ++k) h->bridge_host[(size_t)(first_arm + j) * 8 + k] = w[(size_t)j * VFIK_MIX_CHANNELS + k];
@@ -1114,7 +1126,7 @@ int vfik_set_max_vel(vfik_handle* h, int first_arm, int n_arms, const double* va
     if (check_handle(h)) return VFIK_E_ARG;
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
     if (!values) return fail(VFIK_E_ARG, "null values");
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     for (int j = 0; j < n_arms; ++j)
         if (!(values[j] >= 0.0) || !std::isfinite(values[j])) return fail(VFIK_E_ARG, "arm %d: max_vel %g must be finite and >= 0", first_arm + j, values[j]);
     HIP_TRY(hipSetDevice(h->device));
@@ -1183,10 +1195,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
         // aligned the last piece could reach into the next page.  Such a q is staged through an aligned buffer of the handle.
         const size_t qbytes = (size_t)h->B * h->n * h->esz;
         if (!h->d_qalign) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return fail(VFIK_E_STATE, "io->q is not 16-byte aligned: its staging buffer is allocated at the first such call -- make one before capturing the stream");
-            (void)hipGetLastError();
+            if (refuse_capture(stream, "io->q is not 16-byte aligned: its staging buffer is allocated at the first such call -- make one before capturing the stream")) return VFIK_E_STATE;
             if (dev_alloc(h, &h->d_qalign, (qbytes + 15) / 16 * 16, false)) return VFIK_E_HIP;
         }
         HIP_TRY(hipMemcpyAsync(h->d_qalign, io->q, qbytes, hipMemcpyDefault, stream));
@@ -1234,12 +1243,9 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
         if (want_dist && (!h->d_objects || h->n_objects < 1)) return fail(VFIK_E_STATE, "io->obj_dist needs vfik_set_objects");
         // the observers' buffers are allocated at the first request: never under stream capture (an allocation there would be part of
         // the captured work or fail it) -- a caller that captures vfik_step with observers makes one such call outside the capture first
-        if ((!a.pose && !h->d_obs_pose) || (want_track && ((!a.v6 && !h->d_obs_v6) || !h->d_track))) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return fail(VFIK_E_STATE, "io->track_error / io->obj_dist: the observers' device buffers are allocated at the first request -- make one such vfik_step call before capturing the stream");
-            (void)hipGetLastError();
-        }
+        if (((!a.pose && !h->d_obs_pose) || (want_track && ((!a.v6 && !h->d_obs_v6) || !h->d_track))) &&
+            refuse_capture(stream, "io->track_error / io->obj_dist: the observers' device buffers are allocated at the first request -- make one such vfik_step call before capturing the stream"))
+            return VFIK_E_STATE;
         if (!a.pose) {
             if (!h->d_obs_pose && dev_alloc(h, &h->d_obs_pose, (size_t)h->B * 16 * h->esz, true)) return VFIK_E_HIP;
             a.pose = h->d_obs_pose;
@@ -1281,32 +1287,30 @@ int vfik_sync(vfik_handle* h) {
     return VFIK_OK;
 }
 
-// host-pointer forms: which vfik_io members are inputs / outputs, and their sizes in bytes
+// ---- host-pointer forms: the staging of a call's members (vfik_io_layout.h) between the caller's arrays and the device ----
 namespace {
-constexpr int N_HIN = 7, N_HOUT = 13;
-struct HostIo {
-    const void* hin[N_HIN];
-    size_t bin[N_HIN];
-    void* hout[N_HOUT];
-    size_t bout[N_HOUT];
-};
-HostIo host_io(const vfik_handle* h, const vfik_io* io, void* q_out_host) {
-    const size_t B = h->B, n = h->n, e = h->esz;
-    HostIo x{{io->q, io->null_control, io->q_ref, io->q_cmded, io->active, io->q_lo, io->q_hi},
-             {B * n * e, B * VFIK_NULL_CONTROLS * e, B * n * e, B * n * e, B * sizeof(int32_t), B * n * e, B * n * e},
-             {io->qdot_vf, io->qdot_null, io->qdot_out, io->pose, io->pose_nt, io->v6, io->qdist, io->status, q_out_host, io->goal_dist,
-              io->q_ref ? io->q_ref_out : nullptr, io->track_error, io->obj_dist},
-             {B * n * e, B * n * e, B * n * e, B * 16 * e, B * 16 * e, B * 6 * e, B * n * e, B * sizeof(int32_t), B * n * e, B * 2 * e, B * n * e,
-              B * 8 * e, B * (size_t)(h->n_objects > 0 ? h->n_objects : 1) * 2 * e}};
-    return x;
+using vfik::IoStaging;
+
+// every member in a device buffer of its own, grown on demand (sc[vfik::N_STAGED]); only the inputs: the outputs stay where they point
+int map_buffers(vfik_handle* h, IoStaging& st, vfik_handle::DevBuf* sc, bool inputs_only, const char* what) {
+    for (int i = 0; i < vfik::N_STAGED; ++i) {
+        IoStaging::Member& m = st.m[i];
+        if (!m.present || (inputs_only && !m.input)) continue;
+        if (reserve(h, sc[i], m.bytes, false, false)) return fail(VFIK_E_HIP, "%s allocation failed", what);
+        m.dev = sc[i].p;
+    }
+    return VFIK_OK;
 }
-void device_io(void* const* din, void* const* dout, vfik_io& d) {
-    d = vfik_io{};
-    d.q = din[0]; d.null_control = din[1]; d.q_ref = din[2]; d.q_cmded = din[3];
-    d.active = static_cast<const int32_t*>(din[4]); d.q_lo = din[5]; d.q_hi = din[6];
-    d.qdot_vf = dout[0]; d.qdot_null = dout[1]; d.qdot_out = dout[2]; d.pose = dout[3]; d.pose_nt = dout[4];
-    d.v6 = dout[5]; d.qdist = dout[6]; d.status = static_cast<int32_t*>(dout[7]); d.goal_dist = dout[9]; d.q_ref_out = dout[10];
-    d.track_error = dout[11]; d.obj_dist = dout[12];
+
+// The three copies of a staged call, one hipMemcpyAsync per member.  Gated arms store nothing: under a gate (io->active) the caller's
+// output rows go in before the launch, so that theirs come back as they went in -- the outputs that every arm writes excepted
+// (IoStaging::Member::gated).
+int copy_members(IoStaging& st, IoStaging::Which which, hipStream_t stream) {
+    return st.each(which, [&](IoStaging::Member& m) {
+        if (which == IoStaging::OUTPUTS) HIP_TRY(hipMemcpyAsync(m.host, m.dev, m.bytes, hipMemcpyDeviceToHost, stream));
+        else HIP_TRY(hipMemcpyAsync(m.dev, m.host, m.bytes, hipMemcpyHostToDevice, stream));
+        return (int)VFIK_OK;
+    });
 }
 }  // namespace
 
@@ -1319,50 +1323,25 @@ static int cycles_host(vfik_handle* h, const vfik_io* io, int n_cycles, double d
     if (check_handle(h)) return VFIK_E_ARG;
     if (!io || !io->q) return fail(VFIK_E_ARG, "a control cycle needs io->q");
     HIP_TRY(hipSetDevice(h->device));
-    const HostIo x = host_io(h, io, q_out_host);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off_in[N_HIN], off_out[N_HOUT], total = 0;
-    for (int i = 0; i < N_HIN; ++i) { off_in[i] = total; if (x.hin[i]) total += up(x.bin[i]); }
-    const size_t in_bytes = total;
-    for (int i = 0; i < N_HOUT; ++i) { off_out[i] = total; if (x.hout[i]) total += up(x.bout[i]); }
-    int members = 0;
-    for (int i = 0; i < N_HIN; ++i) members += x.hin[i] != nullptr;
-    for (int i = 0; i < N_HOUT; ++i) members += x.hout[i] != nullptr;
+    IoStaging st(*io, h->B, h->io_dims());
+    st.add(vfik::X_Q_OUT, q_out_host, (size_t)h->B * h->n * h->esz, true);   // (a gated arm's q is not integrated)
+    st.layout();
+    const size_t total = st.total, in_bytes = st.in_bytes;
+    auto launch = [&]() {
+        const vfik_io d = st.device_io();
+        return n_cycles > 0 ? vfik_rollout(h, &d, n_cycles, dt, clamp, st.extra(vfik::X_Q_OUT).dev) : vfik_step(h, &d);
+    };
     // The arena saves ~15 us per member beyond two and costs a host memcpy of every byte (~38 GB/s): measured 197 -> 40 us for
     // one arm with 13 members, 306 -> 190 us for 4 096 arms (2 MB), but 142 -> 236 us for a C3 step (q and qdot_out, 3.6 MB).
-    if (total > ((size_t)256 << 10) && total > (size_t)std::max(0, members - 2) * ((size_t)512 << 10)) {
+    if (total > ((size_t)256 << 10) && total > (size_t)std::max(0, st.members - 2) * ((size_t)512 << 10)) {
         // Few large members: the copies are bandwidth, not count -- every member straight between the caller's array and its
         // own device buffer.
-        auto need = [&](int i, size_t bytes) -> void* {
-            auto& sc = h->sc[i];
-            if (sc.bytes < bytes) {
-                if (sc.p) (void)hipFree(sc.p);
-                sc.p = nullptr; sc.bytes = 0;
-                if (hipMalloc(&sc.p, bytes) != hipSuccess) return nullptr;
-                sc.bytes = bytes;
-            }
-            return sc.p;
-        };
-        void* din[N_HIN] = {};
-        for (int i = 0; i < N_HIN; ++i)
-            if (x.hin[i]) {
-                din[i] = need(i, x.bin[i]);
-                if (!din[i]) return fail(VFIK_E_HIP, "scratch allocation failed");
-                HIP_TRY(hipMemcpyAsync(din[i], x.hin[i], x.bin[i], hipMemcpyHostToDevice, h->stream));
-            }
-        void* dout[N_HOUT];
-        for (int i = 0; i < N_HOUT; ++i) {
-            dout[i] = x.hout[i] ? need(N_HIN + i, x.bout[i]) : nullptr;
-            if (x.hout[i] && !dout[i]) return fail(VFIK_E_HIP, "scratch allocation failed");
-            // gated arms store nothing: their rows of the caller's arrays must come back as they went in
-            if (x.hout[i] && io->active) HIP_TRY(hipMemcpyAsync(dout[i], x.hout[i], x.bout[i], hipMemcpyHostToDevice, h->stream));
-        }
-        vfik_io d;
-        device_io(din, dout, d);
-        const int rc = n_cycles > 0 ? vfik_rollout(h, &d, n_cycles, dt, clamp, dout[8]) : vfik_step(h, &d);
+        int rc = map_buffers(h, st, h->sc, false, "scratch");
+        if (rc == VFIK_OK) rc = copy_members(st, IoStaging::INPUTS, h->stream);
+        if (rc == VFIK_OK && io->active) rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream);
+        if (rc == VFIK_OK) rc = launch();
+        if (rc == VFIK_OK) rc = copy_members(st, IoStaging::OUTPUTS, h->stream);
         if (rc != VFIK_OK) return rc;
-        for (int i = 0; i < N_HOUT; ++i)
-            if (x.hout[i]) HIP_TRY(hipMemcpyAsync(x.hout[i], dout[i], x.bout[i], hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         return VFIK_OK;
     }
@@ -1384,26 +1363,17 @@ static int cycles_host(vfik_handle* h, const vfik_io* io, int n_cycles, double d
     // kernel's few PCIe transactions (ccb_rate: one arm, qdot_out only 23 -> 17 us; profiles/r03_ccb_rate.txt).
     const bool zero_copy = total <= h->zero_copy_max && h->arena_host_dev;
     char* const devA = zero_copy ? static_cast<char*>(h->arena_host_dev) : static_cast<char*>(h->arena_dev);
-    void* din[N_HIN] = {};
-    void* dout[N_HOUT] = {};
-    for (int i = 0; i < N_HIN; ++i)
-        if (x.hin[i]) { std::memcpy(hostA + off_in[i], x.hin[i], x.bin[i]); din[i] = devA + off_in[i]; }
-    size_t h2d = in_bytes;
-    for (int i = 0; i < N_HOUT; ++i)
-        if (x.hout[i]) {
-            dout[i] = devA + off_out[i];
-            // gated arms store nothing: their rows of the caller's arrays must come back as they went in
-            if (io->active) { std::memcpy(hostA + off_out[i], x.hout[i], x.bout[i]); h2d = total; }
-        }
+    st.map(devA);
+    auto pack = [&](IoStaging::Member& m) { std::memcpy(hostA + m.off, m.host, m.bytes); return 0; };
+    st.each(IoStaging::INPUTS, pack);
+    size_t h2d = in_bytes;   // without a gate the input prefix alone goes to the device, with one the whole arena
+    if (io->active && total > in_bytes) { st.each(IoStaging::GATED_OUTPUTS, pack); h2d = total; }
     if (!zero_copy) HIP_TRY(hipMemcpyAsync(devA, hostA, h2d, hipMemcpyHostToDevice, h->stream));
-    vfik_io d;
-    device_io(din, dout, d);
-    const int rc = n_cycles > 0 ? vfik_rollout(h, &d, n_cycles, dt, clamp, dout[8]) : vfik_step(h, &d);
+    const int rc = launch();
     if (rc != VFIK_OK) return rc;
     if (!zero_copy && total > in_bytes) HIP_TRY(hipMemcpyAsync(hostA + in_bytes, devA + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < N_HOUT; ++i)
-        if (x.hout[i]) std::memcpy(x.hout[i], hostA + off_out[i], x.bout[i]);
+    st.each(IoStaging::OUTPUTS, [&](IoStaging::Member& m) { std::memcpy(m.host, hostA + m.off, m.bytes); return 0; });
     return VFIK_OK;
 }
 
@@ -1453,30 +1423,24 @@ int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoR
     r.qrow = (size_t)h->B * h->n * h->esz;
     r.drow = (size_t)h->B * 2 * h->esz;
     r.gated = o->hold || io->active;
-    const bool need_pending = !o->pending && h->goto_pending_cap < r.n_checks;
+    const bool need_pending = !o->pending && h->goto_pending.bytes < (size_t)r.n_checks * sizeof(int);
     const bool need_dist = !o->dist_traj && !io->goal_dist && !h->d_goto_dist;
     const bool need_q = !o->q_traj && !h->d_gotoq[0];
     // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
     const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
                        (o->q_traj && r.n_checks > 1 && (reinterpret_cast<uintptr_t>(o->q_traj) % 16 || r.qrow % 16));
     if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign)) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return fail(VFIK_E_STATE, "vfik_goto: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such vfik_goto call before capturing the stream");
-        (void)hipGetLastError();
+        if (refuse_capture(h->stream, "vfik_goto: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such vfik_goto call before capturing the stream"))
+            return VFIK_E_STATE;
         if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
-        if (need_pending) {
-            HIP_TRY(hipStreamSynchronize(h->stream));   // (an earlier goto may still count into the smaller array)
-            if (h->d_goto_pending) { (void)hipFree(h->d_goto_pending); h->dev_bytes -= (size_t)h->goto_pending_cap * sizeof(int); h->d_goto_pending = nullptr; h->goto_pending_cap = 0; }
-            if (dev_alloc(h, (void**)&h->d_goto_pending, (size_t)r.n_checks * sizeof(int), false)) return VFIK_E_HIP;
-            h->goto_pending_cap = r.n_checks;
-        }
+        // (synchronised: an earlier goto may still count into the smaller array)
+        if (need_pending && reserve(h, h->goto_pending, (size_t)r.n_checks * sizeof(int), true, true)) return VFIK_E_HIP;
         if (need_dist && dev_alloc(h, &h->d_goto_dist, r.drow, false)) return VFIK_E_HIP;
         for (int k = 0; need_q && k < 2; ++k)
             if (!h->d_gotoq[k] && dev_alloc(h, &h->d_gotoq[k], (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
         if (odd_q && !h->d_qalign && dev_alloc(h, &h->d_qalign, (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
     }
-    r.pending = o->pending ? o->pending : h->d_goto_pending;
+    r.pending = o->pending ? o->pending : static_cast<int32_t*>(h->goto_pending.p);
     HIP_TRY(hipMemsetAsync(r.pending, 0, (size_t)r.n_checks * sizeof(int), h->stream));
     vfik::ArriveArgs g{};
     g.arrived = o->arrived;
@@ -1553,47 +1517,27 @@ int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, i
     if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
     HIP_TRY(hipSetDevice(h->device));
     const int n_checks = o->n_cycles / o->stride;
-    const HostIo x = host_io(h, io, o->q_out);
     const size_t qrow = (size_t)h->B * h->n * h->esz, drow = (size_t)h->B * 2 * h->esz;
-    // beside io's members: arrived, pending (always: the early exit reads it), the two traces
-    void* const hx[4] = {o->arrived, o->pending, o->q_traj, o->dist_traj};
-    const size_t bx[4] = {(size_t)h->B * sizeof(int32_t), (size_t)n_checks * sizeof(int32_t), (size_t)n_checks * qrow, (size_t)n_checks * drow};
-    const size_t per_check[4] = {0, sizeof(int32_t), qrow, drow};
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off_in[N_HIN], off_out[N_HOUT], off_x[4], total = 0;
-    for (int i = 0; i < N_HIN; ++i) { off_in[i] = total; if (x.hin[i]) total += up(x.bin[i]); }
-    for (int i = 0; i < N_HOUT; ++i) { off_out[i] = total; if (x.hout[i]) total += up(x.bout[i]); }
-    for (int i = 0; i < 4; ++i) { off_x[i] = total; if (hx[i] || i == 1) total += up(bx[i]); }
-    if (h->goto_stage_bytes < total) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_goto_stage) { (void)hipFree(h->d_goto_stage); h->dev_bytes -= h->goto_stage_bytes; h->d_goto_stage = nullptr; h->goto_stage_bytes = 0; }
-        if (dev_alloc(h, &h->d_goto_stage, total, false)) return VFIK_E_HIP;
-        h->goto_stage_bytes = total;
-    }
-    char* const dev = static_cast<char*>(h->d_goto_stage);
-    void* din[N_HIN] = {};
-    void* dout[N_HOUT] = {};
-    for (int i = 0; i < N_HIN; ++i)
-        if (x.hin[i]) {
-            din[i] = dev + off_in[i];
-            HIP_TRY(hipMemcpyAsync(din[i], x.hin[i], x.bin[i], hipMemcpyHostToDevice, h->stream));
-        }
-    for (int i = 0; i < N_HOUT; ++i)
-        if (x.hout[i]) {
-            dout[i] = dev + off_out[i];
-            // arms the gate keeps out store nothing: their rows of the caller's arrays must come back as they went in
-            if (io->active && i != 8) HIP_TRY(hipMemcpyAsync(dout[i], x.hout[i], x.bout[i], hipMemcpyHostToDevice, h->stream));
-        }
-    // (a gated arm's rows of the distance trace are never written either; its q rows are: they repeat its start)
-    if (io->active && o->dist_traj) HIP_TRY(hipMemcpyAsync(dev + off_x[3], o->dist_traj, bx[3], hipMemcpyHostToDevice, h->stream));
-    vfik_io d;
-    device_io(din, dout, d);
+    IoStaging st(*io, h->B, h->io_dims());
+    // beside io's members.  Under a gate: q_out is written for every arm (goto_end), a gated arm's rows of the distance trace never, its q
+    // rows always (they repeat its start).  pending is staged without an array of the caller's too: the early exit reads it.
+    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
+    st.add(vfik::X_ARRIVED, o->arrived, (size_t)h->B * sizeof(int32_t), false);
+    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
+    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
+    st.add(vfik::X_DIST_TRAJ, o->dist_traj, (size_t)n_checks * drow, true);
+    st.layout();
+    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
+    st.map(h->goto_stage.p);
+    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
+    if (io->active && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    const vfik_io d = st.device_io();
     vfik_goto_opts od = *o;
-    od.arrived = reinterpret_cast<int32_t*>(dev + off_x[0]);
-    od.pending = reinterpret_cast<int32_t*>(dev + off_x[1]);
-    od.q_out = dout[8];
-    od.q_traj = o->q_traj ? dev + off_x[2] : nullptr;
-    od.dist_traj = o->dist_traj ? dev + off_x[3] : nullptr;
+    od.arrived = static_cast<int32_t*>(st.extra(vfik::X_ARRIVED).dev);
+    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
+    od.q_out = st.extra(vfik::X_Q_OUT).dev;
+    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
+    od.dist_traj = st.extra(vfik::X_DIST_TRAJ).dev;
     GotoRun r;
     if ((rc = goto_begin(h, &d, &od, r)) != VFIK_OK) return rc;
     int done = 0;
@@ -1608,10 +1552,11 @@ int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, i
         }
     }
     if ((rc = goto_end(h, r, done)) != VFIK_OK) return rc;
-    for (int i = 0; i < N_HOUT; ++i)
-        if (x.hout[i]) HIP_TRY(hipMemcpyAsync(x.hout[i], dout[i], x.bout[i], hipMemcpyDeviceToHost, h->stream));
-    for (int i = 0; i < 4; ++i)
-        if (hx[i]) HIP_TRY(hipMemcpyAsync(hx[i], dev + off_x[i], i == 0 ? bx[0] : (size_t)done * per_check[i], hipMemcpyDeviceToHost, h->stream));
+    IoStaging back = st;   // what goes back: of pending and the traces the checks that ran (st keeps the sizes its layout was made of)
+    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
+    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
+    back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
+    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (checks_run) *checks_run = done;
     return VFIK_OK;
@@ -1665,42 +1610,25 @@ int vfik_submit_host(vfik_handle* h, const vfik_io* io, long* ticket) {
         HIP_TRY(hipEventSynchronize(ps.ev_out));
         ps.ticket = -1;
     }
-    const HostIo x = host_io(h, io, nullptr);
-    auto need = [&](int i, size_t bytes) -> void* {
-        auto& sc = ps.sc[i];
-        if (sc.bytes < bytes) {
-            if (sc.p) (void)hipFree(sc.p);
-            sc.p = nullptr; sc.bytes = 0;
-            if (hipMalloc(&sc.p, bytes) != hipSuccess) return nullptr;
-            sc.bytes = bytes;
-        }
-        return sc.p;
-    };
+    IoStaging st(*io, h->B, h->io_dims());
     // Zero-copy: when every buffer is pinned (device-visible) host memory the kernel writes qdot across
     // PCIe itself, and reads q the same way when nothing else is in flight (lowest latency: 83 us per C3
     // step, 1.8 MB each way).  While an earlier submission is still running, the inputs go through the
     // copy engine instead, which overlaps that kernel: 56 us per step at 2-3 in flight, against 66 us for
     // reads by the kernel and 95 us for the three-stream staging below.
     bool direct = true;
-    for (int i = 0; i < N_HIN && direct; ++i) direct = !x.hin[i] || gpu_visible(x.hin[i]);
-    for (int i = 0; i < N_HOUT && direct; ++i) direct = !x.hout[i] || gpu_visible(x.hout[i]);
+    for (const IoStaging::Member& m : st.m) direct = direct && (!m.present || gpu_visible(m.host));
     if (direct) {
         bool busy = false;
         for (auto& o : h->pipe)
             if (o.ticket >= 0 && hipEventQuery(o.ev_out) == hipErrorNotReady) busy = true;
         (void)hipGetLastError();
         vfik_io d = *io;
-        if (busy) {
-            void* din[N_HIN] = {};
-            for (int i = 0; i < N_HIN; ++i)
-                if (x.hin[i]) {
-                    void* dp = need(i, x.bin[i]);
-                    if (!dp) return fail(VFIK_E_HIP, "staging allocation failed");
-                    HIP_TRY(hipMemcpyAsync(dp, x.hin[i], x.bin[i], hipMemcpyHostToDevice, h->s_in));
-                    din[i] = dp;
-                }
-            d.q = din[0]; d.null_control = din[1]; d.q_ref = din[2]; d.q_cmded = din[3];
-            d.active = static_cast<const int32_t*>(din[4]); d.q_lo = din[5]; d.q_hi = din[6];
+        if (busy) {   // the inputs alone are staged; the outputs stay the caller's pinned arrays
+            int rc = map_buffers(h, st, ps.sc, true, "staging");
+            if (rc == VFIK_OK) rc = copy_members(st, IoStaging::INPUTS, h->s_in);
+            if (rc != VFIK_OK) return rc;
+            d = st.device_io(io);
             HIP_TRY(hipEventRecord(ps.ev_in, h->s_in));
             HIP_TRY(hipStreamWaitEvent(h->stream, ps.ev_in, 0));
         }
@@ -1711,29 +1639,17 @@ int vfik_submit_host(vfik_handle* h, const vfik_io* io, long* ticket) {
         *ticket = h->next_ticket++;
         return VFIK_OK;
     }
-    void* din[N_HIN] = {};
-    void* dout[N_HOUT];
-    for (int i = 0; i < N_HIN; ++i)
-        if (x.hin[i] && !(din[i] = need(i, x.bin[i]))) return fail(VFIK_E_HIP, "staging allocation failed");
-    for (int i = 0; i < N_HOUT; ++i) {
-        dout[i] = x.hout[i] ? need(N_HIN + i, x.bout[i]) : nullptr;
-        if (x.hout[i] && !dout[i]) return fail(VFIK_E_HIP, "staging allocation failed");
-    }
-    for (int i = 0; i < N_HIN; ++i)
-        if (x.hin[i]) HIP_TRY(hipMemcpyAsync(din[i], x.hin[i], x.bin[i], hipMemcpyHostToDevice, h->s_in));
-    if (io->active)  // gated arms store nothing: their rows must come back as they went in
-        for (int i = 0; i < N_HOUT; ++i)
-            if (x.hout[i]) HIP_TRY(hipMemcpyAsync(dout[i], x.hout[i], x.bout[i], hipMemcpyHostToDevice, h->s_in));
+    int rc = map_buffers(h, st, ps.sc, false, "staging");
+    if (rc == VFIK_OK) rc = copy_members(st, IoStaging::INPUTS, h->s_in);
+    if (rc == VFIK_OK && io->active) rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->s_in);
+    if (rc != VFIK_OK) return rc;
     HIP_TRY(hipEventRecord(ps.ev_in, h->s_in));
     HIP_TRY(hipStreamWaitEvent(h->stream, ps.ev_in, 0));
-    vfik_io d;
-    device_io(din, dout, d);
-    const int rc = vfik_step(h, &d);
-    if (rc != VFIK_OK) return rc;
+    const vfik_io d = st.device_io();
+    if ((rc = vfik_step(h, &d)) != VFIK_OK) return rc;
     HIP_TRY(hipEventRecord(ps.ev_k, h->stream));
     HIP_TRY(hipStreamWaitEvent(h->s_out, ps.ev_k, 0));
-    for (int i = 0; i < N_HOUT; ++i)
-        if (x.hout[i]) HIP_TRY(hipMemcpyAsync(x.hout[i], dout[i], x.bout[i], hipMemcpyDeviceToHost, h->s_out));
+    if ((rc = copy_members(st, IoStaging::OUTPUTS, h->s_out)) != VFIK_OK) return rc;
     HIP_TRY(hipEventRecord(ps.ev_out, h->s_out));
     ps.ticket = h->next_ticket;
     *ticket = h->next_ticket++;
@@ -1783,7 +1699,7 @@ int vfik_set_objects(vfik_handle* h, int first_arm, int n_arms, const double* fr
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
     if (!frames) return fail(VFIK_E_ARG, "null frames");
     if (n_objects < 1 || n_objects > 4096) return fail(VFIK_E_ARG, "n_objects %d outside [1, 4096]", n_objects);
-    if (first_arm < 0 || n_arms < 1 || first_arm + n_arms > h->B) return fail(VFIK_E_ARG, "arm range [%d, %d) outside batch %d", first_arm, first_arm + n_arms, h->B);
+    if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     if (n_objects != h->n_objects && (first_arm != 0 || n_arms != h->B))
         return fail(VFIK_E_ARG, "n_objects changes from %d to %d: the call must cover every arm", h->n_objects, n_objects);
     const size_t count = (size_t)n_arms * n_objects * 16;
@@ -1797,7 +1713,7 @@ int vfik_set_objects(vfik_handle* h, int first_arm, int n_arms, const double* fr
         h->n_objects = n_objects;
     }
     std::vector<char> buf(count * h->esz);
-    for (size_t k = 0; k < count; ++k) { if (h->io_dtype == 32) put<float>(buf, k, frames[k]); else put<double>(buf, k, frames[k]); }
+    for (size_t k = 0; k < count; ++k) put_io(h, buf, k, frames[k]);
     char* dst = static_cast<char*>(h->d_objects) + (size_t)first_arm * n_objects * 16 * h->esz;
     HIP_TRY(hipMemcpyAsync(dst, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

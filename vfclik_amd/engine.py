@@ -26,6 +26,9 @@ class IO(C.Structure):
                 ("track_error", C.c_void_p), ("obj_dist", C.c_void_p)]
 
 
+# columns of the members of IO as (batch, columns) arrays of the engine's dtype ("n": the chain's joints); active and status are int32
+# (batch,), obj_dist is (batch, n_objects, 2): Engine._make_specs
+_IN_SHAPES = {"q": "n", "null_control": _abi.NULL_CONTROLS, "q_ref": "n", "q_cmded": "n", "q_lo": "n", "q_hi": "n"}
 _OUT_SHAPES = {"qdot_vf": "n", "qdot_null": "n", "qdot_out": "n", "pose": 16, "pose_nt": 16, "v6": 6, "qdist": "n",
                "goal_dist": 2, "q_ref_out": "n", "track_error": 8}
 _lib = None
@@ -162,6 +165,7 @@ class Engine:
         self._chk(self.lib.vfik_set_params(self.h, C.byref(self.params)))
         self._torch_out = {}
         self.n_objects = 0  # object frames of the distance monitor held by the handle (set_objects)
+        self._make_specs()
 
     # -- plumbing -------------------------------------------------------------------------------
     def _chk(self, rc):
@@ -351,6 +355,7 @@ class Engine:
             raise ValueError("frames must be (n_arms, n_objects, 16)")
         self._chk(self.lib.vfik_set_objects(self.h, int(first_arm), f.shape[0], f.ctypes.data, f.shape[1]))
         self.n_objects = f.shape[1]
+        self._make_specs()
 
     def set_mixer_weights(self, weights, first_arm=0):
         """Per-arm mixer weights (n_arms, 6); ``None`` returns to the batch-wide ``params.mix_w``."""
@@ -407,31 +412,52 @@ class Engine:
         return self.lib.vfik_device_bytes(self.h)
 
     # -- one control cycle -----------------------------------------------------------------------
-    def _shape(self, key):
-        if key == "obj_dist":  # [B][n_objects][2]: one /dmonitor/distOut entry per object frame of set_objects
-            if self.n_objects < 1:
-                raise VfikError("obj_dist needs set_objects first")
-            return (self.batch, self.n_objects, 2)
-        d = _OUT_SHAPES[key]
-        return (self.batch, self.n if d == "n" else d)
+    def _make_specs(self):
+        """(shape, dtype) of the host array of every member of IO, inputs and outputs apart: a name of the one table is no key of the other.
+        obj_dist [B][n_objects][2] -- one /dmonitor/distOut entry per object frame -- is in it once set_objects gave the count."""
+        def rows(d):
+            return (self.batch, self.n if d == "n" else d), self.io_dtype
+        i32 = ((self.batch,), np.dtype(np.int32))
+        self._in_specs = dict({k: rows(d) for k, d in _IN_SHAPES.items()}, active=i32)
+        self._out_specs = dict({k: rows(d) for k, d in _OUT_SHAPES.items()}, status=i32)
+        if self.n_objects >= 1:
+            self._out_specs["obj_dist"] = ((self.batch, self.n_objects, 2), self.io_dtype)
 
-    def _host_inputs(self, io, keep, active=None, q_lo=None, q_hi=None):
-        """The ABI-3 inputs of a host-array call: fresh-q gate and this cycle's per-arm joint limits."""
+    def _out_spec(self, key):
+        if key == "obj_dist" and self.n_objects < 1:
+            raise VfikError("obj_dist needs set_objects first")
+        return self._out_specs[key]
+
+    def _host_in(self, name, arr):
+        """An input of a host-array call as the library reads it: contiguous, of the member's dtype (active: 0 / 1), shape checked."""
+        shape, dtype = self._in_specs[name]
+        a = np.ascontiguousarray(np.asarray(arr) != 0 if name == "active" else arr, dtype=dtype)
+        if a.shape != shape:
+            raise ValueError("null_control must be (batch, 4)" if name == "null_control" else "%s must be %s, got %s" % (name, shape, a.shape))
+        return a
+
+    def _host_io(self, q, null_control=None, q_ref=None, q_cmded=None, active=None, q_lo=None, q_hi=None, want=(), into=None):
+        """The IO block of a host-array call (step_host, rollout_host, goto_host).  Returns (io, out, keep): ``out`` the output arrays named
+        in ``want`` -- those of ``into`` where it has them, zeros otherwise --, ``keep`` the converted inputs by name, which must stay
+        alive until the call returns."""
+        keep = {"q": self._host_in("q", q)}
         if (q_lo is None) != (q_hi is None):
             raise ValueError("q_lo and q_hi come together")
-        if active is not None:
-            a = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.int32)
-            if a.shape != (self.batch,):
-                raise ValueError("active must be (%d,), got %s" % (self.batch, a.shape))
-            io.active = a.ctypes.data
-            keep.append(a)
-        for name, arr in (("q_lo", q_lo), ("q_hi", q_hi)):
+        for name, arr in (("active", active), ("q_lo", q_lo), ("q_hi", q_hi), ("q_ref", q_ref), ("q_cmded", q_cmded), ("null_control", null_control)):
             if arr is not None:
-                a = np.ascontiguousarray(arr, dtype=self.io_dtype)
-                if a.shape != (self.batch, self.n):
-                    raise ValueError("%s must be (%d, %d), got %s" % (name, self.batch, self.n, a.shape))
-                setattr(io, name, a.ctypes.data)
-                keep.append(a)
+                keep[name] = self._host_in(name, arr)
+        io, out = IO(), {}
+        for name, a in keep.items():
+            setattr(io, name, a.ctypes.data)
+        for k in want:
+            shape, dtype = self._out_spec(k)
+            if into is not None and k in into:
+                out[k] = into[k]
+                self._check_host(k, out[k], shape, dtype)
+            else:
+                out[k] = np.zeros(shape, dtype=dtype)
+            setattr(io, k, out[k].ctypes.data)
+        return io, out, keep
 
     def step_host(self, q, null_control=None, want=("qdot_out",), q_ref=None, q_cmded=None, active=None, q_lo=None, q_hi=None,
                   into=None):
@@ -440,36 +466,7 @@ class Engine:
         active: fresh-q gate (B,) -- arms with 0 publish nothing and keep their state (vf:312-313); q_lo / q_hi:
         this cycle's joint limits per arm (nullspace:167).  `into`: a dict of arrays from an earlier call to write
         into (rows of gated arms then keep their previous content instead of zeros)."""
-        q = np.ascontiguousarray(q, dtype=self.io_dtype)
-        if q.shape != (self.batch, self.n):
-            raise ValueError("q must be (%d, %d), got %s" % (self.batch, self.n, q.shape))
-        io = IO()
-        io.q = q.ctypes.data
-        keep = [q]
-        self._host_inputs(io, keep, active, q_lo, q_hi)
-        for name, arr in (("q_ref", q_ref), ("q_cmded", q_cmded)):
-            if arr is not None:
-                a = np.ascontiguousarray(arr, dtype=self.io_dtype)
-                if a.shape != (self.batch, self.n):
-                    raise ValueError("%s must be (%d, %d), got %s" % (name, self.batch, self.n, a.shape))
-                setattr(io, name, a.ctypes.data)
-                keep.append(a)
-        if null_control is not None:
-            nc = np.ascontiguousarray(null_control, dtype=self.io_dtype)
-            if nc.shape != (self.batch, _abi.NULL_CONTROLS):
-                raise ValueError("null_control must be (batch, 4)")
-            io.null_control = nc.ctypes.data
-            keep.append(nc)
-        out = {}
-        for k in want:
-            if into is not None and k in into:
-                out[k] = into[k]
-                self._check_host(k, out[k], (self.batch,) if k == "status" else self._shape(k), np.int32 if k == "status" else self.io_dtype)
-            elif k == "status":
-                out[k] = np.zeros(self.batch, dtype=np.int32)
-            else:
-                out[k] = np.zeros(self._shape(k), dtype=self.io_dtype)
-            setattr(io, k, out[k].ctypes.data)
+        io, out, keep = self._host_io(q, null_control, q_ref, q_cmded, active, q_lo, q_hi, want, into)
         self._chk(self.lib.vfik_step_host(self.h, C.byref(io)))
         return out
 
@@ -492,22 +489,18 @@ class Engine:
         :meth:`wait` -- use :meth:`host_array` (pinned memory) for overlap: copies from / to pageable memory make the
         call synchronous.  Returns the ticket."""
         io = IO()
-        for name, arr, cols in (("q", q, self.n), ("null_control", null_control, _abi.NULL_CONTROLS), ("q_ref", q_ref, self.n),
-                                ("q_cmded", q_cmded, self.n), ("q_lo", q_lo, self.n), ("q_hi", q_hi, self.n)):
-            if arr is None:
-                continue
-            self._check_host(name, arr, (self.batch, cols), self.io_dtype)
+        # (the caller's arrays as they are: checked, never converted)
+        given = [("q", q), ("null_control", null_control), ("q_ref", q_ref), ("q_cmded", q_cmded), ("q_lo", q_lo), ("q_hi", q_hi)]
+        for name, arr in [(k, a) for k, a in given if a is not None]:
+            self._check_host(name, arr, *self._in_specs[name])
             setattr(io, name, arr.ctypes.data)
         if (q_lo is None) != (q_hi is None):
             raise ValueError("q_lo and q_hi come together")
         if active is not None:
-            self._check_host("active", active, (self.batch,), np.int32)
+            self._check_host("active", active, *self._in_specs["active"])
             io.active = active.ctypes.data
         for k, arr in outs.items():
-            if k == "status":
-                self._check_host(k, arr, (self.batch,), np.int32)
-            else:
-                self._check_host(k, arr, self._shape(k), self.io_dtype)
+            self._check_host(k, arr, *self._out_spec(k))
             setattr(io, k, arr.ctypes.data)
         t = C.c_long(-1)
         self._chk(self.lib.vfik_submit_host(self.h, C.byref(io), C.byref(t)))
@@ -528,32 +521,8 @@ class Engine:
         nothing: their row of ``q`` comes back as it went in (a silent arm keeps its joint angles -- feeding the result into
         the next rollout is the normal closed-loop use), and their rows of the other outputs keep what ``into`` (a dict of
         arrays from an earlier call, as in :meth:`step_host`) held, zeros without it."""
-        q = np.ascontiguousarray(q, dtype=self.io_dtype)
-        if q.shape != (self.batch, self.n):
-            raise ValueError("q must be (%d, %d), got %s" % (self.batch, self.n, q.shape))
-        io = IO()
-        io.q = q.ctypes.data
-        keep = [q]
-        self._host_inputs(io, keep, active, q_lo, q_hi)
-        if q_ref is not None:
-            a = np.ascontiguousarray(q_ref, dtype=self.io_dtype)
-            if a.shape != (self.batch, self.n):
-                raise ValueError("q_ref must be (%d, %d), got %s" % (self.batch, self.n, a.shape))
-            io.q_ref = a.ctypes.data
-            keep.append(a)
-        if null_control is not None:
-            nc = np.ascontiguousarray(null_control, dtype=self.io_dtype)
-            io.null_control = nc.ctypes.data
-            keep.append(nc)
-        out = {}
-        for k in want:
-            if into is not None and k in into:
-                out[k] = into[k]
-                self._check_host(k, out[k], (self.batch,) if k == "status" else self._shape(k), np.int32 if k == "status" else self.io_dtype)
-            else:
-                out[k] = np.zeros(self.batch, dtype=np.int32) if k == "status" else np.zeros(self._shape(k), dtype=self.io_dtype)
-            setattr(io, k, out[k].ctypes.data)
-        out["q"] = q.copy()  # gated arms keep their angles (the kernel stores nothing for them)
+        io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want, into)
+        out["q"] = keep["q"].copy()  # gated arms keep their angles (the kernel stores nothing for them)
         self._chk(self.lib.vfik_rollout_host(self.h, C.byref(io), int(n_cycles), float(dt), 1 if clamp else 0, out["q"].ctypes.data))
         return out
 
@@ -602,32 +571,10 @@ class Engine:
         arm's: those of its last evaluated cycle) and, with ``trajectory``, ``q_traj`` (checks_run, B, n) and ``dist_traj``
         (checks_run, B, 2).  ``poll`` > 0: after every ``poll`` checks the count of arms still under way is read back and the goto ends
         once it is 0 -- ``checks_run`` then tells how far it went.  Arms gated off by ``active`` never run and never arrive."""
-        q = np.ascontiguousarray(q, dtype=self.io_dtype)
-        if q.shape != (self.batch, self.n):
-            raise ValueError("q must be (%d, %d), got %s" % (self.batch, self.n, q.shape))
-        io = IO()
-        io.q = q.ctypes.data
-        keep = [q]
-        self._host_inputs(io, keep, active, q_lo, q_hi)
-        if q_ref is not None:
-            a = np.ascontiguousarray(q_ref, dtype=self.io_dtype)
-            if a.shape != (self.batch, self.n):
-                raise ValueError("q_ref must be (%d, %d), got %s" % (self.batch, self.n, a.shape))
-            io.q_ref = a.ctypes.data
-            keep.append(a)
-        if null_control is not None:
-            nc = np.ascontiguousarray(null_control, dtype=self.io_dtype)
-            if nc.shape != (self.batch, _abi.NULL_CONTROLS):
-                raise ValueError("null_control must be (batch, 4)")
-            io.null_control = nc.ctypes.data
-            keep.append(nc)
+        io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
         o = self._goto_opts(n_cycles, dt, precision, stride, hold, clamp)
         n_checks = max(o.n_cycles // max(o.stride, 1), 0)
-        out = {}
-        for k in want:
-            out[k] = np.zeros(self.batch, dtype=np.int32) if k == "status" else np.zeros(self._shape(k), dtype=self.io_dtype)
-            setattr(io, k, out[k].ctypes.data)
-        out["q"] = q.copy()
+        out["q"] = keep["q"].copy()
         out["arrived"] = np.full(self.batch, -1, dtype=np.int32)
         out["pending"] = np.zeros(n_checks, dtype=np.int32)
         o.q_out, o.arrived, o.pending = out["q"].ctypes.data, out["arrived"].ctypes.data, out["pending"].ctypes.data
