@@ -321,6 +321,54 @@ int vfik_goto(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o);
  * *checks_run (may be NULL) = the number of checks executed; rows of pending, q_traj and dist_traj beyond it are not written. */
 int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, int poll_checks, int* checks_run);
 
+/* Waypoint lists.  A user of the reference never makes just one gotoFrame call: a pick-and-place script is a list of them -- approach pose, grasp
+ * pose, lift pose, place pose -- and the next frame goes out the moment the previous call returned true (handlers.py:346-387).  vfik_follow is
+ * vfik_goto for arms that each carry their own list of goal frames, way16[B][W][16]: the same blocks of `stride` cycles, the same gate, and after
+ * every block one small kernel (follow_kernel) that applies vfik_goto's arrival rule -- the same distance row, both compares strict and in
+ * double, NaN never arrives, an arm without a goal block never arrives -- and, for an arm it finds at its waypoint w, writes waypoint w + 1 into
+ * the arm's goal block in the same kernel.  No host takes part; the whole run is one enqueued sequence.
+ *   path length  L_b = the number of leading rows of way16[b] whose FIRST element is not NaN: a NaN row ends the path, so arms may have paths
+ *                shorter than W.  An arm with L_b == 0 is kept out exactly like an arm with io->active[b] == 0: it does not run, is not counted
+ *                in pending[], and its goal block is not touched.
+ *   before block 0   reached = -1, next = 0, and rows 0..2 of waypoint 0 go into the goal block's frame of every arm that takes part and HAS a
+ *                goal block -- the stores of vfik_move_fields; slow-down distance, force, the `present` flag and the arm's speedScale stay.  An
+ *                arm without a goal block runs, never arrives and is never written to, as in vfik_goto and vfik_move_fields.
+ *   after block k    the precision pair is (via_pos_prec, via_rot_prec) while next[b] < L_b - 1 and (pos_prec, rot_prec) at the arm's last
+ *                waypoint.  On success reached[b][next] = (k + 1) * stride - 1 and next += 1; if next < L_b, the frame of waypoint `next` goes into
+ *                the goal block.  An arm advances by at most ONE waypoint per check: the distance to the new goal exists only after the next
+ *                block (gotoFrame discards its first read for the same reason, handlers.py:365-384).
+ *   gate         of the next block: the caller's && L_b > 0 && !(hold && next == L_b).  pending[k] counts the arms that take part and have
+ *                next < L_b.  Rows of an arm that did not run its block repeat, as in vfik_goto: q_traj, dist_traj and way_traj.
+ *   afterwards   the goal block of an arm holds waypoint min(next, L_b - 1).  Like vfik_move_fields the call changes the goal image only: no
+ *                other vfik_set_* state changes, vfik_launch_epoch does not move, no launch decision changes, and it launches only the cycle
+ *                kernels vfik_rollout launches.
+ * Only a goal that is the plain goal block is supported: a funnel or a near-goal repeller of a goalAndNormal scene (object_feeder:248-303) stays
+ * where vfik_set_fields or vfik_move_scene put it.
+ * Device pointers, io dtype, asynchronous; io outputs, q_out, q_traj, dist_traj, the wait for vfik_submit_host tickets and the allocation of the
+ * handle's buffers (vfik_goto's and one path length per arm: before the first enqueue, never under capture -- VFIK_E_STATE) as vfik_goto.
+ * VFIK_E_ARG, nothing enqueued: what vfik_goto refuses, and n_way < 1, way16 / reached / next NULL, way16 not 16-byte aligned, a via_*
+ * precision negative or NaN. */
+typedef struct vfik_follow_opts {
+    int32_t n_cycles, stride;         /* as vfik_goto_opts */
+    double  dt;
+    int32_t clamp_to_limits, hold;    /* hold: an arm that reached its LAST waypoint takes no further cycle */
+    double  pos_prec, rot_prec;       /* metres, radians: the rule at an arm's last waypoint */
+    double  via_pos_prec, via_rot_prec; /* the rule at every waypoint before an arm's last one */
+    int32_t n_way;                    /* W >= 1 */
+    const void* way16;                /* in  [B][W][16], io dtype, 16-byte aligned: the goal frames in order */
+    int32_t* reached;                 /* out [B][W]  cycle index of the check that found the arm at waypoint w, -1.  Required */
+    int32_t* next;                    /* out [B]     number of waypoints reached = index of the one under way.  Required */
+    int32_t* pending;                 /* out [n_checks] arms that have not reached their last waypoint; may be NULL */
+    void*   q_out; void* q_traj; void* dist_traj;   /* as vfik_goto_opts */
+    int32_t* way_traj;                /* out [n_checks][B] the waypoint index row k of dist_traj was measured against; may be NULL */
+} vfik_follow_opts;
+/* sizeof(vfik_follow_opts) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_follow_opts_size(void);
+int vfik_follow(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o);
+/* The same with HOST pointers (io and o alike), poll_checks and *checks_run as vfik_goto_host: rows of pending, q_traj, dist_traj and way_traj
+ * beyond *checks_run are not written. */
+int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, int poll_checks, int* checks_run);
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

@@ -120,6 +120,7 @@ struct vfik_handle {
     void* d_goto_dist = nullptr;
     void* d_gotoq[2] = {nullptr, nullptr};
     DevBuf goto_stage;
+    int* d_follow_len = nullptr;   // vfik_follow (which runs on vfik_goto's buffers): every arm's path length
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -603,7 +604,7 @@ void vfik_destroy(vfik_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->goto_stage.p};
+                    h->goto_stage.p, h->d_follow_len};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -1415,8 +1416,8 @@ int goto_check(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
     return VFIK_OK;
 }
 
-// the handle's buffers this goto needs (first call: never under stream capture), pending[] zeroed, arrived[] and the gate set
-int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r) {
+// the handle's buffers this goto needs (first call: never under stream capture) and pending[] zeroed; follow: a vfik_follow on these options
+int goto_reserve(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r, bool follow = false) {
     r.io = io;
     r.o = *o;
     r.n_checks = o->n_cycles / o->stride;
@@ -1429,9 +1430,10 @@ int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoR
     // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
     const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
                        (o->q_traj && r.n_checks > 1 && (reinterpret_cast<uintptr_t>(o->q_traj) % 16 || r.qrow % 16));
-    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign)) {
-        if (refuse_capture(h->stream, "vfik_goto: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such vfik_goto call before capturing the stream"))
+    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (follow && !h->d_follow_len)) {
+        if (refuse_capture(h->stream, "vfik_goto / vfik_follow: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such call before capturing the stream"))
             return VFIK_E_STATE;
+        if (follow && !h->d_follow_len && dev_alloc(h, (void**)&h->d_follow_len, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
         if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
         // (synchronised: an earlier goto may still count into the smaller array)
         if (need_pending && reserve(h, h->goto_pending, (size_t)r.n_checks * sizeof(int), true, true)) return VFIK_E_HIP;
@@ -1442,6 +1444,13 @@ int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoR
     }
     r.pending = o->pending ? o->pending : static_cast<int32_t*>(h->goto_pending.p);
     HIP_TRY(hipMemsetAsync(r.pending, 0, (size_t)r.n_checks * sizeof(int), h->stream));
+    return VFIK_OK;
+}
+
+// ... and arrived[] and the gate set
+int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r) {
+    const int rc = goto_reserve(h, io, o, r);
+    if (rc != VFIK_OK) return rc;
     vfik::ArriveArgs g{};
     g.arrived = o->arrived;
     g.gate = h->d_goto_gate;
@@ -1457,25 +1466,40 @@ void* goto_q_row(const vfik_handle* h, const GotoRun& r, int k) {
     return r.o.q_traj ? static_cast<char*>(r.o.q_traj) + (size_t)k * r.qrow : h->d_gotoq[k & 1];
 }
 
-// block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
-int goto_block(vfik_handle* h, const GotoRun& r, int k) {
+// the rows of block k: the q it reads and writes, its goal_dist, and the trace's distance row in front of it (NULL: no trace, or k = 0)
+struct BlockRows {
+    const void* q_prev;
+    void* q_now;
+    void* dist;
+    const void* dist_prev;
+};
+
+// block k: `stride` cycles through launch_cycles, as vfik_rollout runs them
+int goto_cycles(vfik_handle* h, const GotoRun& r, int k, BlockRows& w) {
     vfik_io b = *r.io;
-    const void* const q_prev = k == 0 ? r.io->q : goto_q_row(h, r, k - 1);
-    void* const q_now = goto_q_row(h, r, k);
-    void* const dist = r.o.dist_traj ? static_cast<char*>(r.o.dist_traj) + (size_t)k * r.drow : (r.io->goal_dist ? r.io->goal_dist : h->d_goto_dist);
-    b.q = q_prev;
-    b.goal_dist = dist;
+    w.q_prev = k == 0 ? r.io->q : goto_q_row(h, r, k - 1);
+    w.q_now = goto_q_row(h, r, k);
+    w.dist = r.o.dist_traj ? static_cast<char*>(r.o.dist_traj) + (size_t)k * r.drow : (r.io->goal_dist ? r.io->goal_dist : h->d_goto_dist);
+    w.dist_prev = (r.o.dist_traj && k > 0) ? static_cast<char*>(r.o.dist_traj) + (size_t)(k - 1) * r.drow : nullptr;
+    b.q = w.q_prev;
+    b.goal_dist = w.dist;
     b.active = r.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
-    const int rc = launch_cycles(h, &b, r.o.stride, r.o.dt, r.o.clamp_to_limits, q_now, h->stream, k > 0);
+    return launch_cycles(h, &b, r.o.stride, r.o.dt, r.o.clamp_to_limits, w.q_now, h->stream, k > 0);
+}
+
+// block k and its check
+int goto_block(vfik_handle* h, const GotoRun& r, int k) {
+    BlockRows w;
+    const int rc = goto_cycles(h, r, k, w);
     if (rc != VFIK_OK) return rc;
     vfik::ArriveArgs g{};
     g.arrived = r.o.arrived;
     g.gate = h->d_goto_gate;
     g.active = r.io->active;
-    g.dist = dist;
-    g.dist_prev = (r.o.dist_traj && k > 0) ? static_cast<char*>(r.o.dist_traj) + (size_t)(k - 1) * r.drow : nullptr;
-    g.q_prev = q_prev;
-    g.q_now = q_now;
+    g.dist = w.dist;
+    g.dist_prev = w.dist_prev;
+    g.q_prev = w.q_prev;
+    g.q_now = w.q_now;
     g.goal = h->d_goal;
     g.pending = r.pending + k;
     g.pos_prec = r.o.pos_prec;
@@ -1556,6 +1580,157 @@ int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, i
     back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
     back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
     back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
+    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (checks_run) *checks_run = done;
+    return VFIK_OK;
+}
+
+// ---- waypoint lists (a script of gotoFrame calls, handlers.py:346-387) ---------------------------------
+size_t vfik_follow_opts_size(void) { return sizeof(vfik_follow_opts); }
+
+namespace {
+// vfik_goto's options inside a vfik_follow's: the blocks, the gate and the traces are the goto's (arrived: unused)
+vfik_goto_opts follow_goto_opts(const vfik_follow_opts* o) {
+    vfik_goto_opts g{};
+    g.n_cycles = o->n_cycles; g.stride = o->stride; g.dt = o->dt;
+    g.clamp_to_limits = o->clamp_to_limits; g.hold = o->hold;
+    g.pos_prec = o->pos_prec; g.rot_prec = o->rot_prec;
+    g.arrived = o->next;
+    g.pending = o->pending; g.q_out = o->q_out; g.q_traj = o->q_traj; g.dist_traj = o->dist_traj;
+    return g;
+}
+
+struct FollowRun {
+    GotoRun g;
+    vfik_follow_opts o;
+};
+
+// everything that can refuse the call, before anything is enqueued
+int follow_check(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!o || !o->way16 || !o->reached || !o->next) return fail(VFIK_E_ARG, "vfik_follow: the options, their way16[B][W][16], reached[B][W] and next[B] are required");
+    if (o->n_way < 1) return fail(VFIK_E_ARG, "n_way %d: a path has at least one waypoint", o->n_way);
+    if (reinterpret_cast<uintptr_t>(o->way16) % 16) return fail(VFIK_E_ARG, "way16 must be 16-byte aligned: the kernel loads its rows in 16-byte pieces");
+    if (!(o->via_pos_prec >= 0.0) || !(o->via_rot_prec >= 0.0))
+        return fail(VFIK_E_ARG, "via precision (%g m, %g rad) must not be negative or NaN", o->via_pos_prec, o->via_rot_prec);
+    const vfik_goto_opts g = follow_goto_opts(o);
+    return goto_check(h, io, &g);
+}
+
+// after the shared checks, on the pointer the kernel reads (the host form: its staged copy)
+int follow_begin(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, FollowRun& r) {
+    r.o = *o;
+    const vfik_goto_opts go = follow_goto_opts(o);
+    const int rc = goto_reserve(h, io, &go, r.g, true);
+    if (rc != VFIK_OK) return rc;
+    r.g.gated = true;   // (an arm without a path is kept out: the blocks always run under the gate)
+    vfik::FollowArgs f{};
+    f.reached = o->reached; f.next = o->next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
+    f.active = io->active;
+    f.way16 = o->way16;
+    f.goal = h->d_goal;
+    f.B = h->B; f.W = o->n_way; f.k = -1;
+    f.Bpad = h->Bpad;
+    hipError_t e = vfik::launch_follow(h->io_dtype, f, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+// block k and its check
+int follow_block(vfik_handle* h, const FollowRun& r, int k) {
+    BlockRows w;
+    const int rc = goto_cycles(h, r.g, k, w);
+    if (rc != VFIK_OK) return rc;
+    const vfik_follow_opts& o = r.o;
+    vfik::FollowArgs f{};
+    f.reached = o.reached; f.next = o.next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
+    f.active = r.g.io->active;
+    f.way16 = o.way16;
+    f.dist = w.dist; f.dist_prev = w.dist_prev; f.q_prev = w.q_prev; f.q_now = w.q_now;
+    f.goal = h->d_goal;
+    f.pending = r.g.pending + k;
+    f.way_now = o.way_traj ? o.way_traj + (size_t)k * h->B : nullptr;
+    f.way_prev = (o.way_traj && k > 0) ? o.way_traj + (size_t)(k - 1) * h->B : nullptr;
+    f.pos_prec = o.pos_prec; f.rot_prec = o.rot_prec; f.via_pos_prec = o.via_pos_prec; f.via_rot_prec = o.via_rot_prec;
+    f.B = h->B; f.n = h->n; f.W = o.n_way; f.k = k; f.stride = o.stride; f.hold = o.hold ? 1 : 0;
+    f.Bpad = h->Bpad;
+    hipError_t e = vfik::launch_follow(h->io_dtype, f, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+}  // namespace
+
+int vfik_follow(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o) {
+    int rc = follow_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    FollowRun r;
+    if ((rc = follow_begin(h, io, o, r)) != VFIK_OK) return rc;
+    for (int k = 0; k < r.g.n_checks; ++k)
+        if ((rc = follow_block(h, r, k)) != VFIK_OK) return rc;
+    return goto_end(h, r.g, r.g.n_checks);
+}
+
+// Host-pointer form, as vfik_goto_host: every member of io and of the options in the handle's staging buffer, way16 copied in with the inputs
+// (the alignment rule holds for the caller's array here too, although the kernel reads the staged copy).
+int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, int poll_checks, int* checks_run) {
+    int rc = follow_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    const int n_checks = o->n_cycles / o->stride;
+    const size_t qrow = (size_t)h->B * h->n * h->esz, drow = (size_t)h->B * 2 * h->esz, wrow = (size_t)h->B * sizeof(int32_t);
+    IoStaging st(*io, h->B, h->io_dims());
+    // gated as vfik_goto_host's; reached and next are written for every arm by the pass in front of block 0, a row of way_traj only for arms that ran
+    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
+    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
+    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
+    st.add(vfik::X_DIST_TRAJ, o->dist_traj, (size_t)n_checks * drow, true);
+    st.add(vfik::X_WAY16, const_cast<void*>(o->way16), (size_t)h->B * o->n_way * 16 * h->esz, false, false, true);
+    st.add(vfik::X_REACHED, o->reached, (size_t)h->B * o->n_way * sizeof(int32_t), false);
+    st.add(vfik::X_NEXT, o->next, wrow, false);
+    st.add(vfik::X_WAY_TRAJ, o->way_traj, (size_t)n_checks * wrow, true);
+    st.layout();
+    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
+    st.map(h->goto_stage.p);
+    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
+    // an arm without a path is kept out like a gated one: its output rows go in before the blocks then, too
+    bool kept_out = io->active != nullptr;
+    for (size_t b = 0, row = (size_t)o->n_way * 16; b < (size_t)h->B && !kept_out; ++b)
+        kept_out = h->esz == 4 ? std::isnan(static_cast<const float*>(o->way16)[b * row]) : std::isnan(static_cast<const double*>(o->way16)[b * row]);
+    if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    const vfik_io d = st.device_io();
+    vfik_follow_opts od = *o;
+    od.way16 = st.extra(vfik::X_WAY16).dev;
+    od.reached = static_cast<int32_t*>(st.extra(vfik::X_REACHED).dev);
+    od.next = static_cast<int32_t*>(st.extra(vfik::X_NEXT).dev);
+    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
+    od.q_out = st.extra(vfik::X_Q_OUT).dev;
+    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
+    od.dist_traj = st.extra(vfik::X_DIST_TRAJ).dev;
+    od.way_traj = static_cast<int32_t*>(st.extra(vfik::X_WAY_TRAJ).dev);
+    FollowRun r;
+    if ((rc = follow_begin(h, &d, &od, r)) != VFIK_OK) return rc;
+    int done = 0;
+    while (done < n_checks) {
+        if ((rc = follow_block(h, r, done)) != VFIK_OK) return rc;
+        ++done;
+        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
+            int32_t left = -1;
+            HIP_TRY(hipMemcpyAsync(&left, r.g.pending + (done - 1), sizeof left, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (left == 0) break;   // every arm that takes part is at its last waypoint
+        }
+    }
+    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
+    IoStaging back = st;   // of pending and the traces the checks that ran
+    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
+    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
+    back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
+    back.extra(vfik::X_WAY_TRAJ).bytes = (size_t)done * wrow;
     if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (checks_run) *checks_run = done;

@@ -1,5 +1,5 @@
 // vfik_io_layout.h -- the ONE description of vfik_io for the host-pointer call forms (vfik_step_host, vfik_rollout_host, vfik_goto_host,
-// vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
+// vfik_follow_host, vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
 // vfik_abi.cpp does the copies, tests/c_host/io_layout.cpp checks the layout on the CPU.
 #pragma once
 
@@ -65,13 +65,18 @@ constexpr bool io_inputs_first() {
 }
 static_assert(io_inputs_first(), "IO_MEMBERS: the inputs come first");
 
-// what a call form stages beside vfik_io's members: outputs all of them, behind io's
+// what a call form stages beside vfik_io's members, behind io's: outputs, but for way16 -- an input that a form copies in with the inputs
+// of io, outside their contiguous prefix (in_bytes)
 enum IoExtra {
     X_Q_OUT,       // [B][n]            vfik_rollout_host's and vfik_goto_host's q_out
     X_ARRIVED,     // [B] int32         the rest: vfik_goto_opts
     X_PENDING,     // [n_checks] int32
     X_Q_TRAJ,      // [n_checks][B][n]
     X_DIST_TRAJ,   // [n_checks][B][2]
+    X_WAY16,       // [B][W][16]        input; the rest: vfik_follow_opts
+    X_REACHED,     // [B][W] int32
+    X_NEXT,        // [B] int32
+    X_WAY_TRAJ,    // [n_checks][B] int32
     N_IO_EXTRA
 };
 constexpr int N_STAGED = N_IO + N_IO_EXTRA;
@@ -113,16 +118,17 @@ struct IoStaging {
         }
     }
     // always: staged without an array of the caller's, too
-    void add(IoExtra which, void* host, size_t bytes, bool gated, bool always = false) {
+    void add(IoExtra which, void* host, size_t bytes, bool gated, bool always = false, bool input = false) {
         Member& x = m[N_IO + which];
         x.host = host;
         x.present = host != nullptr || always;
         x.bytes = bytes;
         x.gated = gated;
+        x.input = input;
     }
     Member& extra(IoExtra which) { return m[N_IO + which]; }
 
-    // every present member at the next multiple of ALIGN, in order: the inputs are a prefix, absent members take no room
+    // every present member at the next multiple of ALIGN, in order: io's inputs are a prefix, absent members take no room
     void layout() {
         auto up = [](size_t b) { return (b + ALIGN - 1) & ~(ALIGN - 1); };
         total = in_bytes = 0;
@@ -131,7 +137,7 @@ struct IoStaging {
             x.off = total;
             if (!x.present) continue;
             total += up(x.bytes);
-            if (x.input) in_bytes = total;
+            if (x.input && &x < m + N_IO) in_bytes = total;
             ++members;
         }
     }

@@ -541,6 +541,31 @@ struct ArriveArgs {
     long Bpad;
 };
 hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream);
+// vfik_follow: ArriveArgs' sibling for arms that carry a LIST of goal frames (follow_kernel, vfik_kernel.hip).  The check that finds an arm at
+// waypoint next[b] notes the cycle in reached[b][next], advances next[b] and writes the frame of the following waypoint into the arm's goal
+// block -- move_goal_row's stores.  k < 0: the pass in front of block 0 -- reached = -1, next = 0, len[b] = the arm's path length (leading
+// rows of way16[b] whose first element is not NaN), gate[b] = the caller's gate && len > 0, waypoint 0 into the goal blocks of those arms.
+struct FollowArgs {
+    int* reached;               // [B][W] cycle index of the check that found the arm at waypoint w, -1 = not yet
+    int* next;                  // [B] waypoints reached so far = the index of the one under way
+    int* len;                   // [B] path lengths, a buffer of the handle: written by the k < 0 pass, read by every check
+    int* gate;                  // [B] the handle's gate, as ArriveArgs'
+    const int* active;          // [B] the caller's gate, or NULL = every arm
+    const void* way16;          // [B][W][16] the goal frames in order, 16-byte aligned
+    void* dist;                 // [B][2] goal_dist of block k (metres, degrees)
+    const void* dist_prev;      // [B][2] the trace's row k - 1, or NULL
+    const void* q_prev;         // [B][n] the q row block k read
+    void* q_now;                // [B][n] the q row block k wrote
+    void* goal;                 // the goal block's 4 quad planes: planes 0..2 are written, plane 3 component 0 is the `present` flag
+    int* pending;               // &pending[k]: zeroed on the stream in front of the call
+    int* way_now;               // [B] row k of way_traj -- the waypoint `dist` was measured against -- or NULL
+    const int* way_prev;        // [B] row k - 1 of way_traj, or NULL (no trace, or k = 0)
+    double pos_prec, rot_prec;          // metres, radians: at an arm's last waypoint
+    double via_pos_prec, via_rot_prec;  // at every waypoint before it
+    int B, n, W, k, stride, hold;
+    long Bpad;
+};
+hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

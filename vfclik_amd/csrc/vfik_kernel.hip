@@ -14,7 +14,7 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel.
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, arrive_kernel, follow_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -2826,6 +2826,94 @@ __global__ void __launch_bounds__(256) move_scene_kernel(const SceneMoveArgs s) 
 }
 
 // ------------------------------------------------------------------------------------------------
+// vfik_follow: a user of the reference sends a LIST of gotoFrame calls -- approach, grasp, lift, place -- each the moment the previous one
+// returned true (handlers.py:346-387).  arrive_kernel's check for arms that carry such a list, way16[B][W][16]: one thread per arm after
+// block k, the same distance row, the same strict compares in double (NaN never arrives), the same `present` rule.  An arm found at
+// waypoint next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its path goes on -- the frame of waypoint next + 1
+// in its goal block: move_goal_row's three quad stores (lanes run over arms: a wave's stores to a plane lie in one 1 KiB row; plane 3 --
+// present, slow-down, force, speedScale -- stays), loaded as whole quads by the arriving lanes alone.  At most one waypoint per check: the
+// distance to the new goal exists only after the next block (gotoFrame drops its first read for the same reason, handlers.py:365-384).
+//   precision    (via_pos_prec, via_rot_prec) while a waypoint follows, (pos_prec, rot_prec) at the arm's last one;
+//   gate         the caller's && len > 0 && !(hold && next == len); an arm the gate kept out repeats its q, distance and waypoint rows;
+//   pending[k]   arms that take part and have next < len -- a wave ballot, one atomic add per wave;
+//   way_now[b]   the waypoint the distance row of this check was measured against: min(next, len - 1) on entry.
+// k < 0 (uniform): reached = -1, next = 0, len = leading rows of way16[b] that do not start with NaN, the gate, and waypoint 0 into the goal
+// block of every arm that takes part and has one.  No LDS, no scratch, no register array.
+// ------------------------------------------------------------------------------------------------
+// a quad as ONE value (a struct copy through MoveQuad would stay a 16 / 32-byte private object here: the frame's three loads come before the
+// stores they may alias); 16-byte aligned for either I/O type, which is what way16 and the planes guarantee
+template <typename T> struct FollowQuad { typedef T type __attribute__((ext_vector_type(4), aligned(16))); };
+
+template <typename T>
+__device__ __forceinline__ void follow_goal_store(T* goal, int b, long Qp, const T* frame) {
+    typedef typename FollowQuad<T>::type Quad;
+    const Quad* const src = reinterpret_cast<const Quad*>(frame);
+    Quad* const g = reinterpret_cast<Quad*>(goal) + b;
+    const Quad r0 = src[0], r1 = src[1], r2 = src[2];
+    g[0] = r0;
+    g[Qp] = r1;
+    g[2 * Qp] = r2;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) follow_kernel(const FollowArgs g) {
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool under_way = false;
+    if (b < g.B) {
+        const bool ua = !g.active || g.active[b] != 0;
+        const T* const way = static_cast<const T*>(g.way16) + (long)b * g.W * 16;
+        T* const goal = static_cast<T*>(g.goal);
+        const long Qp = g.Bpad;   // quads per plane
+        const bool present = goal[(3 * Qp + b) * 4] != (T)0;
+        if (g.k < 0) {   // (uniform: the pass in front of block 0)
+            int L = 0;
+            while (L < g.W && way[(long)L * 16] == way[(long)L * 16]) ++L;
+            for (int w = 0; w < g.W; ++w) g.reached[(long)b * g.W + w] = -1;
+            g.next[b] = 0;
+            g.len[b] = L;
+            const bool in = ua && L > 0;
+            g.gate[b] = in ? 1 : 0;
+            if (in && present) follow_goal_store<T>(goal, b, Qp, way);
+            return;
+        }
+        const int L = g.len[b];
+        const bool in = ua && L > 0;
+        int nx = g.next[b];
+        T* const dn = static_cast<T*>(g.dist) + (long)b * 2;
+        if (g.gate[b] == 0) {
+            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
+            T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
+            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
+            if (g.dist_prev) {
+                const T* const dp = static_cast<const T*>(g.dist_prev) + (long)b * 2;
+                dn[0] = dp[0];
+                dn[1] = dp[1];
+            }
+            if (g.way_prev) g.way_now[b] = g.way_prev[b];
+        } else {
+            if (g.way_now) g.way_now[b] = nx < L ? nx : L - 1;
+            if (nx < L) {
+                const bool last = nx == L - 1;
+                const double d = (double)dn[0];
+                const double a = ((double)dn[1] * M_PI) / 180.0;
+                if (present && d < (last ? g.pos_prec : g.via_pos_prec) && a < (last ? g.rot_prec : g.via_rot_prec)) {
+                    g.reached[(long)b * g.W + nx] = (g.k + 1) * g.stride - 1;
+                    ++nx;
+                    g.next[b] = nx;
+                    if (nx < L) follow_goal_store<T>(goal, b, Qp, way + (long)nx * 16);
+                }
+            }
+        }
+        g.gate[b] = (in && !(g.hold && nx == L)) ? 1 : 0;
+        under_way = in && nx < L;
+    } else if (g.k < 0) {
+        return;
+    }
+    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
+}
+
+// ------------------------------------------------------------------------------------------------
 // EIGHT LANES PER ARM (small batches): the mapping BASELINE.json's north_star sketches -- an arm spread over the lanes of
 // a (sub-)wave with cross-lane exchange -- for what vfclik itself runs: a handful of arms (scripts/vfclik:88-105), each
 // with its vf, nullspace and debug process and the bridge's mixer.  Served: revolute chain of up to 7 joints, identity
@@ -3737,6 +3825,13 @@ hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream) 
     const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
     if (io_dtype == 32) hipLaunchKernelGGL(arrive_kernel<float>, grid, blk, 0, stream, g);
     else hipLaunchKernelGGL(arrive_kernel<double>, grid, blk, 0, stream, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream) {
+    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
+    if (io_dtype == 32) hipLaunchKernelGGL(follow_kernel<float>, grid, blk, 0, stream, g);
+    else hipLaunchKernelGGL(follow_kernel<double>, grid, blk, 0, stream, g);
     return hipGetLastError();
 }
 }  // namespace vfik

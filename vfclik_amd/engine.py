@@ -81,6 +81,9 @@ def load_library(path=None):
         "vfik_goto_opts_size": (C.c_size_t, []),
         "vfik_goto": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoOpts)]),
         "vfik_goto_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoOpts), C.c_int, C.POINTER(C.c_int)]),
+        "vfik_follow_opts_size": (C.c_size_t, []),
+        "vfik_follow": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowOpts)]),
+        "vfik_follow_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowOpts), C.c_int, C.POINTER(C.c_int)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -126,6 +129,9 @@ def load_library(path=None):
     if lib.vfik_goto_opts_size() != C.sizeof(_abi.GotoOpts):
         raise VfikError("struct layout mismatch: vfik_goto_opts is %d bytes in the library, %d in the Python mirror"
                         % (lib.vfik_goto_opts_size(), C.sizeof(_abi.GotoOpts)))
+    if lib.vfik_follow_opts_size() != C.sizeof(_abi.FollowOpts):
+        raise VfikError("struct layout mismatch: vfik_follow_opts is %d bytes in the library, %d in the Python mirror"
+                        % (lib.vfik_follow_opts_size(), C.sizeof(_abi.FollowOpts)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
         _lib = lib
     return lib
@@ -586,6 +592,96 @@ class Engine:
         self._chk(self.lib.vfik_goto_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
         out["checks_run"] = int(ran.value)
         for k in ("pending", "q_traj", "dist_traj"):
+            if k in out:
+                out[k] = out[k][:out["checks_run"]]
+        return out
+
+    # -- waypoint lists (vfik_follow: a script of gotoFrame calls for the batch) ---------------------
+    def _follow_opts(self, n_way, n_cycles, dt, precision, via_precision, stride, hold, clamp):
+        pos, rot = precision
+        via_pos, via_rot = precision if via_precision is None else via_precision
+        o = _abi.FollowOpts()
+        o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
+        o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
+        o.pos_prec, o.rot_prec, o.via_pos_prec, o.via_rot_prec = float(pos), float(rot), float(via_pos), float(via_rot)
+        o.n_way = int(n_way)
+        return o
+
+    def follow(self, io, way, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, reached=None, next=None,
+               pending=None, q_out=None, q_traj=None, dist_traj=None, way_traj=None, n_way=None):
+        """Drive every arm along its own list of goal frames, asynchronously on the engine's stream (include/vfik.h: vfik_follow):
+        :meth:`goto`'s blocks and checks, and the check that finds an arm at waypoint w puts waypoint w + 1 into the arm's goal block on
+        the device.  ``way``: (B, W, 16) or (B, W, 4, 4) row-major frames of the engine's dtype, 16-byte aligned; a row whose first
+        element is NaN ends the arm's path (no row: the arm is kept out like one gated off by ``io.active``).  ``precision`` =
+        (metres, radians) holds at an arm's last waypoint, ``via_precision`` at those before it (None: ``precision``).  ``reached``:
+        int32 (B, W), required, the cycle index of the check that found the arm at each waypoint or -1; ``next``: int32 (B,), required,
+        the number of waypoints reached; ``pending``: int32 (n_checks,); ``q_out``, ``q_traj``, ``dist_traj`` as :meth:`goto`;
+        ``way_traj``: int32 (n_checks, B), the waypoint each row of ``dist_traj`` was measured against.  Torch tensors on this device, or
+        raw addresses (``way`` then with ``n_way``).  ``hold``: an arm that reached its last waypoint takes no further cycle.
+        Afterwards the goal block of an arm holds the waypoint it was last sent to.  The Python-side ``FieldSets`` mirror of the host
+        layer does not learn of it, as with :meth:`move_fields`: a later ``set_fields`` from the mirror puts the old goal back."""
+        if reached is None or next is None:
+            raise ValueError("follow needs reached, an int32 (batch, n_way) device array, and next, an int32 (batch,) one")
+        if not isinstance(way, int):
+            if way.dim() not in (3, 4) or way.shape[0] != self.batch or way.numel() != self.batch * way.shape[1] * 16:
+                raise ValueError("way must be (batch, n_way, 16) or (batch, n_way, 4, 4), got %s" % (tuple(way.shape),))
+            if n_way is not None and n_way != way.shape[1]:
+                raise ValueError("way: %d waypoints per arm, n_way says %d" % (way.shape[1], n_way))
+            n_way = way.shape[1]
+        elif n_way is None:
+            raise ValueError("a raw way address needs n_way")
+        n_checks = int(n_cycles) // max(int(stride), 1)
+        ft = self.io_dtype.name
+        for name, x, shape, dt_name in (("way", way, None, ft), ("reached", reached, (self.batch, n_way), "int32"),
+                                        ("next", next, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
+                                        ("q_out", q_out, (self.batch, self.n), ft), ("q_traj", q_traj, (n_checks, self.batch, self.n), ft),
+                                        ("dist_traj", dist_traj, (n_checks, self.batch, 2), ft),
+                                        ("way_traj", way_traj, (n_checks, self.batch), "int32")):
+            if x is None or isinstance(x, int):
+                continue
+            if not x.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            if str(x.dtype).split(".")[-1] != dt_name or (shape is not None and tuple(x.shape) != shape):
+                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
+        o = self._follow_opts(n_way, n_cycles, dt, precision, via_precision, stride, hold, clamp)
+        o.way16, o.reached, o.next, o.pending = _ptr(way), _ptr(reached), _ptr(next), _ptr(pending)
+        o.q_out, o.q_traj, o.dist_traj, o.way_traj = _ptr(q_out), _ptr(q_traj), _ptr(dist_traj), _ptr(way_traj)
+        self._chk(self.lib.vfik_follow(self.h, C.byref(io), C.byref(o)))
+
+    def follow_host(self, q, way, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, trajectory=False, poll=0,
+                    want=("qdot_out",), null_control=None, active=None, q_lo=None, q_hi=None, q_ref=None):
+        """Host arrays in, host arrays out (vfik_follow_host; synchronous).  ``way``: (B, W, 16) or (B, W, 4, 4), converted to the
+        engine's dtype; NaN rows end a path.  Returns what :meth:`goto_host` returns without ``arrived``, plus ``reached`` (B, W),
+        ``next`` (B,) and, with ``trajectory``, ``way_traj`` (checks_run, B).  ``poll`` > 0 ends the call once every arm that takes part
+        is at its last waypoint.  The ``FieldSets`` mirror does not learn of the new goals (see :meth:`follow`)."""
+        w = np.asarray(way)
+        if w.ndim not in (3, 4) or w.shape[0] != self.batch or w.size != self.batch * w.shape[1] * 16 or w.shape[1] < 1:
+            raise ValueError("way must be (batch, n_way, 16) or (batch, n_way, 4, 4), got %s" % (w.shape,))
+        w = np.ascontiguousarray(w, dtype=self.io_dtype).reshape(self.batch, w.shape[1], 16)
+        if w.ctypes.data % 16:   # (NumPy aligns to 16 bytes or more where it allocates; a view of the caller's may not be)
+            buf = np.empty(w.size + 4, dtype=self.io_dtype)
+            off = (-buf.ctypes.data % 16) // buf.itemsize
+            buf = buf[off:off + w.size].reshape(w.shape)
+            buf[...] = w
+            w = buf
+        io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
+        o = self._follow_opts(w.shape[1], n_cycles, dt, precision, via_precision, stride, hold, clamp)
+        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
+        out["q"] = keep["q"].copy()
+        out["reached"] = np.full((self.batch, w.shape[1]), -1, dtype=np.int32)
+        out["next"] = np.zeros(self.batch, dtype=np.int32)
+        out["pending"] = np.zeros(n_checks, dtype=np.int32)
+        o.way16, o.q_out, o.reached, o.next, o.pending = (w.ctypes.data, out["q"].ctypes.data, out["reached"].ctypes.data,
+                                                          out["next"].ctypes.data, out["pending"].ctypes.data)
+        if trajectory:
+            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
+            out["dist_traj"] = np.zeros((n_checks, self.batch, 2), dtype=self.io_dtype)
+            out["way_traj"] = np.full((n_checks, self.batch), -1, dtype=np.int32)
+            o.q_traj, o.dist_traj, o.way_traj = out["q_traj"].ctypes.data, out["dist_traj"].ctypes.data, out["way_traj"].ctypes.data
+        ran = C.c_int(0)
+        self._chk(self.lib.vfik_follow_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
+        out["checks_run"] = int(ran.value)
+        for k in ("pending", "q_traj", "dist_traj", "way_traj"):
             if k in out:
                 out[k] = out[k][:out["checks_run"]]
         return out

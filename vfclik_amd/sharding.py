@@ -231,22 +231,34 @@ class ShardedEngine:
         driven by a thread of its own around the blocking call (the stand-in path of :meth:`step_host`), and the devices work
         concurrently.  With ``poll`` each part ends when ITS arms are there: ``checks_run`` is the largest count, ``pending`` the sum over
         the parts (a part that ended early adds 0), and the traces of a part that ended early repeat its last row."""
+        qs_of = self._rows(q, "q", global_rows)
+        return self._checked_host(lambda e, i, a: e.goto_host(qs_of[i], n_cycles, dt, precision, **a), global_rows, kw)
+
+    def follow_host(self, q, way, n_cycles, dt, precision, global_rows=True, **kw):
+        """Engine.follow_host over this rank's arms, as :meth:`goto_host`: ``way`` (rows, W, 16) is sharded with the arms; ``reached``,
+        ``next`` and, with ``trajectory``, ``way_traj`` (along its arm axis) come back in arm order beside what :meth:`goto_host` returns."""
+        import numpy as np
+        qs_of, ways = self._rows(q, "q", global_rows), self._rows(np.asarray(way), "way", global_rows)
+        return self._checked_host(lambda e, i, a: e.follow_host(qs_of[i], ways[i], n_cycles, dt, precision, **a), global_rows, kw)
+
+    def _checked_host(self, run, global_rows, kw):
+        """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
+        each on a thread of its own, and the parts' results put together in arm order."""
         import numpy as np
         per_arm = ("null_control", "active", "q_lo", "q_hi", "q_ref")
-        qs = self._rows(q, "q", global_rows)
         kws = {k: self._rows(kw.pop(k), k, global_rows) for k in per_arm if kw.get(k) is not None}
         for k in per_arm:
             kw.pop(k, None)
         if not self.parts:
             raise ValueError("this rank owns no arm: there is nothing to drive")
 
-        def run(i):
-            return self.engines[i].goto_host(qs[i], n_cycles, dt, precision, **dict(kw, **{k: v[i] for k, v in kws.items()}))
+        def one(i):
+            return run(self.engines[i], i, dict(kw, **{k: v[i] for k, v in kws.items()}))
         if len(self.parts) == 1:
-            return run(0)
+            return one(0)
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=len(self.parts)) as pool:
-            outs = list(pool.map(run, range(len(self.parts))))
+            outs = list(pool.map(one, range(len(self.parts))))
         ran = max(o["checks_run"] for o in outs)
         full = {"checks_run": ran}
         for k in outs[0]:
@@ -254,7 +266,7 @@ class ShardedEngine:
                 continue
             if k == "pending":
                 full[k] = np.sum([np.pad(o[k], (0, ran - len(o[k]))) for o in outs], axis=0).astype(np.int32)
-            elif k in ("q_traj", "dist_traj"):
+            elif k in ("q_traj", "dist_traj", "way_traj"):
                 full[k] = np.concatenate([np.concatenate([o[k]] + [o[k][-1:]] * (ran - len(o[k])), axis=0) for o in outs], axis=1)
             else:
                 full[k] = np.concatenate([o[k] for o in outs], axis=0)
