@@ -191,7 +191,17 @@ typedef struct vfik_io {
                                  VFIK_ST_NULL_AMBIGUOUS, /control contributes nothing, and qdot_null carries the
                                  joint-limit task alone.  What IS reproduced there is the subspace: the reference's
                                  command lies in null(J) and the projector used here leaves it unchanged
-                                 (tests/test_oracle_golden.py, the reference's own n = 14 outputs) */
+                                 (tests/test_oracle_golden.py, the reference's own n = 14 outputs).
+                                 THE RANK DECISION next to a singular pose, in terms of sigma_6 / sigma_1 of J:
+                                 up to 7 joints, a row of J is kept while its residual is above 1e-12 of its length, the reference's
+                                 pinv keeps what is above 1e-15: below sigma_6 / sigma_1 = 1e-10 the decision (hence nullity, status
+                                 and qdot_null) is the implementation's own, above it qdot_null is the reference's to within
+                                 eps sigma_1 / sigma_6.  8 and more joints: the joint-limit task is projected off the rows of J
+                                 that pass VFIK_PROJ_ROW_MIN (vfik_types.h) -- a row within 1e-3 of the span of the rows before it
+                                 is dropped, so from about sigma_6 / sigma_1 = 1e-3 down the projected task keeps a component of
+                                 up to 1e-3 sigma_1 |z| in task space that the reference's pinv would remove; the C oracle
+                                 states the same rule, and the decision is the implementation's own only where a row sits within
+                                 a factor of 4 of the threshold (tests/hp_nullspace.py) */
     void* qdot_vf;            /* out [B][n]   /vectorField/qdotOut (vf:462-466) */
     void* qdot_null;          /* out [B][n]   /nullspace/qdotout (nullspace:180-184) */
     void* qdot_out;           /* out [B][n]   mixed (+limited) command (bridge:626); = qdot_vf without the mixer */

@@ -24,6 +24,11 @@ extern "C" {
 #define VFIK_MAX_PARAMS 17   /* type 1 carries frame16 + slow-down distance */
 #define VFIK_MIX_CHANNELS 6  /* bridge:593-596: vectorfield, null, joint, mechanism, xtra1, xtra2 */
 #define VFIK_NULL_CONTROLS 4 /* nullspace:137,144 "expects four-float-bottles" */
+/* Chains of 8 and more joints, the joint-limit task's projector (vfik_io.null_control in vfik.h): the rows of J are
+ * taken in their order (v_x v_y v_z w_x w_y w_z); a row takes part when the squared length of its component orthogonal to the rows kept
+ * before it is above this fraction of the largest squared row length of J.  The task's direction z is projected off the span of the
+ * kept rows. */
+#define VFIK_PROJ_ROW_MIN 1e-6
 
 /* field primitive type codes = keys of vfl.vfl.vectorFieldLibrary() used by the reference
  * (vf:148,238; object_feeder:236,268,288,324,342) */

@@ -140,6 +140,15 @@ def restrict(J):
     return Bm
 
 
+def restrict_rows(J):
+    """chains of 8 and more joints: the joint-limit task's projector by the rule of VFIK_PROJ_ROW_MIN"""
+    J = np.ascontiguousarray(J, dtype=np.float64)
+    n = J.shape[1]
+    Bm = np.zeros((n, n))
+    lib().vfo_restrict_rows(_p(J), C.c_int(n), _p(Bm))
+    return Bm
+
+
 class NullspaceC:
     """Stateful wrapper of vfo_nullspace_basis / vfo_move_in_nullspace."""
 

@@ -290,6 +290,42 @@ void vfo_restrict(const double* J, int n, double* Bout) {
     }
 }
 
+/* The joint-limit task's projector of chains of 8 and more joints, by the rule of VFIK_PROJ_ROW_MIN (vfik_types.h): the rows of J in
+ * their order, a row kept when the squared length of its component orthogonal to the rows kept before it is above VFIK_PROJ_ROW_MIN of
+ * the largest squared row length; Bout = I - Q^T Q, Q an orthonormal basis of the kept rows (Gram-Schmidt, every row cleared twice:
+ * the kept rows are independent to 1e-3, so Q is orthonormal to a few eps).  Where every row is kept this is restrict(I6, J). */
+void vfo_restrict_rows(const double* J, int n, double* Bout) {
+    double Q[6 * MAXJ], gmax = 0.0;
+    int kept = 0;
+    for (int r = 0; r < 6; ++r) {
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) s += J[r * n + i] * J[r * n + i];
+        gmax = fmax(gmax, s);
+    }
+    for (int r = 0; r < 6; ++r) {
+        double* t = Q + kept * n;
+        for (int i = 0; i < n; ++i) t[i] = J[r * n + i];
+        for (int pass = 0; pass < 2; ++pass)
+            for (int k = 0; k < kept; ++k) {
+                double c = 0.0;
+                for (int i = 0; i < n; ++i) c += Q[k * n + i] * t[i];
+                for (int i = 0; i < n; ++i) t[i] -= c * Q[k * n + i];
+            }
+        double d = 0.0;
+        for (int i = 0; i < n; ++i) d += t[i] * t[i];
+        if (!(d > VFIK_PROJ_ROW_MIN * gmax)) continue;
+        double inv = 1.0 / sqrt(d);
+        for (int i = 0; i < n; ++i) t[i] *= inv;
+        ++kept;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double s = (i == j) ? 1.0 : 0.0;
+            for (int k = 0; k < kept; ++k) s -= Q[k * n + i] * Q[k * n + j];
+            Bout[i * n + j] = s;
+        }
+}
+
 /* cyclic Jacobi eigen-decomposition of a symmetric n x n matrix; V columns = eigenvectors */
 static void sym_jacobi(double* A, int n, double* V, double* w) {
     for (int i = 0; i < n; ++i)
@@ -481,7 +517,8 @@ void vfo_cycle(const vfik_chain* c, const vfik_params* p, const double tool[16],
         if (rank >= 2) status |= VFIK_ST_NULL_AMBIGUOUS;
         if (p->flags & VFIK_F_JOINT_LIMIT_TASK) {
             double B[MAXJ * MAXJ], z[MAXJ];
-            vfo_restrict(J, n, B);
+            if (n >= 8) vfo_restrict_rows(J, n, B); /* the stated rule of the long chains (vfik_types.h) */
+            else vfo_restrict(J, n, B);
             for (int i = 0; i < n; ++i) {
                 double mid = 0.5 * (c->q_lo[i] + c->q_hi[i]), half = 0.5 * (c->q_hi[i] - c->q_lo[i]);
                 z[i] = -p->jl_gain * (q[i] - mid) / (half * half);

@@ -35,6 +35,7 @@ void vfo_ikv(const double* J, int n, const double tw[6], const double wy[6], con
              double lambda, double* qdot);
 /* A10: B = I - pinv(J) J  (P = I6), row-major n x n */
 void vfo_restrict(const double* J, int n, double* Bout);
+void vfo_restrict_rows(const double* J, int n, double* Bout); /* chains of 8+ joints: the rule of VFIK_PROJ_ROW_MIN */
 /* A11: stateful basis; returns r = number of rows written to basis (r x n, row-major) */
 int vfo_nullspace_basis(const double* J, int n, double* lastvec /*n x n, column i = vector i*/,
                         int* sig /*n*/, double* basis);

@@ -1987,8 +1987,12 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                 }
         }
         if constexpr (FUSEP) {
-            // LDL^T of the undamped Gram matrix; a vanishing pivot (singular pose) drops that direction
-            // instead of dividing by it.  Then wn <- (J J^T)^-1 J z.
+            // LDL^T of the undamped Gram matrix.  A row of J whose part orthogonal to the rows kept before it is short -- pivot <=
+            // VFIK_PROJ_ROW_MIN of the largest squared row length (include/vfik_types.h) -- is DROPPED: what is
+            // computed is the exact projector off the span of the kept rows, wn <- (Jk Jk^T)^-1 Jk z.  The normal equations lose
+            // eps / (pivot / gmax): with the rule at 1e-6 the kept rows' projector is good to 1e-10 |z|; at the 1e-12 this code
+            // used before, an arm next to a singular pose (sigma_6 / sigma_1 from 1e-6 down) got a projected task that was off by
+            // O(|z|) from either projector (tests/test_gpu_nullspace.py).
             double (*const Gm)[6] = G;
             double gmax = Gm[0][0];
 #pragma unroll
@@ -2003,7 +2007,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                 double dj = Gm[jj][j];
 #pragma unroll
                 for (int k = 0; k < j; ++k) dj = __builtin_fma(-Gm[jj][k], v[k], dj);
-                const bool okp = dj > 1e-12 * gmax;
+                const bool okp = dj > VFIK_PROJ_ROW_MIN * gmax;
                 Gm[jj][j] = okp ? dj : 0.0;
                 gi[j] = okp ? rcp_nr(dj) : 0.0;
 #pragma unroll
