@@ -379,6 +379,77 @@ int vfik_follow(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o);
  * beyond *checks_run are not written. */
 int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, int poll_checks, int* checks_run);
 
+/* Joint-space goto.  The reference's second motion call, HandleJController.set_ref_js(js, wait, goal_precision) (handlers.py:544-576): it sends a
+ * joint reference to /jpctrl/ref -- io->q_ref -- and reads /bridge/encoders until
+ *     ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
+ * or the time is up, and returns (result, js - q).  vfik_goto_js is that wait for the batch: the blocks of vfik_goto unchanged -- `stride` cycles
+ * through the kernels of vfik_rollout, under the handle's gate, the same q ping-pong or q_traj rows -- and after every block one small kernel
+ * (arrive_js_kernel) that applies the reference's rule to each arm that ran the block and has not arrived, in double on the io-typed values:
+ *     ok = for all i:  (ref[i] - prec[i]) <= q[i]  &&  (ref[i] + prec[i]) >= q[i]
+ * Both compares are non-strict and the two edges are computed as written (|ref - q| <= prec is another function in floating point).  q is the
+ * block's integrated row -- what /bridge/encoders would publish; ref is the arm's row of io->q_ref AS THE CALLER SENT IT, not the clamped value the
+ * controller keeps (io->q_ref_out): a reference beyond a limit by more than its precision never arrives, as in the reference.  NaN in q or in
+ * the row never arrives; an arm whose row STARTS with NaN has no controller (the io->q_ref convention): it runs, never arrives and counts in
+ * pending[], like an arm without a goal block in vfik_goto.  There is no check in front of block 0.
+ *   arrived[b]   = (k + 1) * stride - 1 for the first check k the arm passed, the number vfik_goto gives for check k: the 0-based index of the
+ *                  last cycle taken before the joint angles that passed; -1: not within n_cycles.
+ *   diff[b][i]   = (T)(ref[i] - q[i]), written at every check the arm ran: set_ref_js's `difference`.  Held and gated arms keep their row.
+ *   hold, io->active, pending[k], the io outputs (status ORs over the blocks, io->q is never written), q_out, q_traj, the wait for
+ *   vfik_submit_host tickets and the allocation of the handle's buffers (never under capture: VFIK_E_STATE): as vfik_goto.
+ * The cycle kernel is the one a vfik_rollout with this io launches, the same for every block; it is asked for goal_dist only when io names it
+ * (the rule does not read it).  The mixer flag, the mixer weights (vfik_set_params, vfik_set_mixer_weights: what set_joint_control sends,
+ * handlers.py:189-211) and the fields are the caller's: WITHOUT VFIK_F_MIXER the reference moves nothing, as in vfik_step, and the check is
+ * made all the same.  vfik_launch_epoch does not move.
+ * VFIK_E_ARG, nothing enqueued: what vfik_goto refuses, io->q_ref NULL, prec NULL or an element of it negative or NaN. */
+typedef struct vfik_goto_js_opts {
+    int32_t n_cycles, stride;      /* as vfik_goto_opts */
+    double  dt;
+    int32_t clamp_to_limits, hold;
+    const double* prec;            /* HOST [n]: goal_precision of handlers.py:544-576, radians (metres for a prismatic joint); each >= 0, not NaN,
+                                      +inf allowed (that joint never decides).  Read during the call, in the device form too */
+    int32_t* arrived;              /* out [B], required */
+    int32_t* pending;              /* out [n_checks], may be NULL */
+    void*   q_out;                 /* out [B][n] */
+    void*   q_traj;                /* out [n_checks][B][n] */
+    void*   diff;                  /* out [B][n]  js - q of the arm's last check: set_ref_js's `difference`; may be NULL */
+} vfik_goto_js_opts;
+/* sizeof(vfik_goto_js_opts) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_goto_js_opts_size(void);
+int vfik_goto_js(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o);
+/* The same with HOST pointers (io and o alike); poll_checks and *checks_run as vfik_goto_host. */
+int vfik_goto_js_host(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, int poll_checks, int* checks_run);
+
+/* Posture lists: vfik_follow's state machine with vfik_goto_js's rule, for arms that each carry a list of joint references wayq[B][W][n] -- the
+ * home posture, the pre-grasp posture, ... of a script of set_ref_js calls.  len, reached, next, way_traj, one advance per check, the via / last
+ * precision and the gate (the caller's && L_b > 0 && !(hold && next == L_b)) are vfik_follow's; a row of wayq whose FIRST element is NaN ends the
+ * arm's list.  The reference row every block reads as io->q_ref belongs to the HANDLE ([B][n], io dtype, allocated with the other goto buffers):
+ * in front of block 0 posture 0 goes into it -- an arm that does not take part gets a row that starts with NaN --, and the check that finds an arm
+ * at posture `next` writes the following one (follow_js_kernel).  Nothing else of the handle changes: the goal image, vfik_launch_epoch and the
+ * launch decisions stay, the cycle kernel is the one a caller's own q_ref would select, and a later call with the caller's own io->q_ref never
+ * sees the handle's row.  diff is measured against the posture the arm was sent to, min(next, L_b - 1) on entry to the check.
+ * VFIK_E_ARG, nothing enqueued: what vfik_goto refuses, io->q_ref GIVEN (the handle supplies it), n_way < 1, wayq / reached / next NULL, wayq
+ * not aligned to its element type, prec NULL, an element of prec or via_prec negative or NaN. */
+typedef struct vfik_follow_js_opts {
+    int32_t n_cycles, stride;      /* as vfik_goto_opts */
+    double  dt;
+    int32_t clamp_to_limits, hold; /* hold: an arm that reached its LAST posture takes no further cycle */
+    const double* prec;            /* HOST [n]: the rule at an arm's last posture */
+    const double* via_prec;        /* HOST [n]: at those before it; NULL = prec */
+    int32_t n_way;                 /* W >= 1 */
+    const void* wayq;              /* in  [B][W][n], io dtype, element-aligned: a row whose FIRST element is NaN ends the arm's list */
+    int32_t* reached;              /* out [B][W], required */
+    int32_t* next;                 /* out [B], required */
+    int32_t* pending;              /* out [n_checks], may be NULL */
+    void*   q_out;                 /* out [B][n] */
+    void*   q_traj;                /* out [n_checks][B][n] */
+    void*   diff;                  /* out [B][n], may be NULL */
+    int32_t* way_traj;             /* out [n_checks][B] the posture index the arm's check k was made against; may be NULL */
+} vfik_follow_js_opts;
+/* sizeof(vfik_follow_js_opts) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_follow_js_opts_size(void);
+int vfik_follow_js(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o);
+int vfik_follow_js_host(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, int poll_checks, int* checks_run);
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

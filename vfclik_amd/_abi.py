@@ -64,6 +64,21 @@ class FollowOpts(C.Structure):
                 ("q_out", C.c_void_p), ("q_traj", C.c_void_p), ("dist_traj", C.c_void_p), ("way_traj", C.c_void_p)]
 
 
+class GotoJsOpts(C.Structure):
+    """``struct vfik_goto_js_opts`` (include/vfik.h: vfik_goto_js)."""
+    _fields_ = [("n_cycles", C.c_int32), ("stride", C.c_int32), ("dt", C.c_double), ("clamp_to_limits", C.c_int32), ("hold", C.c_int32),
+                ("prec", C.c_void_p), ("arrived", C.c_void_p), ("pending", C.c_void_p), ("q_out", C.c_void_p), ("q_traj", C.c_void_p),
+                ("diff", C.c_void_p)]
+
+
+class FollowJsOpts(C.Structure):
+    """``struct vfik_follow_js_opts`` (include/vfik.h: vfik_follow_js)."""
+    _fields_ = [("n_cycles", C.c_int32), ("stride", C.c_int32), ("dt", C.c_double), ("clamp_to_limits", C.c_int32), ("hold", C.c_int32),
+                ("prec", C.c_void_p), ("via_prec", C.c_void_p), ("n_way", C.c_int32), ("wayq", C.c_void_p), ("reached", C.c_void_p),
+                ("next", C.c_void_p), ("pending", C.c_void_p), ("q_out", C.c_void_p), ("q_traj", C.c_void_p), ("diff", C.c_void_p),
+                ("way_traj", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

@@ -121,6 +121,7 @@ struct vfik_handle {
     void* d_gotoq[2] = {nullptr, nullptr};
     DevBuf goto_stage;
     int* d_follow_len = nullptr;   // vfik_follow (which runs on vfik_goto's buffers): every arm's path length
+    void* d_js_ref = nullptr;      // vfik_follow_js: the reference row [B][n] its blocks read as io->q_ref (nobody else reads it)
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -604,7 +605,7 @@ void vfik_destroy(vfik_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->goto_stage.p, h->d_follow_len};
+                    h->goto_stage.p, h->d_follow_len, h->d_js_ref};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -1397,6 +1398,8 @@ struct GotoRun {
     int32_t* pending;
     size_t qrow, drow;   // bytes of a q row [B][n] and of a distance row [B][2]
     bool gated;          // the blocks run under the handle's gate (hold, or the caller gates): else every arm runs every block
+    bool joint = false;  // a joint-space form (vfik_goto_js, vfik_follow_js): no distance row -- the blocks' goal_dist is the caller's business
+    const void* q_ref = nullptr;   // ... and, when set, what the blocks read as io->q_ref in place of the caller's (vfik_follow_js: the handle's row)
 };
 
 // everything that can refuse the call, before anything is enqueued
@@ -1417,23 +1420,26 @@ int goto_check(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
 }
 
 // the handle's buffers this goto needs (first call: never under stream capture) and pending[] zeroed; follow: a vfik_follow on these options
-int goto_reserve(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r, bool follow = false) {
+int goto_reserve(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r, bool follow = false, bool joint = false) {
     r.io = io;
+    r.joint = joint;
     r.o = *o;
     r.n_checks = o->n_cycles / o->stride;
     r.qrow = (size_t)h->B * h->n * h->esz;
     r.drow = (size_t)h->B * 2 * h->esz;
     r.gated = o->hold || io->active;
     const bool need_pending = !o->pending && h->goto_pending.bytes < (size_t)r.n_checks * sizeof(int);
-    const bool need_dist = !o->dist_traj && !io->goal_dist && !h->d_goto_dist;
+    const bool need_dist = !joint && !o->dist_traj && !io->goal_dist && !h->d_goto_dist;
     const bool need_q = !o->q_traj && !h->d_gotoq[0];
     // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
     const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
                        (o->q_traj && r.n_checks > 1 && (reinterpret_cast<uintptr_t>(o->q_traj) % 16 || r.qrow % 16));
-    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (follow && !h->d_follow_len)) {
+    const bool need_ref = joint && follow && !h->d_js_ref;
+    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (follow && !h->d_follow_len) || need_ref) {
         if (refuse_capture(h->stream, "vfik_goto / vfik_follow: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such call before capturing the stream"))
             return VFIK_E_STATE;
         if (follow && !h->d_follow_len && dev_alloc(h, (void**)&h->d_follow_len, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
+        if (need_ref && dev_alloc(h, &h->d_js_ref, (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
         if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
         // (synchronised: an earlier goto may still count into the smaller array)
         if (need_pending && reserve(h, h->goto_pending, (size_t)r.n_checks * sizeof(int), true, true)) return VFIK_E_HIP;
@@ -1482,7 +1488,8 @@ int goto_cycles(vfik_handle* h, const GotoRun& r, int k, BlockRows& w) {
     w.dist = r.o.dist_traj ? static_cast<char*>(r.o.dist_traj) + (size_t)k * r.drow : (r.io->goal_dist ? r.io->goal_dist : h->d_goto_dist);
     w.dist_prev = (r.o.dist_traj && k > 0) ? static_cast<char*>(r.o.dist_traj) + (size_t)(k - 1) * r.drow : nullptr;
     b.q = w.q_prev;
-    b.goal_dist = w.dist;
+    if (!r.joint) b.goal_dist = w.dist;   // (a joint form: w.dist is io->goal_dist or a row nobody reads)
+    if (r.q_ref) b.q_ref = r.q_ref;
     b.active = r.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
     return launch_cycles(h, &b, r.o.stride, r.o.dt, r.o.clamp_to_limits, w.q_now, h->stream, k > 0);
 }
@@ -1730,6 +1737,287 @@ int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* 
     back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
     back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
     back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
+    back.extra(vfik::X_WAY_TRAJ).bytes = (size_t)done * wrow;
+    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (checks_run) *checks_run = done;
+    return VFIK_OK;
+}
+
+// ---- joint-space goto and posture lists (set_ref_js, handlers.py:544-576) ---------------------------------
+size_t vfik_goto_js_opts_size(void) { return sizeof(vfik_goto_js_opts); }
+size_t vfik_follow_js_opts_size(void) { return sizeof(vfik_follow_js_opts); }
+
+namespace {
+// vfik_goto's options inside a joint form's: the blocks, the gate and the q rows are the goto's (no precision pair, no distance trace)
+extern "C++" {
+template <typename O>
+vfik_goto_opts js_goto_opts(const O* o, int32_t* arrived) {
+    vfik_goto_opts g{};
+    g.n_cycles = o->n_cycles; g.stride = o->stride; g.dt = o->dt;
+    g.clamp_to_limits = o->clamp_to_limits; g.hold = o->hold;
+    g.arrived = arrived;
+    g.pending = o->pending; g.q_out = o->q_out; g.q_traj = o->q_traj;
+    return g;
+}
+}
+
+int js_prec_check(const vfik_handle* h, const double* prec, const char* what) {
+    for (int i = 0; i < h->n; ++i)
+        if (!(prec[i] >= 0.0)) return fail(VFIK_E_ARG, "%s[%d] = %g: a goal precision must not be negative or NaN", what, i, prec[i]);
+    return VFIK_OK;
+}
+
+struct GotoJsRun {
+    GotoRun g;
+    vfik_goto_js_opts o;
+};
+
+// everything that can refuse the call, before anything is enqueued
+int goto_js_check(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!o || !o->arrived) return fail(VFIK_E_ARG, "vfik_goto_js: the options and their arrived[B] are required");
+    const vfik_goto_opts g = js_goto_opts(o, o->arrived);
+    const int rc = goto_check(h, io, &g);
+    if (rc != VFIK_OK) return rc;
+    if (!io->q_ref) return fail(VFIK_E_ARG, "vfik_goto_js needs io->q_ref, the joint reference of every arm");
+    if (!o->prec) return fail(VFIK_E_ARG, "vfik_goto_js: prec[n], the goal precision per joint, is required");
+    return js_prec_check(h, o->prec, "prec");
+}
+
+vfik::ArriveJsArgs goto_js_args(vfik_handle* h, const GotoJsRun& r, int k) {
+    vfik::ArriveJsArgs g{};
+    g.arrived = r.o.arrived;
+    g.gate = h->d_goto_gate;
+    g.active = r.g.io->active;
+    for (int i = 0; i < h->n; ++i) g.prec[i] = r.o.prec[i];
+    g.B = h->B; g.n = h->n; g.k = k; g.stride = r.o.stride; g.hold = r.o.hold ? 1 : 0;
+    return g;
+}
+
+int goto_js_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, GotoJsRun& r) {
+    r.o = *o;
+    const vfik_goto_opts go = js_goto_opts(o, o->arrived);
+    const int rc = goto_reserve(h, io, &go, r.g, false, true);
+    if (rc != VFIK_OK) return rc;
+    hipError_t e = vfik::launch_arrive_js(h->io_dtype, goto_js_args(h, r, -1), h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive_js launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+// block k and its check
+int goto_js_block(vfik_handle* h, const GotoJsRun& r, int k) {
+    BlockRows w;
+    const int rc = goto_cycles(h, r.g, k, w);
+    if (rc != VFIK_OK) return rc;
+    vfik::ArriveJsArgs g = goto_js_args(h, r, k);
+    g.ref = r.g.io->q_ref;
+    g.q_prev = w.q_prev;
+    g.q_now = w.q_now;
+    g.diff = r.o.diff;
+    g.pending = r.g.pending + k;
+    hipError_t e = vfik::launch_arrive_js(h->io_dtype, g, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive_js launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+struct FollowJsRun {
+    GotoRun g;
+    vfik_follow_js_opts o;
+};
+
+int follow_js_check(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!o || !o->wayq || !o->reached || !o->next) return fail(VFIK_E_ARG, "vfik_follow_js: the options, their wayq[B][W][n], reached[B][W] and next[B] are required");
+    if (o->n_way < 1) return fail(VFIK_E_ARG, "n_way %d: a list has at least one posture", o->n_way);
+    if (reinterpret_cast<uintptr_t>(o->wayq) % h->esz) return fail(VFIK_E_ARG, "wayq must be aligned to its element type");
+    const vfik_goto_opts g = js_goto_opts(o, o->next);
+    const int rc = goto_check(h, io, &g);
+    if (rc != VFIK_OK) return rc;
+    if (io->q_ref) return fail(VFIK_E_ARG, "vfik_follow_js supplies io->q_ref itself (the handle's reference row): leave it NULL");
+    if (!o->prec) return fail(VFIK_E_ARG, "vfik_follow_js: prec[n], the goal precision per joint, is required");
+    if (js_prec_check(h, o->prec, "prec") != VFIK_OK) return VFIK_E_ARG;
+    return o->via_prec ? js_prec_check(h, o->via_prec, "via_prec") : (int)VFIK_OK;
+}
+
+vfik::FollowJsArgs follow_js_args(vfik_handle* h, const FollowJsRun& r, int k) {
+    const vfik_follow_js_opts& o = r.o;
+    vfik::FollowJsArgs f{};
+    f.reached = o.reached; f.next = o.next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
+    f.active = r.g.io->active;
+    f.wayq = o.wayq;
+    f.ref = h->d_js_ref;
+    for (int i = 0; i < h->n; ++i) {
+        f.prec[i] = o.prec[i];
+        f.via_prec[i] = o.via_prec ? o.via_prec[i] : o.prec[i];
+    }
+    f.B = h->B; f.n = h->n; f.W = o.n_way; f.k = k; f.stride = o.stride; f.hold = o.hold ? 1 : 0;
+    return f;
+}
+
+int follow_js_begin(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, FollowJsRun& r) {
+    r.o = *o;
+    const vfik_goto_opts go = js_goto_opts(o, o->next);
+    const int rc = goto_reserve(h, io, &go, r.g, true, true);
+    if (rc != VFIK_OK) return rc;
+    r.g.gated = true;   // (an arm without a list is kept out: the blocks always run under the gate)
+    r.g.q_ref = h->d_js_ref;
+    hipError_t e = vfik::launch_follow_js(h->io_dtype, follow_js_args(h, r, -1), h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow_js launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+// block k and its check
+int follow_js_block(vfik_handle* h, const FollowJsRun& r, int k) {
+    BlockRows w;
+    const int rc = goto_cycles(h, r.g, k, w);
+    if (rc != VFIK_OK) return rc;
+    vfik::FollowJsArgs f = follow_js_args(h, r, k);
+    f.q_prev = w.q_prev; f.q_now = w.q_now;
+    f.diff = r.o.diff;
+    f.pending = r.g.pending + k;
+    f.way_now = r.o.way_traj ? r.o.way_traj + (size_t)k * h->B : nullptr;
+    f.way_prev = (r.o.way_traj && k > 0) ? r.o.way_traj + (size_t)(k - 1) * h->B : nullptr;
+    hipError_t e = vfik::launch_follow_js(h->io_dtype, f, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow_js launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+// the early exit of the host forms: pending[done - 1] read back after every poll_checks checks
+int poll_pending(vfik_handle* h, const GotoRun& r, int done, int32_t* left) {
+    HIP_TRY(hipMemcpyAsync(left, r.pending + (done - 1), sizeof *left, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return VFIK_OK;
+}
+}  // namespace
+
+int vfik_goto_js(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o) {
+    int rc = goto_js_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    GotoJsRun r;
+    if ((rc = goto_js_begin(h, io, o, r)) != VFIK_OK) return rc;
+    for (int k = 0; k < r.g.n_checks; ++k)
+        if ((rc = goto_js_block(h, r, k)) != VFIK_OK) return rc;
+    return goto_end(h, r.g, r.g.n_checks);
+}
+
+// Host-pointer form, as vfik_goto_host: io's members (q_ref among its inputs) and the options' arrays in the handle's staging buffer.  diff goes
+// in under a gate: a gated arm keeps its row.
+int vfik_goto_js_host(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, int poll_checks, int* checks_run) {
+    int rc = goto_js_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    const int n_checks = o->n_cycles / o->stride;
+    const size_t qrow = (size_t)h->B * h->n * h->esz;
+    IoStaging st(*io, h->B, h->io_dims());
+    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
+    st.add(vfik::X_ARRIVED, o->arrived, (size_t)h->B * sizeof(int32_t), false);
+    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
+    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
+    st.add(vfik::X_DIFF, o->diff, qrow, true);
+    st.layout();
+    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
+    st.map(h->goto_stage.p);
+    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
+    if (io->active && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    const vfik_io d = st.device_io();
+    vfik_goto_js_opts od = *o;
+    od.arrived = static_cast<int32_t*>(st.extra(vfik::X_ARRIVED).dev);
+    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
+    od.q_out = st.extra(vfik::X_Q_OUT).dev;
+    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
+    od.diff = st.extra(vfik::X_DIFF).dev;
+    GotoJsRun r;
+    if ((rc = goto_js_begin(h, &d, &od, r)) != VFIK_OK) return rc;
+    int done = 0;
+    while (done < n_checks) {
+        if ((rc = goto_js_block(h, r, done)) != VFIK_OK) return rc;
+        ++done;
+        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
+            int32_t left = -1;
+            if ((rc = poll_pending(h, r.g, done, &left)) != VFIK_OK) return rc;
+            if (left == 0) break;   // everybody the caller lets run is there
+        }
+    }
+    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
+    IoStaging back = st;   // of pending and the trace the checks that ran
+    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
+    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
+    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (checks_run) *checks_run = done;
+    return VFIK_OK;
+}
+
+int vfik_follow_js(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o) {
+    int rc = follow_js_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    FollowJsRun r;
+    if ((rc = follow_js_begin(h, io, o, r)) != VFIK_OK) return rc;
+    for (int k = 0; k < r.g.n_checks; ++k)
+        if ((rc = follow_js_block(h, r, k)) != VFIK_OK) return rc;
+    return goto_end(h, r.g, r.g.n_checks);
+}
+
+// Host-pointer form, as vfik_follow_host: wayq copied in with the inputs
+int vfik_follow_js_host(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, int poll_checks, int* checks_run) {
+    int rc = follow_js_check(h, io, o);
+    if (rc != VFIK_OK) return rc;
+    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    const int n_checks = o->n_cycles / o->stride;
+    const size_t qrow = (size_t)h->B * h->n * h->esz, wrow = (size_t)h->B * sizeof(int32_t);
+    IoStaging st(*io, h->B, h->io_dims());
+    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
+    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
+    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
+    st.add(vfik::X_REACHED, o->reached, (size_t)h->B * o->n_way * sizeof(int32_t), false);
+    st.add(vfik::X_NEXT, o->next, wrow, false);
+    st.add(vfik::X_WAY_TRAJ, o->way_traj, (size_t)n_checks * wrow, true);
+    st.add(vfik::X_DIFF, o->diff, qrow, true);
+    st.add(vfik::X_WAYQ, const_cast<void*>(o->wayq), (size_t)o->n_way * qrow, false, false, true);
+    st.layout();
+    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
+    st.map(h->goto_stage.p);
+    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
+    // an arm without a list is kept out like a gated one: its output rows go in before the blocks then, too
+    bool kept_out = io->active != nullptr;
+    for (size_t b = 0, row = (size_t)o->n_way * h->n; b < (size_t)h->B && !kept_out; ++b)
+        kept_out = h->esz == 4 ? std::isnan(static_cast<const float*>(o->wayq)[b * row]) : std::isnan(static_cast<const double*>(o->wayq)[b * row]);
+    if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    const vfik_io d = st.device_io();
+    vfik_follow_js_opts od = *o;
+    od.wayq = st.extra(vfik::X_WAYQ).dev;
+    od.reached = static_cast<int32_t*>(st.extra(vfik::X_REACHED).dev);
+    od.next = static_cast<int32_t*>(st.extra(vfik::X_NEXT).dev);
+    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
+    od.q_out = st.extra(vfik::X_Q_OUT).dev;
+    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
+    od.diff = st.extra(vfik::X_DIFF).dev;
+    od.way_traj = static_cast<int32_t*>(st.extra(vfik::X_WAY_TRAJ).dev);
+    FollowJsRun r;
+    if ((rc = follow_js_begin(h, &d, &od, r)) != VFIK_OK) return rc;
+    int done = 0;
+    while (done < n_checks) {
+        if ((rc = follow_js_block(h, r, done)) != VFIK_OK) return rc;
+        ++done;
+        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
+            int32_t left = -1;
+            if ((rc = poll_pending(h, r.g, done, &left)) != VFIK_OK) return rc;
+            if (left == 0) break;   // every arm that takes part is at its last posture
+        }
+    }
+    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
+    IoStaging back = st;   // of pending and the traces the checks that ran
+    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
+    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
     back.extra(vfik::X_WAY_TRAJ).bytes = (size_t)done * wrow;
     if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));

@@ -1,5 +1,5 @@
 // vfik_io_layout.h -- the ONE description of vfik_io for the host-pointer call forms (vfik_step_host, vfik_rollout_host, vfik_goto_host,
-// vfik_follow_host, vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
+// vfik_follow_host, vfik_goto_js_host, vfik_follow_js_host, vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
 // vfik_abi.cpp does the copies, tests/c_host/io_layout.cpp checks the layout on the CPU.
 #pragma once
 
@@ -65,8 +65,8 @@ constexpr bool io_inputs_first() {
 }
 static_assert(io_inputs_first(), "IO_MEMBERS: the inputs come first");
 
-// what a call form stages beside vfik_io's members, behind io's: outputs, but for way16 -- an input that a form copies in with the inputs
-// of io, outside their contiguous prefix (in_bytes)
+// what a call form stages beside vfik_io's members, behind io's: outputs, but for way16 and wayq -- inputs that a form copies in with the
+// inputs of io, outside their contiguous prefix (in_bytes)
 enum IoExtra {
     X_Q_OUT,       // [B][n]            vfik_rollout_host's and vfik_goto_host's q_out
     X_ARRIVED,     // [B] int32         the rest: vfik_goto_opts
@@ -77,6 +77,8 @@ enum IoExtra {
     X_REACHED,     // [B][W] int32
     X_NEXT,        // [B] int32
     X_WAY_TRAJ,    // [n_checks][B] int32
+    X_DIFF,        // [B][n]            vfik_goto_js_opts' and vfik_follow_js_opts' diff
+    X_WAYQ,        // [B][W][n]         input, as X_WAY16: vfik_follow_js_opts
     N_IO_EXTRA
 };
 constexpr int N_STAGED = N_IO + N_IO_EXTRA;

@@ -566,6 +566,44 @@ struct FollowArgs {
     long Bpad;
 };
 hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream);
+// vfik_goto_js: ArriveArgs' sibling for the joint-space wait of set_ref_js (arrive_js_kernel, vfik_kernel.hip): the check reads the arm's row of
+// the reference the caller sent and the q row block k wrote, no distance row and no goal block.  k < 0: as ArriveArgs'.
+struct ArriveJsArgs {
+    int* arrived;               // [B] cycle index of the arm's first successful check, -1 = not yet
+    int* gate;                  // [B] the handle's gate, as ArriveArgs'
+    const int* active;          // [B] the caller's gate, or NULL = every arm
+    const void* ref;            // [B][n] io->q_ref as the caller sent it: a row that starts with NaN never arrives
+    const void* q_prev;         // [B][n] the q row block k read
+    void* q_now;                // [B][n] the q row block k wrote
+    void* diff;                 // [B][n] ref - q of every arm that ran block k, or NULL
+    int* pending;               // &pending[k]: zeroed on the stream in front of the call
+    double prec[VFIK_MAX_JOINTS];   // goal_precision per joint; entries at or beyond n are not read
+    int B, n, k, stride, hold;
+};
+hipError_t launch_arrive_js(int io_dtype, const ArriveJsArgs& g, hipStream_t stream);
+// vfik_follow_js: FollowArgs' sibling for arms that carry a LIST of postures (follow_js_kernel, vfik_kernel.hip).  The check that finds an arm at
+// posture next[b] notes the cycle in reached[b][next], advances next[b] and writes the following posture into the arm's row of `ref`, the
+// reference row of the handle that every block reads as io->q_ref.  k < 0: reached = -1, next = 0, len[b] = the arm's list length (leading rows of
+// wayq[b] whose first element is not NaN), gate[b] = the caller's gate && len > 0, and posture 0 -- for an arm kept out, NaN -- into `ref`.
+struct FollowJsArgs {
+    int* reached;               // [B][W] cycle index of the check that found the arm at posture w, -1 = not yet
+    int* next;                  // [B] postures reached so far = the index of the one under way
+    int* len;                   // [B] list lengths, a buffer of the handle: written by the k < 0 pass, read by every check
+    int* gate;                  // [B] the handle's gate, as ArriveArgs'
+    const int* active;          // [B] the caller's gate, or NULL = every arm
+    const void* wayq;           // [B][W][n] the postures in order
+    void* ref;                  // [B][n] the handle's reference row: the posture the arm is under way to, min(next, len - 1)
+    const void* q_prev;         // [B][n] the q row block k read
+    void* q_now;                // [B][n] the q row block k wrote
+    void* diff;                 // [B][n] ref - q of every arm that ran block k, or NULL
+    int* pending;               // &pending[k]: zeroed on the stream in front of the call
+    int* way_now;               // [B] row k of way_traj -- the posture this check was made against -- or NULL
+    const int* way_prev;        // [B] row k - 1 of way_traj, or NULL (no trace, or k = 0)
+    double prec[VFIK_MAX_JOINTS];       // at an arm's last posture
+    double via_prec[VFIK_MAX_JOINTS];   // at every posture before it
+    int B, n, W, k, stride, hold;
+};
+hipError_t launch_follow_js(int io_dtype, const FollowJsArgs& g, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

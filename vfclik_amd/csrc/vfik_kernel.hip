@@ -14,7 +14,7 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, arrive_kernel, follow_kernel.
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, arrive_kernel, follow_kernel, arrive_js_kernel, follow_js_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -2565,6 +2565,56 @@ __global__ void __launch_bounds__(256) arrive_kernel(const ArriveArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// vfik_goto_js: the wait of the reference's joint-space motion call, HandleJController.set_ref_js(js, wait, goal_precision)
+// (handlers.py:544-576), batched: it sends js to /jpctrl/ref and reads /bridge/encoders until
+//     ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
+// and returns (result, js - q).  arrive_kernel's sibling, one thread per arm after block k: `ref` is the arm's row of io->q_ref as the caller
+// sent it (not the clamped value the controller keeps), q the row the block integrated.  Both edges are computed as written, in double on the
+// io-typed values, both compares non-strict; NaN in q or in the row fails a compare, so it never arrives -- a row that starts with NaN (an arm
+// without a controller) included.  diff = (T)(ref - q) for every arm that ran the block; an arm that did not repeats its q row and keeps its
+// diff row.  Gate, hold, arrived and pending[k] as arrive_kernel.  The precisions come by value and are indexed by the uniform loop counter
+// alone: scalar loads from the kernel arguments.  No LDS, no scratch.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) arrive_js_kernel(const ArriveJsArgs g) {
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool under_way = false;
+    if (b < g.B) {
+        const bool ua = !g.active || g.active[b] != 0;
+        if (g.k < 0) {   // (uniform: the pass in front of block 0)
+            g.arrived[b] = -1;
+            g.gate[b] = ua ? 1 : 0;
+            return;
+        }
+        int arr = g.arrived[b];
+        T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
+        if (g.gate[b] == 0) {
+            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
+            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
+        } else {
+            const T* const rf = static_cast<const T*>(g.ref) + (long)b * g.n;
+            T* const df = g.diff ? static_cast<T*>(g.diff) + (long)b * g.n : nullptr;
+            bool ok = true;
+            for (int i = 0; i < g.n; ++i) {
+                const double r = (double)rf[i], q = (double)qn[i], p = g.prec[i];
+                ok = ok & ((r - p) <= q) & ((r + p) >= q);
+                if (df) df[i] = (T)(r - q);
+            }
+            if (arr < 0 && ok) {
+                arr = (g.k + 1) * g.stride - 1;
+                g.arrived[b] = arr;
+            }
+        }
+        g.gate[b] = (ua && !(g.hold && arr >= 0)) ? 1 : 0;
+        under_way = ua && arr < 0;
+    } else if (g.k < 0) {
+        return;
+    }
+    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Distance monitor of scripts/monitor_distance (monitor_distance:76-84,148-167), batched: for every arm
 // and every object frame it was told about (/dmonitor/objectsIn: the goal is object 0, obstacles
 // follow), the xyz distance between the tool pose and the object and the rotation angle between their
@@ -2905,6 +2955,75 @@ __global__ void __launch_bounds__(256) follow_kernel(const FollowArgs g) {
                     ++nx;
                     g.next[b] = nx;
                     if (nx < L) follow_goal_store<T>(goal, b, Qp, way + (long)nx * 16);
+                }
+            }
+        }
+        g.gate[b] = (in && !(g.hold && nx == L)) ? 1 : 0;
+        under_way = in && nx < L;
+    } else if (g.k < 0) {
+        return;
+    }
+    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
+}
+
+// ------------------------------------------------------------------------------------------------
+// vfik_follow_js: a script of set_ref_js calls -- home posture, pre-grasp posture, ... (handlers.py:544-576) -- as follow_kernel's state machine
+// with arrive_js_kernel's rule, for arms that carry a list of postures wayq[B][W][n].  `ref` is the reference row of the HANDLE that every block
+// reads as io->q_ref: it holds the posture the arm is under way to, min(next, len - 1), copied element by element from wayq, so the rule reads
+// the posture as the caller sent it.  An arm found at posture next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its
+// list goes on -- the following posture into its row.  At most one posture per check: the controller has not moved towards the new one yet.
+//   precision    via_prec while a posture follows, prec at the arm's last one;
+//   gate         the caller's && len > 0 && !(hold && next == len); an arm the gate kept out repeats its q and posture-index rows, keeps its diff;
+//   pending[k]   arms that take part and have next < len -- a wave ballot, one atomic add per wave;
+//   way_now[b]   the posture this check was made against: min(next, len - 1) on entry.
+// k < 0 (uniform): reached = -1, next = 0, len = leading rows of wayq[b] that do not start with NaN, the gate, and posture 0 into the arm's row --
+// NaN for an arm that does not take part: no controller, the io->q_ref convention.  No LDS, no scratch.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) follow_js_kernel(const FollowJsArgs g) {
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool under_way = false;
+    if (b < g.B) {
+        const bool ua = !g.active || g.active[b] != 0;
+        const T* const way = static_cast<const T*>(g.wayq) + (long)b * g.W * g.n;
+        T* const rf = static_cast<T*>(g.ref) + (long)b * g.n;
+        if (g.k < 0) {   // (uniform: the pass in front of block 0)
+            int L = 0;
+            while (L < g.W && way[(long)L * g.n] == way[(long)L * g.n]) ++L;
+            for (int w = 0; w < g.W; ++w) g.reached[(long)b * g.W + w] = -1;
+            g.next[b] = 0;
+            g.len[b] = L;
+            const bool in = ua && L > 0;
+            g.gate[b] = in ? 1 : 0;
+            for (int i = 0; i < g.n; ++i) rf[i] = in ? way[i] : (T)__builtin_nan("");
+            return;
+        }
+        const int L = g.len[b];
+        const bool in = ua && L > 0;
+        int nx = g.next[b];
+        T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
+        if (g.gate[b] == 0) {
+            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
+            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
+            if (g.way_prev) g.way_now[b] = g.way_prev[b];
+        } else {
+            if (g.way_now) g.way_now[b] = nx < L ? nx : L - 1;
+            T* const df = g.diff ? static_cast<T*>(g.diff) + (long)b * g.n : nullptr;
+            const bool last = nx >= L - 1;
+            bool ok = true;
+            for (int i = 0; i < g.n; ++i) {
+                const double r = (double)rf[i], q = (double)qn[i], p = last ? g.prec[i] : g.via_prec[i];
+                ok = ok & ((r - p) <= q) & ((r + p) >= q);
+                if (df) df[i] = (T)(r - q);
+            }
+            if (nx < L && ok) {
+                g.reached[(long)b * g.W + nx] = (g.k + 1) * g.stride - 1;
+                ++nx;
+                g.next[b] = nx;
+                if (nx < L) {
+                    const T* const nw = way + (long)nx * g.n;
+                    for (int i = 0; i < g.n; ++i) rf[i] = nw[i];
                 }
             }
         }
@@ -3836,6 +3955,20 @@ hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream) 
     const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
     if (io_dtype == 32) hipLaunchKernelGGL(follow_kernel<float>, grid, blk, 0, stream, g);
     else hipLaunchKernelGGL(follow_kernel<double>, grid, blk, 0, stream, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_arrive_js(int io_dtype, const ArriveJsArgs& g, hipStream_t stream) {
+    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
+    if (io_dtype == 32) hipLaunchKernelGGL(arrive_js_kernel<float>, grid, blk, 0, stream, g);
+    else hipLaunchKernelGGL(arrive_js_kernel<double>, grid, blk, 0, stream, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_follow_js(int io_dtype, const FollowJsArgs& g, hipStream_t stream) {
+    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
+    if (io_dtype == 32) hipLaunchKernelGGL(follow_js_kernel<float>, grid, blk, 0, stream, g);
+    else hipLaunchKernelGGL(follow_js_kernel<double>, grid, blk, 0, stream, g);
     return hipGetLastError();
 }
 }  // namespace vfik

@@ -84,6 +84,12 @@ def load_library(path=None):
         "vfik_follow_opts_size": (C.c_size_t, []),
         "vfik_follow": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowOpts)]),
         "vfik_follow_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowOpts), C.c_int, C.POINTER(C.c_int)]),
+        "vfik_goto_js_opts_size": (C.c_size_t, []),
+        "vfik_goto_js": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoJsOpts)]),
+        "vfik_goto_js_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.GotoJsOpts), C.c_int, C.POINTER(C.c_int)]),
+        "vfik_follow_js_opts_size": (C.c_size_t, []),
+        "vfik_follow_js": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowJsOpts)]),
+        "vfik_follow_js_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowJsOpts), C.c_int, C.POINTER(C.c_int)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -132,6 +138,10 @@ def load_library(path=None):
     if lib.vfik_follow_opts_size() != C.sizeof(_abi.FollowOpts):
         raise VfikError("struct layout mismatch: vfik_follow_opts is %d bytes in the library, %d in the Python mirror"
                         % (lib.vfik_follow_opts_size(), C.sizeof(_abi.FollowOpts)))
+    for name, size, mirror in (("vfik_goto_js_opts", lib.vfik_goto_js_opts_size(), _abi.GotoJsOpts),
+                               ("vfik_follow_js_opts", lib.vfik_follow_js_opts_size(), _abi.FollowJsOpts)):
+        if size != C.sizeof(mirror):
+            raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
         _lib = lib
     return lib
@@ -682,6 +692,147 @@ class Engine:
         self._chk(self.lib.vfik_follow_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
         out["checks_run"] = int(ran.value)
         for k in ("pending", "q_traj", "dist_traj", "way_traj"):
+            if k in out:
+                out[k] = out[k][:out["checks_run"]]
+        return out
+
+    # -- joint-space goto and posture lists (vfik_goto_js / vfik_follow_js: set_ref_js, handlers.py:544-576, for the batch) --------
+    def _js_precision(self, precision, name="precision"):
+        """goal_precision per joint as the library reads it: float64 (n,), each >= 0 and not NaN."""
+        p = np.ascontiguousarray(precision, dtype=np.float64)
+        if p.shape != (self.n,):
+            raise ValueError("%s must be a sequence of %d values (one per joint), got shape %s" % (name, self.n, p.shape))
+        return p
+
+    def _js_opts(self, cls, n_cycles, dt, stride, hold, clamp):
+        o = cls()
+        o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
+        o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
+        return o
+
+    def _check_dev(self, specs):
+        """Contiguity, dtype and shape of the device arrays of a goto / follow call: (name, array, shape or None, dtype name) each."""
+        for name, x, shape, dt_name in specs:
+            if x is None or isinstance(x, int):
+                continue
+            if not x.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            if str(x.dtype).split(".")[-1] != dt_name or (shape is not None and tuple(x.shape) != shape):
+                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
+
+    def goto_js(self, io, n_cycles, dt, precision, stride=1, hold=False, clamp=False, arrived=None, pending=None, q_out=None, q_traj=None,
+                diff=None):
+        """Drive the arms to the joint references ``io.q_ref`` and report arrival, asynchronously on the engine's stream (include/vfik.h:
+        vfik_goto_js): :meth:`goto`'s blocks, and after each one set_ref_js's rule ``(ref - precision <= q) & (ref + precision >= q)`` on
+        every joint.  ``precision``: a length-n sequence (host values), goal_precision per joint.  ``arrived``: int32 (B,), required;
+        ``pending``: int32 (n_checks,); ``q_out``, ``diff`` (B, n) -- ``ref - q`` of each arm's last check; ``q_traj`` (n_checks, B, n).  Torch
+        tensors on this device or raw addresses.  The mixer flag and weights are the caller's (joint control: ``mix_w = [0, 0, 1, 0, 0, 0]``
+        with ``F_MIXER``)."""
+        if arrived is None:
+            raise ValueError("goto_js needs arrived, an int32 (batch,) device array")
+        n_checks = int(n_cycles) // max(int(stride), 1)
+        ft = self.io_dtype.name
+        self._check_dev((("arrived", arrived, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
+                         ("q_out", q_out, (self.batch, self.n), ft), ("q_traj", q_traj, (n_checks, self.batch, self.n), ft),
+                         ("diff", diff, (self.batch, self.n), ft)))
+        prec = self._js_precision(precision)
+        o = self._js_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
+        o.prec = prec.ctypes.data
+        o.arrived, o.pending, o.q_out, o.q_traj, o.diff = _ptr(arrived), _ptr(pending), _ptr(q_out), _ptr(q_traj), _ptr(diff)
+        self._chk(self.lib.vfik_goto_js(self.h, C.byref(io), C.byref(o)))
+
+    def goto_js_host(self, q, q_ref, n_cycles, dt, precision, stride=1, hold=False, clamp=False, trajectory=False, poll=0, want=("qdot_out",),
+                     null_control=None, active=None, q_lo=None, q_hi=None):
+        """Host arrays in, host arrays out (vfik_goto_js_host; synchronous).  Returns what :meth:`goto_host` returns, with ``diff`` (B, n)
+        -- ``q_ref - q`` of every arm's last check, set_ref_js's ``difference`` -- and without ``dist_traj``: ``q``, ``arrived``, ``pending``,
+        ``checks_run``, the rows named in ``want`` and, with ``trajectory``, ``q_traj`` (checks_run, B, n).  A row of ``q_ref`` that starts
+        with NaN is an arm without a joint controller: it runs and never arrives."""
+        if q_ref is None:
+            raise ValueError("goto_js_host needs q_ref, the joint reference of every arm")
+        io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
+        prec = self._js_precision(precision)
+        o = self._js_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
+        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
+        out["q"] = keep["q"].copy()
+        out["arrived"] = np.full(self.batch, -1, dtype=np.int32)
+        out["pending"] = np.zeros(n_checks, dtype=np.int32)
+        out["diff"] = np.zeros((self.batch, self.n), dtype=self.io_dtype)
+        o.prec = prec.ctypes.data
+        o.q_out, o.arrived, o.pending, o.diff = out["q"].ctypes.data, out["arrived"].ctypes.data, out["pending"].ctypes.data, out["diff"].ctypes.data
+        if trajectory:
+            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
+            o.q_traj = out["q_traj"].ctypes.data
+        ran = C.c_int(0)
+        self._chk(self.lib.vfik_goto_js_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
+        out["checks_run"] = int(ran.value)
+        for k in ("pending", "q_traj"):
+            if k in out:
+                out[k] = out[k][:out["checks_run"]]
+        return out
+
+    def follow_js(self, io, wayq, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, reached=None, next=None,
+                  pending=None, q_out=None, q_traj=None, diff=None, way_traj=None, n_way=None):
+        """Drive every arm along its own list of postures, asynchronously on the engine's stream (include/vfik.h: vfik_follow_js):
+        :meth:`follow`'s state machine with :meth:`goto_js`'s rule.  ``wayq``: (B, W, n) of the engine's dtype; a row whose first element
+        is NaN ends the arm's list.  ``io.q_ref`` must be left out: the reference row belongs to the engine.  ``precision`` (length n) holds
+        at an arm's last posture, ``via_precision`` at those before it (None: ``precision``).  ``reached`` int32 (B, W) and ``next`` int32
+        (B,) are required; ``pending``, ``q_out``, ``q_traj``, ``diff`` as :meth:`goto_js`; ``way_traj``: int32 (n_checks, B).  Torch tensors
+        on this device, or raw addresses (``wayq`` then with ``n_way``)."""
+        if reached is None or next is None:
+            raise ValueError("follow_js needs reached, an int32 (batch, n_way) device array, and next, an int32 (batch,) one")
+        if not isinstance(wayq, int):
+            if wayq.dim() != 3 or wayq.shape[0] != self.batch or wayq.shape[2] != self.n:
+                raise ValueError("wayq must be (batch, n_way, %d), got %s" % (self.n, tuple(wayq.shape)))
+            if n_way is not None and n_way != wayq.shape[1]:
+                raise ValueError("wayq: %d postures per arm, n_way says %d" % (wayq.shape[1], n_way))
+            n_way = wayq.shape[1]
+        elif n_way is None:
+            raise ValueError("a raw wayq address needs n_way")
+        n_checks = int(n_cycles) // max(int(stride), 1)
+        ft = self.io_dtype.name
+        self._check_dev((("wayq", wayq, None, ft), ("reached", reached, (self.batch, n_way), "int32"), ("next", next, (self.batch,), "int32"),
+                         ("pending", pending, (n_checks,), "int32"), ("q_out", q_out, (self.batch, self.n), ft),
+                         ("q_traj", q_traj, (n_checks, self.batch, self.n), ft), ("diff", diff, (self.batch, self.n), ft),
+                         ("way_traj", way_traj, (n_checks, self.batch), "int32")))
+        prec = self._js_precision(precision)
+        via = None if via_precision is None else self._js_precision(via_precision, "via_precision")
+        o = self._js_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
+        o.prec, o.via_prec, o.n_way = prec.ctypes.data, (None if via is None else via.ctypes.data), int(n_way)
+        o.wayq, o.reached, o.next, o.pending = _ptr(wayq), _ptr(reached), _ptr(next), _ptr(pending)
+        o.q_out, o.q_traj, o.diff, o.way_traj = _ptr(q_out), _ptr(q_traj), _ptr(diff), _ptr(way_traj)
+        self._chk(self.lib.vfik_follow_js(self.h, C.byref(io), C.byref(o)))
+
+    def follow_js_host(self, q, wayq, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, trajectory=False,
+                       poll=0, want=("qdot_out",), null_control=None, active=None, q_lo=None, q_hi=None):
+        """Host arrays in, host arrays out (vfik_follow_js_host; synchronous).  ``wayq``: (B, W, n), converted to the engine's dtype; a row
+        that starts with NaN ends a list.  Returns what :meth:`goto_js_host` returns without ``arrived``, plus ``reached`` (B, W), ``next``
+        (B,) and, with ``trajectory``, ``way_traj`` (checks_run, B).  ``poll`` > 0 ends the call once every arm that takes part is at its
+        last posture."""
+        w = np.asarray(wayq)
+        if w.ndim != 3 or w.shape[0] != self.batch or w.shape[1] < 1 or w.shape[2] != self.n:
+            raise ValueError("wayq must be (batch, n_way, %d), got %s" % (self.n, w.shape))
+        w = np.ascontiguousarray(w, dtype=self.io_dtype)
+        io, out, keep = self._host_io(q, null_control, None, None, active, q_lo, q_hi, want)
+        prec = self._js_precision(precision)
+        via = None if via_precision is None else self._js_precision(via_precision, "via_precision")
+        o = self._js_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
+        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
+        out["q"] = keep["q"].copy()
+        out["reached"] = np.full((self.batch, w.shape[1]), -1, dtype=np.int32)
+        out["next"] = np.zeros(self.batch, dtype=np.int32)
+        out["pending"] = np.zeros(n_checks, dtype=np.int32)
+        out["diff"] = np.zeros((self.batch, self.n), dtype=self.io_dtype)
+        o.prec, o.via_prec, o.n_way = prec.ctypes.data, (None if via is None else via.ctypes.data), w.shape[1]
+        o.wayq, o.q_out, o.reached, o.next, o.pending, o.diff = (w.ctypes.data, out["q"].ctypes.data, out["reached"].ctypes.data,
+                                                                 out["next"].ctypes.data, out["pending"].ctypes.data, out["diff"].ctypes.data)
+        if trajectory:
+            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
+            out["way_traj"] = np.full((n_checks, self.batch), -1, dtype=np.int32)
+            o.q_traj, o.way_traj = out["q_traj"].ctypes.data, out["way_traj"].ctypes.data
+        ran = C.c_int(0)
+        self._chk(self.lib.vfik_follow_js_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
+        out["checks_run"] = int(ran.value)
+        for k in ("pending", "q_traj", "way_traj"):
             if k in out:
                 out[k] = out[k][:out["checks_run"]]
         return out

@@ -241,6 +241,19 @@ class ShardedEngine:
         qs_of, ways = self._rows(q, "q", global_rows), self._rows(np.asarray(way), "way", global_rows)
         return self._checked_host(lambda e, i, a: e.follow_host(qs_of[i], ways[i], n_cycles, dt, precision, **a), global_rows, kw)
 
+    def goto_js_host(self, q, q_ref, n_cycles, dt, precision, global_rows=True, **kw):
+        """Engine.goto_js_host over this rank's arms, as :meth:`goto_host`: ``q_ref`` is sharded with the arms, ``precision`` (one value
+        per joint) is shared; ``diff`` comes back in arm order beside ``q`` and ``arrived``."""
+        qs_of, refs = self._rows(q, "q", global_rows), self._rows(q_ref, "q_ref", global_rows)
+        return self._checked_host(lambda e, i, a: e.goto_js_host(qs_of[i], refs[i], n_cycles, dt, precision, **a), global_rows, kw)
+
+    def follow_js_host(self, q, wayq, n_cycles, dt, precision, global_rows=True, **kw):
+        """Engine.follow_js_host over this rank's arms, as :meth:`follow_host`: ``wayq`` (rows, W, n) is sharded with the arms, ``precision``
+        and ``via_precision`` are shared."""
+        import numpy as np
+        qs_of, ways = self._rows(q, "q", global_rows), self._rows(np.asarray(wayq), "wayq", global_rows)
+        return self._checked_host(lambda e, i, a: e.follow_js_host(qs_of[i], ways[i], n_cycles, dt, precision, **a), global_rows, kw)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
