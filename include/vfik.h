@@ -81,7 +81,18 @@ int vfik_set_speed_scale(vfik_handle* h, int first_arm, int n_arms, const double
 /* /tool (vf:321-326): 16 doubles row-major, shared by the batch (per_arm = 0) or tool16[B][16].  ONE tool for the batch keeps the
  * launches of an all-revolute chain on the kernels built for such chains (the lean and publishing-lean float32-I/O
  * variants apply it themselves); per-arm tools take the general variants.  A per-arm array whose rows are all equal IS a
- * shared tool and is stored as one (with the values rounded to the I/O type, as the per-arm image would hold them). */
+ * shared tool and is stored as one (with the values rounded to the I/O type, as the per-arm image would hold them).
+ *
+ * What a tool may be: ANY twelve numbers, as for KDL's frame product (vf:329-332).  Nothing is checked and nothing is assumed of the
+ * 3 x 3 block -- a tool read from a float32 file or typed with four decimals is off a rotation by 5e-8 ... 1e-4, and its transpose is
+ * NOT its inverse to the accuracy of the results: pose = flange * tool, the twist is shifted by p_flange - p_tip, and pose_no_tool is
+ * the flange frame, for every block.  The kernels that apply the shared tool themselves keep no flange value through the field and
+ * rebuild both from the tool pose with the block's INVERSE (the host's, in long double).  The rule for a block that cannot be inverted
+ * to working accuracy: a shared tool with max |Rtool Rtool^T - I| > VFIK_TOOL_MAX_DEFECT (1/16: no rigid hand), a singular or a
+ * non-finite block is not a tool of those kernels -- the handle takes the general variants (vfik_dh_pattern reports 0), which keep
+ * the flange frame and need no inverse.  One exception: chains of 10 joints and more recompose pose_no_tool's ROTATION from the tool
+ * pose on the general variants too (they have no registers to keep it), so with a block that has no inverse those nine entries are
+ * not finite; its position, pose and every qdot are right. */
 int vfik_set_tool(vfik_handle* h, const double* tool16, int per_arm);
 
 /* Field sets of arms [first_arm, first_arm + n_arms): the result of the add/remove bookkeeping of

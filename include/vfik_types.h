@@ -23,6 +23,8 @@ extern "C" {
 #define VFIK_MAX_JOINTS 16
 #define VFIK_MAX_PARAMS 17   /* type 1 carries frame16 + slow-down distance */
 #define VFIK_MIX_CHANNELS 6  /* bridge:593-596: vectorfield, null, joint, mechanism, xtra1, xtra2 */
+/* The largest max |Rtool Rtool^T - I| of a shared tool's 3 x 3 block that the kernels built for all-revolute chains serve (vfik_set_tool) */
+#define VFIK_TOOL_MAX_DEFECT 0.0625
 #define VFIK_NULL_CONTROLS 4 /* nullspace:137,144 "expects four-float-bottles" */
 /* Chains of 8 and more joints, the joint-limit task's projector (vfik_io.null_control in vfik.h): the rows of J are
  * taken in their order (v_x v_y v_z w_x w_y w_z); a row takes part when the squared length of its component orthogonal to the rows kept

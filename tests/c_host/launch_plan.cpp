@@ -36,6 +36,15 @@ int main() {
         a.tool_stride = get("tool", 0) ? a.Bpad : 0;
         a.plain = (int)get("plain", 1);
         a.dhp = (int)get("dhp", 0);
+        // The rule for a shared tool's 3 x 3 block (include/vfik.h, vfik_set_tool): tool_shear_e6 = s gives the identity with entry (0, 1) =
+        // s / 1e6, a block whose max |R R^T - I| is that entry; tool_flat = 1 zeroes the block's last column (no inverse).  A block the rule
+        // refuses is not a plain + tool handle: kconst_fill reports plain = 0 and no pattern for it, restated here.
+        if (kv.count("tool_shear_e6") || kv.count("tool_flat")) {
+            double tool12[12] = {1, 0, 0, 0.02, 0, 1, 0, -0.01, 0, 0, 1, 0.2}, c3[3];
+            tool12[1] = (double)get("tool_shear_e6", 0) / 1e6;
+            if (get("tool_flat", 0)) tool12[2] = tool12[6] = tool12[10] = 0.0;
+            if (!vfik::tool_block_serves_plain(tool12, c3)) a.plain = a.dhp = 0;
+        }
         a.mixw = ptr("mixw");
         a.wts = static_cast<const double*>(ptr("wts"));
         a.ext = ptr("ext");

@@ -8,7 +8,12 @@ mantissa where mpmath cannot be imported):
 
   * forward kinematics in chain.py's z-normal form, T = B[0] Jz(q_1) B[1] ... Jz(q_n) B[n], the doubles of chain.B and of q taken as exact;
   * the geometric Jacobian about the flange origin in the base frame, rows (v, w) as oracle_c.jacobian orders them;
-  * qdot = Wq Jw^T (Jw Jw^T + lambda^2 I)^-1 Wy tw with Jw = Wy J Wq (identity tool: the twist is taken at the flange).
+  * qdot = Wq Jw^T (Jw Jw^T + lambda^2 I)^-1 Wy tw with Jw = Wy J Wq (identity tool: the twist is taken at the flange);
+  * with a tool (16 doubles taken as exact, nothing assumed of its 3 x 3 block): the tool pose T_tip = T_flange Tool as a 3 x 4 product
+    (vf:321-332), AB = p_flange - p_tip, and the solve -- flange Jacobian, unchanged -- of the twist (v + w x AB, w)
+    (Twist.RefPoint, vf:456-459).  `pose` is then the tool pose and `pose_nt` the flange; the error unit of such a case is
+    cond u (max |qdot| + max |qdot_shift|), qdot_shift the solve of (w x AB, 0) alone (unit_scale): w x AB can cancel v.  The tools are
+    the named table TOOLS / tool() below; tests/test_oracle_tool.py and tests/test_gpu_tool.py hold the oracles and the kernels to it.
 
 The twist is an INPUT (the oracle's v6 for the same, already rounded inputs): what is held here is the kinematics and the solve.  The field
 evaluation is NOT well conditioned everywhere (decay orders up to 127, cancelling forces, normCart, the 1e-9 floors) and is held to a
@@ -19,7 +24,8 @@ singular values of Jw (numpy.linalg.svd of the rounded high-precision Jw), and t
 Results are returned as pairs of doubles (hi, lo) with hi + lo = the high-precision value to ~32 digits, so that `error` does not add the
 half ulp a reference rounded to one double would carry.
 
-The kinematics of a pose set and each solve are cached at module level: the kernel-family runs of one case share one reference.
+The kinematics of a pose set and each solve are cached at module level: the kernel-family runs of one case share one reference, and the
+tools of one pose set share one forward kinematics (the tool product and the solve are cached by pose set and tool name).
 
 The poses (make_case).  B = 192 arms = three waves = twenty-four groups of eight; arm b has pattern index p = b mod 24, kind p mod 6 and
 offset eps = EPS[p div 6], so that every eight consecutive arms hold every kind:
@@ -50,6 +56,7 @@ except ImportError:   # the fall-back: a 64-bit mantissa, u_ref = 2^-64 = u / 20
     _num, _sin, _cos = np.longdouble, np.sin, np.cos
     RESIDUAL_BAR = 64 * float(np.finfo(np.longdouble).eps)
 
+_HP = type(_num(0))
 U = 2.0 ** -53
 B_ARMS = 192
 EPS = (0.0, 1e-9, 1e-6, 1e-3)
@@ -162,8 +169,14 @@ def _fk_jac(chain, q):
     return X, J
 
 
-def _solve(J, n, tw, lam, wy, wq):
-    """one arm: (qdot [n], relative residual, Jw as doubles)"""
+def _asnum(x):
+    """a double taken as exact, or a value already in the high-precision type"""
+    return x if isinstance(x, _HP) else _num(float(x))
+
+
+def _solve(J, n, tw, lam, wy, wq, extra=None):
+    """one arm: (qdot [n], relative residual, Jw as doubles); with `extra`, a second twist solved by the same factorisation (one more
+    back-substitution), its qdot comes fourth"""
     wy = [_num(float(x)) for x in wy]
     wq = [_num(float(x)) for x in wq]
     Jw = [[wy[r] * J[r][i] * wq[i] for i in range(n)] for r in range(6)]
@@ -175,7 +188,7 @@ def _solve(J, n, tw, lam, wy, wq):
             for i in range(n):
                 s = s + Jw[r][i] * Jw[c][i]
             A[r][c] = A[c][r] = s + lam2 if r == c else s
-    rhs = [wy[r] * _num(float(tw[r])) for r in range(6)]
+    rhs = [wy[r] * _asnum(tw[r]) for r in range(6)]
     # LDL^T (A is symmetric positive definite, or semi-definite with a positive pivot sequence at lambda = 0 off the singularities)
     L = [[_num(0)] * 6 for _ in range(6)]
     d = [None] * 6
@@ -189,33 +202,45 @@ def _solve(J, n, tw, lam, wy, wq):
             for k in range(j):
                 t = t - L[i][k] * L[j][k] * d[k]
             L[i][j] = t / s
-    y = [None] * 6
-    for i in range(6):
-        s = rhs[i]
-        for k in range(i):
-            s = s - L[i][k] * y[k]
-        y[i] = s
-    for i in range(6):
-        y[i] = y[i] / d[i]
-    for i in range(5, -1, -1):
-        s = y[i]
-        for k in range(i + 1, 6):
-            s = s - L[k][i] * y[k]
-        y[i] = s
+
+    def back(rhs):
+        y = [None] * 6
+        for i in range(6):
+            s = rhs[i]
+            for k in range(i):
+                s = s - L[i][k] * y[k]
+            y[i] = s
+        for i in range(6):
+            y[i] = y[i] / d[i]
+        for i in range(5, -1, -1):
+            s = y[i]
+            for k in range(i + 1, 6):
+                s = s - L[k][i] * y[k]
+            y[i] = s
+        return y
+
+    def joints(y):
+        qd = []
+        for i in range(n):
+            s = _num(0)
+            for r in range(6):
+                s = s + Jw[r][i] * y[r]
+            qd.append(wq[i] * s)
+        return qd
+
+    y = back(rhs)
     res2 = nrm2 = _num(0)
     for r in range(6):
         s = -rhs[r]
         for c in range(6):
             s = s + A[r][c] * y[c]
         res2, nrm2 = res2 + s * s, nrm2 + rhs[r] * rhs[r]
-    qd = []
-    for i in range(n):
-        s = _num(0)
-        for r in range(6):
-            s = s + Jw[r][i] * y[r]
-        qd.append(wq[i] * s)
+    qd = joints(y)
     resid = math.sqrt(float(res2 / nrm2)) if nrm2 != 0 else 0.0
-    return qd, resid, [[float(x) for x in row] for row in Jw]
+    Jwd = [[float(x) for x in row] for row in Jw]
+    if extra is None:
+        return qd, resid, Jwd
+    return qd, resid, Jwd, joints(back([wy[r] * _asnum(extra[r]) for r in range(6)]))
 
 
 def _hilo(x):
@@ -236,34 +261,76 @@ def kinematics(key, chain, q):
     return kin
 
 
-def reference(key, chain, q, tw, lam, wy, wq, wkey):
+def _put(out, name, b, T):
+    for r in range(3):
+        for c in range(4):
+            out[name][b, 4 * r + c], out[name + "_lo"][b, 4 * r + c] = _hilo(T[r][c])
+
+
+def _arm(out, b, T, J, n, tw, lam, wy, wq, tool16):
+    """one arm's row of `out`.  With a tool (16 doubles taken as exact; nothing is assumed of its 3 x 3 block): the tool pose is the 3 x 4
+    product of the flange frame and the tool's rows 0..2, AB = p_flange - p_tip, and the solve -- flange Jacobian, unchanged -- takes the
+    twist (v + w x AB, w) (Twist.RefPoint, vf:456-459).  qshift: max |qdot| of the solve of (w x AB, 0) alone."""
+    if tool16 is None:
+        qd, out["resid"][b], Jw = _solve(J, n, tw, lam, wy, wq)
+        Tt = T
+    else:
+        Tt = _mul(T, _frame(np.asarray(tool16, dtype=np.float64).reshape(4, 4)))
+        AB = [T[k][3] - Tt[k][3] for k in range(3)]
+        v = [_num(float(x)) for x in tw[:3]]
+        w = [_num(float(x)) for x in tw[3:6]]
+        sh = [w[1] * AB[2] - w[2] * AB[1], w[2] * AB[0] - w[0] * AB[2], w[0] * AB[1] - w[1] * AB[0]]
+        zero = _num(0)
+        qd, out["resid"][b], Jw, qs = _solve(J, n, [v[0] + sh[0], v[1] + sh[1], v[2] + sh[2]] + w, lam, wy, wq, extra=sh + [zero] * 3)
+        out["qshift"][b] = max(abs(float(x)) for x in qs)
+    for i in range(n):
+        out["qdot"][b, i], out["qdot_lo"][b, i] = _hilo(qd[i])
+    _put(out, "pose", b, Tt)
+    _put(out, "pose_nt", b, T)
+    s = np.linalg.svd(np.array(Jw), compute_uv=False)
+    out["cond"][b] = (s[0] ** 2 + lam * lam) / (s[5] ** 2 + lam * lam)
+
+
+def _empty(B, n):
+    out = dict(qdot=np.zeros((B, n)), qdot_lo=np.zeros((B, n)), pose=np.zeros((B, 16)), pose_lo=np.zeros((B, 16)),
+               pose_nt=np.zeros((B, 16)), pose_nt_lo=np.zeros((B, 16)), cond=np.zeros(B), resid=np.zeros(B), qshift=np.zeros(B))
+    out["pose"][:, 15] = out["pose_nt"][:, 15] = 1.0
+    return out
+
+
+def reference(key, chain, q, tw, lam, wy, wq, wkey, tool=None, tname=None, arms=None):
     """The reference of one case.  key: the pose set's (see kinematics); tw (B, 6); wy (6,) or (B, 6), wq (n,) or (B, n); wkey names
-    the weights in the cache.  Returns dict(qdot, qdot_lo (B, n), pose, pose_lo (B, 16), cond (B,), resid (B,)), not to be written to."""
-    ck = (key, float(lam), wkey)
-    if ck in _SOL:
-        tw0, out = _SOL[ck]
+    the weights in the cache.  tool: None (the identity: the twist is taken at the flange), (16,) or (B, 16) doubles taken as exact,
+    and tname its name in the cache -- the tools of one pose set share one forward kinematics.  Returns dict(qdot, qdot_lo (B, n),
+    pose, pose_lo (the tool pose), pose_nt, pose_nt_lo (the flange) (B, 16), cond, resid, qshift (B,)), not to be written to.
+    arms: only these rows are computed (the others stay zero) and nothing is cached -- for an oracle too slow for the whole batch,
+    whose twists are its own."""
+    assert (tool is None) == (tname is None)
+    ck = (key, float(lam), wkey) if tool is None else (key, float(lam), wkey, tname)
+    if arms is None and ck in _SOL:
+        tw0, tool0, out = _SOL[ck]
         assert np.array_equal(tw0, tw), "reference(%r): another twist under the same key" % (ck,)
+        assert tool is None or np.array_equal(tool0, tool), "reference(%r): another tool under the same key" % (ck,)
         return out
     kin = kinematics(key, chain, q)
     B, n = len(kin), chain.n
     wy = np.broadcast_to(np.asarray(wy, dtype=np.float64), (B, 6))
     wq = np.broadcast_to(np.asarray(wq, dtype=np.float64)[..., :n], (B, n))
-    out = dict(qdot=np.zeros((B, n)), qdot_lo=np.zeros((B, n)), pose=np.zeros((B, 16)), pose_lo=np.zeros((B, 16)),
-               cond=np.zeros(B), resid=np.zeros(B))
-    out["pose"][:, 15] = 1.0
-    for b, (T, J) in enumerate(kin):
-        qd, out["resid"][b], Jw = _solve(J, n, tw[b], lam, wy[b], wq[b])
-        for i in range(n):
-            out["qdot"][b, i], out["qdot_lo"][b, i] = _hilo(qd[i])
-        for r in range(3):
-            for c in range(4):
-                out["pose"][b, 4 * r + c], out["pose_lo"][b, 4 * r + c] = _hilo(T[r][c])
-        s = np.linalg.svd(np.array(Jw), compute_uv=False)
-        out["cond"][b] = (s[0] ** 2 + lam * lam) / (s[5] ** 2 + lam * lam)
+    tools = None if tool is None else np.broadcast_to(np.asarray(tool, dtype=np.float64), (B, 16))
+    out = _empty(B, n)
+    for b in (range(B) if arms is None else arms):
+        T, J = kin[b]
+        _arm(out, b, T, J, n, tw[b], lam, wy[b], wq[b], None if tools is None else tools[b])
     for v in out.values():
         v.setflags(write=False)
-    _SOL[ck] = (np.array(tw, dtype=np.float64), out)
+    if arms is None:
+        _SOL[ck] = (np.array(tw, dtype=np.float64), None if tool is None else np.array(tool, dtype=np.float64), out)
     return out
+
+
+def unit_scale(ref):
+    """per arm: max |qdot| + max |qdot_shift| -- w x AB can cancel v, and the error of either part stays (0 more without a tool)"""
+    return np.abs(ref["qdot"]).max(axis=1) + ref["qshift"]
 
 
 def error(got, ref, name):
@@ -274,7 +341,7 @@ def error(got, ref, name):
 def ratio(got_qdot, ref):
     """per arm: max_i |got - reference| / (cond u max_i |qdot|) -- the error in units of what the conditioning allows"""
     err = error(got_qdot, ref, "qdot").max(axis=1)
-    scale = ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1)
+    scale = ref["cond"] * U * unit_scale(ref)
     return err / scale, err
 
 
@@ -282,7 +349,7 @@ def ratio(got_qdot, ref):
 def bars(ref, io_dtype, R):
     """(B, n) bar of qdot against the reference of one case; R: the oracle's worst ratio on it"""
     K = K_MARGIN * max(1.0, R)
-    arm = np.maximum(S_BAR[io_dtype], K * ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1))
+    arm = np.maximum(S_BAR[io_dtype], K * ref["cond"] * U * unit_scale(ref))
     bar = np.repeat(arm[:, None], ref["qdot"].shape[1], axis=1)
     if io_dtype == np.float32:
         bar = bar + 2.0 ** -24 * np.abs(ref["qdot"])
@@ -296,7 +363,7 @@ def check_qdot(got, ref, io_dtype, R, what, kinds, eps, failures, row=None):
     err = error(got, ref, "qdot")
     bar = bars(ref, io_dtype, R)
     store = 2.0 ** -24 * np.abs(ref["qdot"]) if io_dtype == np.float32 else 0.0
-    rat = (np.maximum(err - store, 0.0)).max(axis=1) / (ref["cond"] * U * np.abs(ref["qdot"]).max(axis=1))
+    rat = (np.maximum(err - store, 0.0)).max(axis=1) / (ref["cond"] * U * unit_scale(ref))
     b = int(np.argmax(rat))
     over = err / bar
     wb = int(np.argmax(over.max(axis=1)))
@@ -323,6 +390,107 @@ def oracle_case(oc, robot, io_dtype, lam, wname, poses):
     ref = reference((robot, np.dtype(io_dtype).name, poses), chain, w["q"], orc["v6"], lam, wy, wq, wname)
     R = float(ratio(orc["qdot_vf"], ref)[0].max())
     return chain, params, w, kinds, eps, orc, ref, R
+
+
+# ---- the tools (tests/test_oracle_tool.py, tests/test_gpu_tool.py) ---------------------------------------------------------------------
+# Each from one construction, then rounded as stated.  `kind` names the band of the defect max |Rtool Rtool^T - I| (DEFECT_BANDS):
+# a later edit cannot quietly make every tool orthonormal again.
+TOOLS = ("hand", "turned", "long", "f32", "typed4", "typed3", "rows", "per-arm", "flat")
+PER_ARM_OF = ("hand", "turned", "long", "f32", "typed4", "typed3")   # arm b of `per-arm` takes tool b mod 6 of these
+DEFECT_BANDS = {"exact": (0.0, 1e-15), "f32": (1e-8, 1e-7), "typed": (1e-5, 1e-3), "singular": (0.0625, 1.5)}   # (singular: beyond VFIK_TOOL_MAX_DEFECT, include/vfik.h)
+TOOL_KIND = {"hand": "exact", "turned": "exact", "long": "exact", "f32": "f32", "typed4": "typed", "typed3": "typed", "rows": "typed",
+             "flat": "singular"}
+
+
+def _turned():
+    """2.5 rad about (1, 2, 3) / sqrt(14), in doubles (Rodrigues): strongly non-symmetric"""
+    a = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return math.cos(2.5) * np.eye(3) + math.sin(2.5) * K + (1.0 - math.cos(2.5)) * np.outer(a, a)
+
+
+def _tool16(R, t):
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return T.reshape(16)
+
+
+def tool(name, io_dtype, B=B_ARMS):
+    """(what set_tool gets, per_arm, what the oracle and the reference get) of a tool of the table.
+
+      hand     identity rotation, t = (0, 0, 0.2) (old/README.old:84)
+      turned   _turned(), t = (0.02, -0.01, 0.2)
+      long     turned's rotation, t = (0.3, -0.4, 1.0): the lever is longer than the arm, the point shift dominates v
+      f32      turned, every entry rounded to float32 -- given to BOTH I/O types
+      typed4   turned, every entry rounded to 4 decimals;   typed3: to 3 decimals
+      rows     typed4 as (B, 16) equal rows, per_arm: the library stores it as the shared tool, rounded to the I/O type (the reference
+               gets the rounded values)
+      per-arm  arm b takes tool b mod 6 of the above plus a seeded offset in +-0.5 m per axis, rounded to the I/O type
+      flat     turned with the last column of its 3 x 3 block zero: a block that has no inverse"""
+    R, t = _turned(), np.array([0.02, -0.01, 0.2])
+    if name == "hand":
+        T = _tool16(np.eye(3), [0.0, 0.0, 0.2])
+    elif name == "turned":
+        T = _tool16(R, t)
+    elif name == "long":
+        T = _tool16(R, [0.3, -0.4, 1.0])
+    elif name == "f32":
+        T = _tool16(R, t).astype(np.float32).astype(np.float64)
+    elif name in ("typed4", "typed3", "rows"):
+        T = np.round(_tool16(R, t), 3 if name == "typed3" else 4)
+    elif name == "flat":
+        T = _tool16(R, t)
+        T[[2, 6, 10]] = 0.0
+    else:
+        assert name == "per-arm"
+        T = np.stack([tool(PER_ARM_OF[b % 6], io_dtype)[2] for b in range(B)])
+        T[:, [3, 7, 11]] += np.random.default_rng(41).uniform(-0.5, 0.5, (B, 3))
+        T = T.astype(io_dtype).astype(np.float64)
+        return T, True, T
+    if name == "rows":
+        return np.tile(T, (B, 1)), True, T.astype(io_dtype).astype(np.float64)
+    return T, False, T
+
+
+def defect(T16):
+    """max |Rtool Rtool^T - I| of a tool (16,) or of each row of (B, 16)"""
+    R = np.asarray(T16, dtype=np.float64).reshape(-1, 4, 4)[:, :3, :3]
+    return np.abs(R @ R.transpose(0, 2, 1) - np.eye(3)).max(axis=(1, 2))
+
+
+def per_arm_kinds(io_dtype, B=B_ARMS):
+    """the band of each row of `per-arm`: an exact row rounded to float32 I/O is an `f32` row"""
+    k = [TOOL_KIND[PER_ARM_OF[b % 6]] for b in range(B)]
+    return ["f32" if (x == "exact" and io_dtype == np.float32 and PER_ARM_OF[b % 6] != "hand") else x for b, x in enumerate(k)]
+
+
+def oracle_tool_case(oc, robot, io_dtype, lam, tname, poses="mixed", chain=None):
+    """oracle_case with a tool of the table, unit weights: (chain, params, workload, kinds, eps, oracle outputs, reference, R, tool triple).
+    chain: a Chain of the caller's (regular poses) under the name `robot`."""
+    from vfclik_amd import _abi, synth
+    if chain is None:
+        chain, w, kinds, eps = make_case(robot, io_dtype, poses)
+    else:
+        assert poses == "regular"
+        w = synth.make_workload(chain, B_ARMS, 2, seed=3, io_dtype=io_dtype)
+        kinds, eps = np.full(B_ARMS, 5), np.zeros(B_ARMS)
+    wy, wq = weights("unit", chain.n)
+    params = _abi.default_params(**{"lambda": lam})
+    tl = None if tname is None else tool(tname, io_dtype)
+    orc = oc.cycle_batch(chain, params, w["q"], w["fields"], w["nfields"], tool=None if tl is None else tl[2],
+                         want=("qdot_vf", "qdot_out", "pose", "pose_nt", "v6", "status"))
+    ref = reference((robot, np.dtype(io_dtype).name, poses), chain, w["q"], orc["v6"], lam, wy, wq, "unit",
+                    tool=None if tl is None else tl[2], tname=tname)
+    R = float(ratio(orc["qdot_vf"], ref)[0].max())
+    return chain, params, w, kinds, eps, orc, ref, R, tl
+
+
+def tool_cases():
+    """(robot, lambda, tool) of the tool tests"""
+    out = [("lwr", 0.1, t) for t in TOOLS] + [("lwr", 1e-3, t) for t in ("turned", "typed4")]
+    for robot in ("powercube6", "lwr_dual14"):
+        out += [(robot, 0.1, t) for t in ("turned", "long", "typed4", "per-arm")]
+    return out
 
 
 def cases():

@@ -66,6 +66,21 @@ ROUTES = [
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, true, 5> grid=256 block=256 lds=80896'),
     ('nj=7 io=32 B=65536 dhp=1 plain=4',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 7> grid=256 block=256 lds=80896'),
+    # the rule for a shared tool's 3 x 3 block (include/vfik.h, vfik_set_tool; the driver restates kconst_fill's use of it): a block off a rotation
+    # by 1e-4 (typed with four decimals), and one at 0.062 -- below VFIK_TOOL_MAX_DEFECT = 1/16 -- stay plain + tool handles ...
+    ('nj=7 io=32 B=65536 dhp=1 plain=2 tool_shear_e6=100',
+     'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 3> grid=256 block=256 lds=80896'),
+    ('nj=7 io=32 B=65536 dhp=1 plain=2 tool_shear_e6=62000',
+     'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 3> grid=256 block=256 lds=80896'),
+    # ... one beyond it, and a block without an inverse (last column zero), take the general variants, which need no inverse
+    ('nj=7 io=32 B=65536 dhp=1 plain=2 tool_shear_e6=63000',
+     'cycle_kernel_x<float, 7, false, false, false, true, 0, -1, false, false, 1, false, false, 0> grid=256 block=256 lds=117760'),
+    ('nj=7 io=32 B=65536 dhp=1 plain=2 tool_flat=1',
+     'cycle_kernel_x<float, 7, false, false, false, true, 0, -1, false, false, 1, false, false, 0> grid=256 block=256 lds=117760'),
+    ('nj=7 io=64 B=64 pose=1 pose_nt=1 dhp=1 plain=2 tool_shear_e6=100',
+     'cycle_sub8_kernel_x<double, 7, false, 3> grid=8 block=64 lds=8192'),
+    ('nj=7 io=64 B=64 pose=1 pose_nt=1 dhp=1 plain=2 tool_flat=1',
+     'cycle_kernel_x<double, 7, false, false, false, true, 0, -1, false, false, 1, false, false, 0> grid=1 block=256 lds=161792'),
     ('nj=7 io=32 B=65536 dhp=0 plain=2',
      'cycle_kernel_x<float, 7, false, false, false, true, 0, -1, false, false, 1, false, false, 0> grid=256 block=256 lds=117760'),
     ('nj=7 io=32 B=131072 dhp=1',

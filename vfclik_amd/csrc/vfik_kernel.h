@@ -482,6 +482,31 @@ inline std::string cycle_kernel_name(const CyclePlan& p, int nj, int io_bits, bo
     }
 }
 
+// Whether a shared tool (rows 0..2 of the 4 x 4, row-major 3 x 4) can ride on the PLAIN kernels' TOOLC variants, which rebuild the lever arm
+// p_ee - p_tip = -Rt (Rtool^-1 t) and /pose_no_tool from the tool pose: its 3 x 3 block must be invertible to working accuracy --
+// max |Rtool Rtool^T - I| <= VFIK_TOOL_MAX_DEFECT (include/vfik.h states the rule); a block with a larger defect, a singular or a non-finite
+// one is not a plain + tool handle (kconst_fill then reports plain = 0: the general variants, which keep the flange frame).
+// c3 = Rtool^-1 t by cofactors in long double (zeros when the answer is no).  Host code.
+inline bool tool_block_serves_plain(const double* tool12, double* c3) {
+    const long double a = tool12[0], b = tool12[1], c = tool12[2], d = tool12[4], e = tool12[5], f = tool12[6], g = tool12[8], h = tool12[9], i = tool12[10];
+    const long double t[3] = {tool12[3], tool12[7], tool12[11]};
+    const long double co[9] = {e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d};
+    const long double det = a * co[0] + b * co[3] + c * co[6];
+    long double defect = 0.0L;
+    bool finite = true;
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) {
+            long double s = r == k ? -1.0L : 0.0L;
+            for (int m = 0; m < 3; ++m) s += (long double)tool12[4 * r + m] * (long double)tool12[4 * k + m];
+            s = s < 0.0L ? -s : s;
+            finite = finite && s == s;
+            defect = s > defect ? s : defect;
+        }
+    const bool ok = finite && defect <= (long double)VFIK_TOOL_MAX_DEFECT && det != 0.0L;
+    for (int j = 0; j < 3; ++j) c3[j] = ok ? (double)((co[3 * j] * t[0] + co[3 * j + 1] * t[1] + co[3 * j + 2] * t[2]) / det) : 0.0;
+    return ok;
+}
+
 // Type-erased launchers (implemented in vfik_kernel.hip).  kargs points to a KArgs<nj>.
 uint32_t supported_joints_mask();
 // *plan (may be NULL) receives the launch's plan -- which instantiation it took (cycle_kernel_name), the eight-lanes-per-arm kernel among them

@@ -55,6 +55,31 @@ __device__ __forceinline__ double rcp_nr(double x) {  // 1/x, ~1 ulp, x normal a
     return __builtin_fma(y, e, y);
 }
 
+// The flange rotation from the tool pose, Rf = Rt Rtool^-1 (tl: rows 0..2 of the tool, row-major 3 x 4), where /pose_no_tool recomposes it.
+// NOT Rt Rtool^T: a tool read from a float32 file or typed with four decimals is off a rotation by 5e-8 ... 1e-4, and the reference's frame
+// product (KDL) assumes nothing of the nine numbers.  The inverse by cofactors, then row by row: a row of Rt dies as its row of Rf is formed,
+// and the barriers keep the scheduler from interleaving the two phases (the long chains' variants have no registers for both at once).
+// Good to a few ulp times the block's condition number -- the published frame is held to 1e-9.  A block without an inverse gives non-finite values.
+__device__ __forceinline__ void flange_rotation(const double* Rt, const double* tl, double* Rf) {
+    const double a = tl[0], b = tl[1], c = tl[2], d = tl[4], e = tl[5], f = tl[6], g = tl[8], h = tl[9], i = tl[10];
+    double ti[9];
+    ti[0] = __builtin_fma(e, i, -(f * h)); ti[3] = __builtin_fma(f, g, -(d * i)); ti[6] = __builtin_fma(d, h, -(e * g));
+    const double r = rcp_nr(a * ti[0] + b * ti[3] + c * ti[6]);
+    ti[1] = __builtin_fma(c, h, -(b * i)); ti[2] = __builtin_fma(b, f, -(c * e));
+    ti[4] = __builtin_fma(a, i, -(c * g)); ti[5] = __builtin_fma(c, d, -(a * f));
+    ti[7] = __builtin_fma(b, g, -(a * h)); ti[8] = __builtin_fma(a, e, -(b * d));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ti[k] *= r;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double x = Rt[3 * q], y = Rt[3 * q + 1], z = Rt[3 * q + 2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Rf[3 * q + k] = x * ti[k] + y * ti[3 + k] + z * ti[6 + k];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // 1/sqrt(x) from ONE Newton step on v_rsq_f64 (5 instructions): the decay repellers' 1 / D, which is raised to the decay order (up to 127).
 // The step's error is measured directly by tools/ubench_rsqrt.hip (figures in DESIGN 6.2).  An error COMMON to the slots of one order is
 // a common factor of their terms and leaves a normalised sum unchanged but for the goal's share; tests/test_gpu_field_edges.py bounds
@@ -1383,7 +1408,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // ---------------- A4: tool offset (vf:321-332) --------------------------------------------
     double Rt[9], pt[3], rr[3];
     // (TOOLC: the batch's shared tool on the PLAIN kernel.  The flange frame dies here either way: the point shift of the twist (below)
-    // and /pose_no_tool (epilogue) are formed from the tool pose and the tool's constants.)
+    // and /pose_no_tool (epilogue) are formed from the tool pose and the tool's constants -- with the block's INVERSE, never its transpose.)
     if (PLAIN) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) Rt[k] = R[k];
@@ -1926,10 +1951,11 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     tw[1] = PLAIN ? v[1] : v[1] + (w[2] * rr[0] - w[0] * rr[2]);
     tw[2] = PLAIN ? v[2] : v[2] + (w[0] * rr[1] - w[1] * rr[0]);
     if constexpr (PLAIN) {
-        if constexpr (TOOLC) {  // p_ee - p_tip = -R t = -Rt (Rtool^T t): from the tool pose, so that nothing of the flange frame lives through the field
+        if constexpr (TOOLC) {  // p_ee - p_tip = -R t = -Rt (Rtool^-1 t): from the tool pose, so that nothing of the flange frame lives through the field
+            // (c3 = Rtool^-1 t is the host's, formed in long double: KConst::dh[2..4].pad)
             double c3[3], r3[3];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) c3[j] = HOTK(tool[j]) * HOTK(tool[3]) + HOTK(tool[4 + j]) * HOTK(tool[7]) + HOTK(tool[8 + j]) * HOTK(tool[11]);
+            for (int j = 0; j < 3; ++j) c3[j] = HOTK(dh[2 + j].pad);
 #pragma unroll
             for (int r = 0; r < 3; ++r) r3[r] = -(Rt[3 * r] * c3[0] + Rt[3 * r + 1] * c3[1] + Rt[3 * r + 2] * c3[2]);
             tw[0] += w[1] * r3[2] - w[2] * r3[1];
@@ -2275,7 +2301,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             });
         if (a.pose_nt) {
             if constexpr (!PLAIN && NJ >= 10) {
-                // Long chains: the flange frame is recomposed from the tool pose, R = Rt Rtool^T and p = pt + (p_ee - p_tip),
+                // Long chains: the flange frame is recomposed from the tool pose, R = Rt Rtool^-1 and p = pt + (p_ee - p_tip),
                 // instead of living in 12 double registers through the field and the IK beside Rt / pt (scratch otherwise).
                 double tl[12];
                 if (a.tool_stride) {
@@ -2286,30 +2312,25 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                     for (int k = 0; k < 12; ++k) tl[k] = kc->tool[k];
                 }
                 double Rf[9];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) Rf[3 * r + c] = Rt[3 * r] * tl[4 * c] + Rt[3 * r + 1] * tl[4 * c + 1] + Rt[3 * r + 2] * tl[4 * c + 2];
+                flange_rotation(Rt, tl, Rf);
                 put_rows(a.pose_nt, std::integral_constant<int, 16>(), [&](int i) {
                     return i < 12 ? ((i & 3) == 3 ? pt[i >> 2] + rr[i >> 2] : Rf[3 * (i >> 2) + (i & 3)]) : (i == 15 ? 1.0 : 0.0);
                 });
             } else if constexpr (PLAIN) {
                 // (the tool pose IS the flange pose without a tool; with the batch's shared tool -- TOOLC -- the flange frame is recomposed,
-                // R = Rt Rtool^T and p = pt - R t)
+                // R = Rt Rtool^-1 and p = pt - R t = pt - Rt c3)
                 double Rf[9], pf[3];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) Rf[k] = Rt[k];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) pf[k] = pt[k];
                 if constexpr (TOOLC) {
+                    double tl[12];
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) {
+                    for (int k = 0; k < 12; ++k) tl[k] = HOTK(tool[k]);
+                    flange_rotation(Rt, tl, Rf);
 #pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            Rf[3 * r + c] = Rt[3 * r] * HOTK(tool[4 * c]) + Rt[3 * r + 1] * HOTK(tool[4 * c + 1]) + Rt[3 * r + 2] * HOTK(tool[4 * c + 2]);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) pf[r] = pt[r] - (Rf[3 * r] * HOTK(tool[3]) + Rf[3 * r + 1] * HOTK(tool[7]) + Rf[3 * r + 2] * HOTK(tool[11]));
+                    for (int r = 0; r < 3; ++r) pf[r] = pt[r] - (Rt[3 * r] * HOTK(dh[2].pad) + Rt[3 * r + 1] * HOTK(dh[3].pad) + Rt[3 * r + 2] * HOTK(dh[4].pad));
                 }
                 put_rows(a.pose_nt, std::integral_constant<int, 16>(), [&](int i) {
                     return i < 12 ? ((i & 3) == 3 ? pf[i >> 2] : Rf[3 * (i >> 2) + (i & 3)]) : (i == 15 ? 1.0 : 0.0);
@@ -3188,7 +3209,7 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
         const double cx = Jm[i][4] * dz - Jm[i][5] * dy, cy = Jm[i][5] * dx - Jm[i][3] * dz, cz = Jm[i][3] * dy - Jm[i][4] * dx;
         Jm[i][0] = cx; Jm[i][1] = cy; Jm[i][2] = cz;
     }
-    if constexpr (TOOLC) {   // A4 (vf:321-332): the field is evaluated at the tool pose; the flange frame is recomposed where /pose_no_tool asks for it
+    if constexpr (TOOLC) {   // A4 (vf:321-332): the field is evaluated at the tool pose; the flange frame is recomposed (Rtool^-1) where /pose_no_tool asks for it
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const double x = R[3 * r], y = R[3 * r + 1], z = R[3 * r + 2];
@@ -3235,10 +3256,10 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { tw[k] = tot[k] * kt; tw[3 + k] = tot[3 + k] * kr; }
     }
-    if constexpr (TOOLC) {  // A6 (vf:456-459): the twist at the flange, shifted by p_ee - p_tip = -Rt (Rtool^T t)
+    if constexpr (TOOLC) {  // A6 (vf:456-459): the twist at the flange, shifted by p_ee - p_tip = -Rt (Rtool^-1 t) (the host's c3, as in cycle_body)
         double c3[3], r3[3];
 #pragma unroll
-        for (int jx = 0; jx < 3; ++jx) c3[jx] = kc->tool[jx] * kc->tool[3] + kc->tool[4 + jx] * kc->tool[7] + kc->tool[8 + jx] * kc->tool[11];
+        for (int jx = 0; jx < 3; ++jx) c3[jx] = kc->dh[2 + jx].pad;
 #pragma unroll
         for (int r = 0; r < 3; ++r) r3[r] = -(R[3 * r] * c3[0] + R[3 * r + 1] * c3[1] + R[3 * r + 2] * c3[2]);
         tw[0] += tw[4] * r3[2] - tw[5] * r3[1];
@@ -3400,19 +3421,16 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
                 for (int i = 0; i < 16; ++i) o[i] = fr[i];
             }
             if (a.pose_nt) {
-                if constexpr (TOOLC) {   // the flange frame: R = Rt Rtool^T, p = pt - R t
-                    double Rf[9];
+                if constexpr (TOOLC) {   // the flange frame: R = Rt Rtool^-1, p = pt - R t = pt - Rt c3
+                    double tl[12], Rf[9];
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            Rf[3 * r + c] = R[3 * r] * kc->tool[4 * c] + R[3 * r + 1] * kc->tool[4 * c + 1] + R[3 * r + 2] * kc->tool[4 * c + 2];
-                    }
+                    for (int k = 0; k < 12; ++k) tl[k] = kc->tool[k];
+                    flange_rotation(R, tl, Rf);
 #pragma unroll
                     for (int r = 0; r < 3; ++r) {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) fr[4 * r + c] = (T)Rf[3 * r + c];
-                        fr[4 * r + 3] = (T)(p[r] - (Rf[3 * r] * kc->tool[3] + Rf[3 * r + 1] * kc->tool[7] + Rf[3 * r + 2] * kc->tool[11]));
+                        fr[4 * r + 3] = (T)(p[r] - (R[3 * r] * kc->dh[2].pad + R[3 * r + 1] * kc->dh[3].pad + R[3 * r + 2] * kc->dh[4].pad));
                     }
                 }
                 T* o = static_cast<T*>(a.pose_nt) + (long)arm * 16;
@@ -3762,6 +3780,15 @@ double kconst_fill_t(void* dst, const vfik_chain& ch, const vfik_params& p, cons
     for (int i = 0; i < 6; ++i) c.wy[i] = p.wy[i];
     for (int i = 0; i < VFIK_MIX_CHANNELS; ++i) c.mix_w[i] = p.mix_w[i];
     for (int k = 0; k < 12; ++k) c.tool[k] = tool12[k];
+    // The shared tool on the PLAIN kernels (TOOLC): they keep no flange value through the field and rebuild the lever arm p_ee - p_tip =
+    // -Rt (Rtool^-1 t) and /pose_no_tool from the tool pose.  c3 = Rtool^-1 t is formed here, in long double by cofactors, and rides in
+    // dh[2..4].pad (no member moves); the block must be invertible to working accuracy for that -- the rule of include/vfik.h:
+    // max |Rtool Rtool^T - I| <= VFIK_TOOL_MAX_DEFECT, else the handle takes the general variants, which keep the flange frame itself
+    // (vfik_kernel.h: tool_block_serves_plain).
+    static_assert(NJ >= 5, "KConst::dh[2..4].pad");
+    double c3[3];
+    const bool tool_block_ok = tool_block_serves_plain(tool12, c3);
+    for (int j = 0; j < 3; ++j) c.dh[2 + j].pad = c3[j];
     c.speed = p.speed_scale;
     c.lambda2 = p.lambda * p.lambda;
     c.rot_slow = p.rot_slowdown;
@@ -3778,7 +3805,7 @@ double kconst_fill_t(void* dst, const vfik_chain& ch, const vfik_params& p, cons
     // is not the identity ? 1 : 0) + (its IK weights are not all one ? 2 : 0): the lean float32 kernels and the eight-lanes kernel have
     // variants that apply a shared tool and shared weights themselves (cycle_body: TOOLC, WTSC), every other launch of such a handle takes
     // the general variants (plan_cycle).
-    bool pl = c.prismatic_mask == 0 && c.tail_c == 1.0 && c.tail_s == 0.0 && c.tail_e == 0.0;
+    bool pl = c.prismatic_mask == 0 && c.tail_c == 1.0 && c.tail_s == 0.0 && c.tail_e == 0.0 && tool_block_ok;
     static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     bool tool_ident = true;
     for (int k = 0; k < 12; ++k) tool_ident = tool_ident && tool12[k] == ident[k];
