@@ -345,7 +345,7 @@ int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, i
 /* Waypoint lists.  A user of the reference never makes just one gotoFrame call: a pick-and-place script is a list of them -- approach pose, grasp
  * pose, lift pose, place pose -- and the next frame goes out the moment the previous call returned true (handlers.py:346-387).  vfik_follow is
  * vfik_goto for arms that each carry their own list of goal frames, way16[B][W][16]: the same blocks of `stride` cycles, the same gate, and after
- * every block one small kernel (follow_kernel) that applies vfik_goto's arrival rule -- the same distance row, both compares strict and in
+ * every block one small kernel (check_kernel<T, JOINT, LIST>, here <T, 0, 1>) that applies vfik_goto's arrival rule -- the same distance row, both compares strict and in
  * double, NaN never arrives, an arm without a goal block never arrives -- and, for an arm it finds at its waypoint w, writes waypoint w + 1 into
  * the arm's goal block in the same kernel.  No host takes part; the whole run is one enqueued sequence.
  *   path length  L_b = the number of leading rows of way16[b] whose FIRST element is not NaN: a NaN row ends the path, so arms may have paths
@@ -395,7 +395,7 @@ int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* 
  *     ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
  * or the time is up, and returns (result, js - q).  vfik_goto_js is that wait for the batch: the blocks of vfik_goto unchanged -- `stride` cycles
  * through the kernels of vfik_rollout, under the handle's gate, the same q ping-pong or q_traj rows -- and after every block one small kernel
- * (arrive_js_kernel) that applies the reference's rule to each arm that ran the block and has not arrived, in double on the io-typed values:
+ * (check_kernel<T, 1, 0>) that applies the reference's rule to each arm that ran the block and has not arrived, in double on the io-typed values:
  *     ok = for all i:  (ref[i] - prec[i]) <= q[i]  &&  (ref[i] + prec[i]) >= q[i]
  * Both compares are non-strict and the two edges are computed as written (|ref - q| <= prec is another function in floating point).  q is the
  * block's integrated row -- what /bridge/encoders would publish; ref is the arm's row of io->q_ref AS THE CALLER SENT IT, not the clamped value the
@@ -435,7 +435,7 @@ int vfik_goto_js_host(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts
  * precision and the gate (the caller's && L_b > 0 && !(hold && next == L_b)) are vfik_follow's; a row of wayq whose FIRST element is NaN ends the
  * arm's list.  The reference row every block reads as io->q_ref belongs to the HANDLE ([B][n], io dtype, allocated with the other goto buffers):
  * in front of block 0 posture 0 goes into it -- an arm that does not take part gets a row that starts with NaN --, and the check that finds an arm
- * at posture `next` writes the following one (follow_js_kernel).  Nothing else of the handle changes: the goal image, vfik_launch_epoch and the
+ * at posture `next` writes the following one (check_kernel<T, 1, 1>).  Nothing else of the handle changes: the goal image, vfik_launch_epoch and the
  * launch decisions stay, the cycle kernel is the one a caller's own q_ref would select, and a later call with the caller's own io->q_ref never
  * sees the handle's row.  diff is measured against the posture the arm was sent to, min(next, L_b - 1) on entry to the check.
  * VFIK_E_ARG, nothing enqueued: what vfik_goto refuses, io->q_ref GIVEN (the handle supplies it), n_way < 1, wayq / reached / next NULL, wayq

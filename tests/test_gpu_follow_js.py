@@ -73,15 +73,15 @@ def _params(env):
     return env.abi.default_params(flags=env.abi.F_MIXER, mix_w=MIX_JOINT, jp_kp=KP)
 
 
-def _reference(env, robot, B, stride, hold, io_dtype=np.float64):
+def _reference(env, robot, B, stride, hold, io_dtype=np.float64, active=None):
     """The oracle's run of a case, computed once per module and never modified."""
-    key = (robot, B, stride, hold, np.dtype(io_dtype).name)
+    key = (robot, B, stride, hold, np.dtype(io_dtype).name, None if active is None else active.tobytes())
     if key not in env.cache:
         chain, w, q0, wayq = _case(env, robot, B, io_dtype)
         params = _params(env)
         p = _prec(chain.n)
         out = jr.follow_js_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], wayq, N_CYCLES, stride, DT, p, via_prec=3 * p,
-                                     hold=hold, clamp=True, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7)
+                                     hold=hold, clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7)
         for v in out.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)
@@ -105,11 +105,12 @@ def _follow(eng, q0, wayq, stride, hold, **kw):
     return got
 
 
-def _replay(wayq, L, q_traj, stride, hold, prec, via):
-    """The state machine of the header on given q rows, with the helper's rule: (reached, next, way_traj, last check every arm ran)."""
+def _replay(wayq, L, q_traj, stride, hold, prec, via, ua=None):
+    """The state machine of the header on given q rows, with the helper's rule: (reached, next, way_traj, last check every arm ran).
+    ua: the caller's gate as booleans (None: every arm)."""
     n_checks, B, n = q_traj.shape
     arms = np.arange(B)
-    part = L > 0
+    part = (L > 0) if ua is None else (L > 0) & ua
     nxt = np.zeros(B, dtype=np.int32)
     reached = np.full((B, wayq.shape[1]), -1, dtype=np.int32)
     way_traj = np.full((n_checks, B), -1, dtype=np.int32)
@@ -127,14 +128,17 @@ def _replay(wayq, L, q_traj, stride, hold, prec, via):
     return reached, nxt, way_traj, last_ran
 
 
-def _check(got, ref, q0, wayq, stride, hold, io_dtype):
+def _check(got, ref, q0, wayq, stride, hold, io_dtype, active=None, n_checks=None):
+    """active: the caller's gate of the run (None: every arm); n_checks: the checks the call is to have run (None: all of N_CYCLES), with
+    `ref` then cut to as many."""
     io_dtype = np.dtype(io_dtype)
     B, n = q0.shape
     prec = _prec(n)
-    n_checks = N_CYCLES // stride
+    n_checks = N_CYCLES // stride if n_checks is None else n_checks
     L = jr.list_lengths(wayq)
     assert np.array_equal(L, ref["length"]) and set(L) == {0, 1, 2, 3}
-    part = L > 0
+    ua = np.ones(B, dtype=bool) if active is None else active != 0
+    part = (L > 0) & ua
     margin, cap = MARGIN[io_dtype]
     out = ref["closest"] < margin
     share = np.count_nonzero(out & part) / np.count_nonzero(part)
@@ -151,7 +155,7 @@ def _check(got, ref, q0, wayq, stride, hold, io_dtype):
         assert np.array_equal(got[k][inc], ref[k][inc]), (k, np.flatnonzero(inc & np.any(np.atleast_2d(got[k].T != ref[k].T), axis=0)))
     assert np.array_equal(got["way_traj"][:, inc], ref["way_traj"][:, inc])
     # every arm against the state machine on the GPU's own rows
-    r, nx, wt, last_ran = _replay(wayq, L, got["q_traj"], stride, hold, prec, 3 * prec)
+    r, nx, wt, last_ran = _replay(wayq, L, got["q_traj"], stride, hold, prec, 3 * prec, ua)
     assert np.array_equal(got["reached"], r) and np.array_equal(got["next"], nx) and np.array_equal(got["way_traj"], wt)
     rows = inc if hold else np.ones(B, dtype=bool)
     eq = np.abs(got["q_traj"][:, rows].astype(np.float64) - ref["q_traj"][:, rows]).max()
@@ -163,7 +167,7 @@ def _check(got, ref, q0, wayq, stride, hold, io_dtype):
     mine = np.array([np.count_nonzero(part & ((fin < 0) | (fin > c))) for c in cyc])
     assert np.array_equal(got["pending"], mine)
     assert np.array_equal(got["q"], got["q_traj"][-1])
-    # the arm without a list is kept out: its rows carry its start, nothing is stored for it
+    # the arm without a list, and one the caller gates off, is kept out: its rows carry its start, nothing is stored for it
     assert np.all(got["q_traj"][:, ~part] == q0[~part].astype(io_dtype)) and np.all(got["way_traj"][:, ~part] == -1)
     assert np.all(got["reached"][~part] == -1) and np.all(got["next"][~part] == 0)
     assert np.all(got["status"][~part] == 0) and np.all(got["qdot_out"][~part] == 0) and np.all(got["diff"][~part] == 0)
@@ -190,6 +194,44 @@ def test_follow_js(env, robot, B, stride, hold, io_dtype):
     eng = _engine(env, chain, B, io_dtype, params, w)
     got = _follow(eng, q0, wayq, stride, hold)
     _check(got, ref, q0, wayq, stride, hold, io_dtype)
+    eng.close()
+
+
+@pytest.mark.parametrize("poll", [0, 8])
+@pytest.mark.parametrize("io_dtype", [np.float32, np.float64])
+def test_traced_under_a_gate_and_early_exit(env, io_dtype, poll):
+    """lwr, 203 arms, W = 3, stride 4, hold, with traces, under the caller's gate (arms 2, 9, 16, ... off) and with arm 5 without a list;
+    once to the end and once polled every 8 checks.  The oracle (on the CPU) has every arm that takes part finish its list by check 28 of
+    40, with arms under way at the polls before: the polled call ends after 32 checks.  An early end comes only once no arm that takes part
+    is under way (pending == 0), so what is still short of its list then are the arms the gate keeps out -- they have postures left and
+    must come back untouched.  With hold every arm stands still from the check that found it at its last posture, so the oracle's run
+    cut to the checks that ran is the oracle's run of as many checks."""
+    B, stride, hold = 203, 4, True
+    active = np.ones(B, dtype=np.int32)
+    active[2::7] = 0
+    chain, w, q0, wayq, params, ref = _reference(env, "lwr", B, stride, hold, io_dtype, active)
+    n_checks = N_CYCLES // stride
+    L, ua = ref["length"], active != 0
+    part = ua & (L > 0)
+    zero = np.flatnonzero(ref["pending"] == 0)
+    assert np.count_nonzero(ref["next"][part] == L[part]) >= 1 and np.any(~ua & (L > 0)) and np.all(ref["next"][~ua] == 0)
+    assert len(zero) and ref["pending"][7] > 0 and ref["pending"][zero[0] - 1] > 0
+    want_run = n_checks if poll == 0 else (zero[0] + 1 + poll - 1) // poll * poll
+    assert poll == 0 or want_run < n_checks
+    # an arm whose decision lies within the margin may be found a check later than the oracle finds it: none of them is among the last
+    near = part & (ref["closest"] < MARGIN[np.dtype(io_dtype)][0])
+    assert not near.any() or ref["reached"][near].max() + 3 * stride < (zero[0] + 1) * stride
+    eng = _engine(env, chain, B, io_dtype, params, w)
+    got = _follow(eng, q0, wayq, stride, hold, active=active, poll=poll)
+    print("checks_run %d of %d (the oracle's pending is 0 from check %d on)" % (got["checks_run"], n_checks, zero[0]))
+    assert got["checks_run"] == want_run
+    for k in ("pending", "q_traj", "way_traj"):
+        assert got[k].shape[0] == want_run, k
+    assert got["pending"][-1] == 0 and (poll == 0 or got["pending"][want_run - poll - 1] > 0)   # under way at the poll before the last
+    cut = dict(ref)
+    for k in ("pending", "q_traj", "way_traj"):
+        cut[k] = ref[k][:want_run]
+    _check(got, cut, q0, wayq, stride, hold, io_dtype, active=active, n_checks=want_run)
     eng.close()
 
 

@@ -5,7 +5,7 @@ goal + 8 obstacles, float32 I/O, 200 control cycles, W = 4 waypoints per arm, st
 vfik_goto is existing code and the yardstick.  Both calls get the same options and an all-ones io->active, so that both run their blocks
 under the handle's gate (a follow always does; a goto without hold and without a caller's gate launches its blocks without one): the
 cycle launches are then the same kernels on the same arms, and the difference of the two periods, divided by the number of checks, is
-what follow_kernel costs over arrive_kernel.  Two scenes:
+what check_kernel<T, 0, 1> costs over check_kernel<T, 0, 0>.  Two scenes:
 
  far    every waypoint is C3's own random goal: the arms that get there within 200 cycles pass all four, one per check; hold off and on;
  near   waypoints at fk(q0 + 0.04 w U(-1, 1)), w = 1..4: arms reach waypoints throughout the run (counted), hold off -- every arm runs
@@ -13,7 +13,7 @@ what follow_kernel costs over arrive_kernel.  Two scenes:
 
 Series alternate goto, follow, goto, follow, ...: --series of each, every one a median of --reps HIP-event periods after 2 untimed runs.
 Reported: the medians, the spread of goto's own medians over its series, the difference per check, and the extra bytes a check moves
-(next and the path length where arrive_kernel reads arrived: 8 against 4 B per arm; per arm that reaches a waypoint a frame's rows 0..2
+(next and the path length where check_kernel<T, 0, 0> reads arrived: 8 against 4 B per arm; per arm that reaches a waypoint a frame's rows 0..2
 read and written, 2 x 48 B at float32 I/O, and reached / next, 8 B) at the 4.81 TB/s profiles/move_fields_cost.txt reached.  No bar is
 fixed: anything beyond spread plus bytes is stated as a finding.
 
@@ -137,7 +137,7 @@ say("FINDINGS" if findings else "FINDINGS: none -- every difference lies inside 
 for x in findings:
     say("    " + x)
 if findings:
-    say("    What the excess is made of is not measured here.  follow_kernel reads two words per arm where arrive_kernel reads one, has three")
+    say("    What the excess is made of is not measured here.  check_kernel<T, 0, 1> reads two words per arm where check_kernel<T, 0, 0> reads one, has three")
     say("    quad stores per arriving lane, and otherwise the same kernel boundary and the same one atomic add per wave.")
 say()
 eng.close()

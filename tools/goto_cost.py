@@ -163,7 +163,7 @@ if floor is not None:
         say("    s = %2d, hold %s, %-18s: %6.2f us per check, bar %.2f us : %s" % (s, "on " if hold else "off", "q_traj + dist_traj" if traces else "no trace", c, bar,
                                                                                  "PASS" if ok else "MISSED"))
 if failed:
-    say("    What the excess is made of is NOT measured here.  A check is one launch of arrive_kernel: a kernel boundary, 2.4 MB of rows and, while")
+    say("    What the excess is made of is NOT measured here.  A check is one launch of check_kernel<T, 0, 0>: a kernel boundary, 2.4 MB of rows and, while")
     say("    most arms are under way, one atomic add per wave -- 1024 waves adding to ONE word, pending[k].  Adds of every wave of the chip to a")
     say("    single address are the first suspect (same-address atomics serialise); a per-block sum in front of the atomic is the experiment to make.")
 say()

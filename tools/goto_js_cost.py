@@ -9,9 +9,9 @@ and the reference the controller reads is the same array -- the caller's io->q_r
 row by vfik_follow_js.  The cycle launches are then the same kernels on the same arms, and the difference of two periods, divided by the
 number of checks, is what one check kernel costs over the other:
 
- (a) goto_js over goto      arrive_js_kernel reads two q-sized rows per arm (the reference and the integrated angles: 2 x 28 B) where
-                            arrive_kernel reads the distance pair and the goal block's `present` flag (12 B);
- (b) follow_js over goto_js follow_js_kernel reads next and the list length where arrive_js_kernel reads arrived (8 against 4 B per arm)
+ (a) goto_js over goto      check_kernel<T, 1, 0> reads two q-sized rows per arm (the reference and the integrated angles: 2 x 28 B) where
+                            check_kernel<T, 0, 0> reads the distance pair and the goal block's `present` flag (12 B);
+ (b) follow_js over goto_js check_kernel<T, 1, 1> reads next and the list length where check_kernel<T, 1, 0> reads arrived (8 against 4 B per arm)
                             and, per posture reached, copies a row (2 x 28 B) and writes reached / next (8 B).  The goto_js heads for
                             posture 0 of the W = 4 postures per arm.
 

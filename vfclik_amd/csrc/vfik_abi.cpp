@@ -1386,643 +1386,308 @@ int vfik_rollout_host(vfik_handle* h, const vfik_io* io, int n_cycles, double dt
     return cycles_host(h, io, n_cycles, dt, clamp_to_limits, q_out);
 }
 
-// ---- batched goto (handlers.py:346-440) ------------------------------------------------------------
+// ---- timed moves: batched goto (handlers.py:346-440), waypoint lists (a script of gotoFrame calls, handlers.py:346-387), joint-space goto and
+// posture lists (set_ref_js, handlers.py:544-576).  Every form is blocks of `stride` cycles through launch_cycles, as vfik_rollout runs them, one
+// check kernel after each block, the handle's gate, pending[k], ping-pong q rows and optional traces: ONE vfik::TimedMove (vfik_io_layout.h) that each
+// form's check fills from its own options, one run loop on it. ----
 size_t vfik_goto_opts_size(void) { return sizeof(vfik_goto_opts); }
+size_t vfik_follow_opts_size(void) { return sizeof(vfik_follow_opts); }
+size_t vfik_goto_js_opts_size(void) { return sizeof(vfik_goto_js_opts); }
+size_t vfik_follow_js_opts_size(void) { return sizeof(vfik_follow_js_opts); }
 
 namespace {
-// one goto between its checks and its last block: the caller's io and options (device pointers) and the buffers that stand in for those it left out
-struct GotoRun {
-    const vfik_io* io;
-    vfik_goto_opts o;
-    int n_checks;
-    int32_t* pending;
-    size_t qrow, drow;   // bytes of a q row [B][n] and of a distance row [B][2]
-    bool gated;          // the blocks run under the handle's gate (hold, or the caller gates): else every arm runs every block
-    bool joint = false;  // a joint-space form (vfik_goto_js, vfik_follow_js): no distance row -- the blocks' goal_dist is the caller's business
-    const void* q_ref = nullptr;   // ... and, when set, what the blocks read as io->q_ref in place of the caller's (vfik_follow_js: the handle's row)
-};
+using vfik::TimedMove;
 
-// everything that can refuse the call, before anything is enqueued
-int goto_check(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
-    if (check_handle(h)) return VFIK_E_ARG;
+// the members every form's options carry under the same names
+extern "C++" {
+template <typename O>
+TimedMove timed_of(const vfik_io* io, const O* o, bool joint, bool list) {
+    TimedMove m{};
+    m.io = io;
+    m.joint = joint;
+    m.list = list;
+    m.n_cycles = o->n_cycles; m.stride = o->stride; m.dt = o->dt;
+    m.clamp = o->clamp_to_limits; m.hold = o->hold;
+    m.x[vfik::X_PENDING] = o->pending; m.x[vfik::X_Q_OUT] = o->q_out; m.x[vfik::X_Q_TRAJ] = o->q_traj;
+    return m;
+}
+}
+
+// what every form refuses, before anything is enqueued
+int timed_check(vfik_handle* h, TimedMove& m) {
+    const vfik_io* io = m.io;
     if (!io || !io->q) return fail(VFIK_E_ARG, "a goto needs io->q");
-    if (!o || !o->arrived) return fail(VFIK_E_ARG, "vfik_goto: the options and their arrived[B] are required");
-    if (o->stride < 1) return fail(VFIK_E_ARG, "stride %d: at least one cycle between two checks", o->stride);
-    if (o->n_cycles < 1 || o->n_cycles > 1000000) return fail(VFIK_E_ARG, "n_cycles %d outside [1, 1e6]", o->n_cycles);
-    if (o->n_cycles % o->stride) return fail(VFIK_E_ARG, "n_cycles %d is no multiple of stride %d", o->n_cycles, o->stride);
-    if (!std::isfinite(o->dt)) return fail(VFIK_E_ARG, "dt must be finite");
-    if (!(o->pos_prec >= 0.0) || !(o->rot_prec >= 0.0)) return fail(VFIK_E_ARG, "goal precision (%g m, %g rad) must not be negative or NaN", o->pos_prec, o->rot_prec);
+    if (m.stride < 1) return fail(VFIK_E_ARG, "stride %d: at least one cycle between two checks", m.stride);
+    if (m.n_cycles < 1 || m.n_cycles > 1000000) return fail(VFIK_E_ARG, "n_cycles %d outside [1, 1e6]", m.n_cycles);
+    if (m.n_cycles % m.stride) return fail(VFIK_E_ARG, "n_cycles %d is no multiple of stride %d", m.n_cycles, m.stride);
+    if (!std::isfinite(m.dt)) return fail(VFIK_E_ARG, "dt must be finite");
+    if (!m.joint && (!(m.prec[0] >= 0.0) || !(m.prec[1] >= 0.0)))
+        return fail(VFIK_E_ARG, "goal precision (%g m, %g rad) must not be negative or NaN", m.prec[0], m.prec[1]);
     if (io->q_cmded) return fail(VFIK_E_ARG, "io->q_cmded (LWR position command form) is for vfik_step only");
     if (io->track_error || io->obj_dist) return fail(VFIK_E_ARG, "io->track_error / io->obj_dist are per control cycle: vfik_step only, not a goto");
     if (!io->q_lo != !io->q_hi) return fail(VFIK_E_ARG, "io->q_lo and io->q_hi come together (both or neither)");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
+    m.n_checks = m.n_cycles / m.stride;
+    m.gated = m.hold || io->active || m.list;
     return VFIK_OK;
 }
 
-// the handle's buffers this goto needs (first call: never under stream capture) and pending[] zeroed; follow: a vfik_follow on these options
-int goto_reserve(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r, bool follow = false, bool joint = false) {
-    r.io = io;
-    r.joint = joint;
-    r.o = *o;
-    r.n_checks = o->n_cycles / o->stride;
-    r.qrow = (size_t)h->B * h->n * h->esz;
-    r.drow = (size_t)h->B * 2 * h->esz;
-    r.gated = o->hold || io->active;
-    const bool need_pending = !o->pending && h->goto_pending.bytes < (size_t)r.n_checks * sizeof(int);
-    const bool need_dist = !joint && !o->dist_traj && !io->goal_dist && !h->d_goto_dist;
-    const bool need_q = !o->q_traj && !h->d_gotoq[0];
-    // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
-    const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
-                       (o->q_traj && r.n_checks > 1 && (reinterpret_cast<uintptr_t>(o->q_traj) % 16 || r.qrow % 16));
-    const bool need_ref = joint && follow && !h->d_js_ref;
-    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (follow && !h->d_follow_len) || need_ref) {
-        if (refuse_capture(h->stream, "vfik_goto / vfik_follow: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such call before capturing the stream"))
-            return VFIK_E_STATE;
-        if (follow && !h->d_follow_len && dev_alloc(h, (void**)&h->d_follow_len, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
-        if (need_ref && dev_alloc(h, &h->d_js_ref, (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
-        if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
-        // (synchronised: an earlier goto may still count into the smaller array)
-        if (need_pending && reserve(h, h->goto_pending, (size_t)r.n_checks * sizeof(int), true, true)) return VFIK_E_HIP;
-        if (need_dist && dev_alloc(h, &h->d_goto_dist, r.drow, false)) return VFIK_E_HIP;
-        for (int k = 0; need_q && k < 2; ++k)
-            if (!h->d_gotoq[k] && dev_alloc(h, &h->d_gotoq[k], (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
-        if (odd_q && !h->d_qalign && dev_alloc(h, &h->d_qalign, (r.qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
-    }
-    r.pending = o->pending ? o->pending : static_cast<int32_t*>(h->goto_pending.p);
-    HIP_TRY(hipMemsetAsync(r.pending, 0, (size_t)r.n_checks * sizeof(int), h->stream));
-    return VFIK_OK;
+int goto_check(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, TimedMove& m) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!io || !io->q) return fail(VFIK_E_ARG, "a goto needs io->q");
+    if (!o || !o->arrived) return fail(VFIK_E_ARG, "vfik_goto: the options and their arrived[B] are required");
+    m = timed_of(io, o, false, false);
+    m.prec[0] = o->pos_prec; m.prec[1] = o->rot_prec;
+    m.x[vfik::X_ARRIVED] = o->arrived; m.x[vfik::X_DIST_TRAJ] = o->dist_traj;
+    return timed_check(h, m);
 }
 
-// ... and arrived[] and the gate set
-int goto_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, GotoRun& r) {
-    const int rc = goto_reserve(h, io, o, r);
-    if (rc != VFIK_OK) return rc;
-    vfik::ArriveArgs g{};
-    g.arrived = o->arrived;
-    g.gate = h->d_goto_gate;
-    g.active = io->active;
-    g.B = h->B;
-    g.k = -1;
-    hipError_t e = vfik::launch_arrive(h->io_dtype, g, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-void* goto_q_row(const vfik_handle* h, const GotoRun& r, int k) {
-    return r.o.q_traj ? static_cast<char*>(r.o.q_traj) + (size_t)k * r.qrow : h->d_gotoq[k & 1];
-}
-
-// the rows of block k: the q it reads and writes, its goal_dist, and the trace's distance row in front of it (NULL: no trace, or k = 0)
-struct BlockRows {
-    const void* q_prev;
-    void* q_now;
-    void* dist;
-    const void* dist_prev;
-};
-
-// block k: `stride` cycles through launch_cycles, as vfik_rollout runs them
-int goto_cycles(vfik_handle* h, const GotoRun& r, int k, BlockRows& w) {
-    vfik_io b = *r.io;
-    w.q_prev = k == 0 ? r.io->q : goto_q_row(h, r, k - 1);
-    w.q_now = goto_q_row(h, r, k);
-    w.dist = r.o.dist_traj ? static_cast<char*>(r.o.dist_traj) + (size_t)k * r.drow : (r.io->goal_dist ? r.io->goal_dist : h->d_goto_dist);
-    w.dist_prev = (r.o.dist_traj && k > 0) ? static_cast<char*>(r.o.dist_traj) + (size_t)(k - 1) * r.drow : nullptr;
-    b.q = w.q_prev;
-    if (!r.joint) b.goal_dist = w.dist;   // (a joint form: w.dist is io->goal_dist or a row nobody reads)
-    if (r.q_ref) b.q_ref = r.q_ref;
-    b.active = r.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
-    return launch_cycles(h, &b, r.o.stride, r.o.dt, r.o.clamp_to_limits, w.q_now, h->stream, k > 0);
-}
-
-// block k and its check
-int goto_block(vfik_handle* h, const GotoRun& r, int k) {
-    BlockRows w;
-    const int rc = goto_cycles(h, r, k, w);
-    if (rc != VFIK_OK) return rc;
-    vfik::ArriveArgs g{};
-    g.arrived = r.o.arrived;
-    g.gate = h->d_goto_gate;
-    g.active = r.io->active;
-    g.dist = w.dist;
-    g.dist_prev = w.dist_prev;
-    g.q_prev = w.q_prev;
-    g.q_now = w.q_now;
-    g.goal = h->d_goal;
-    g.pending = r.pending + k;
-    g.pos_prec = r.o.pos_prec;
-    g.rot_prec = r.o.rot_prec;
-    g.B = h->B; g.n = h->n; g.k = k; g.stride = r.o.stride; g.hold = r.o.hold ? 1 : 0;
-    g.Bpad = h->Bpad;
-    hipError_t e = vfik::launch_arrive(h->io_dtype, g, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-// q_out: the row the last executed block wrote; io->goal_dist beside a trace: the trace's last row
-int goto_end(vfik_handle* h, const GotoRun& r, int checks_run) {
-    if (r.o.q_out && checks_run > 0) HIP_TRY(hipMemcpyAsync(r.o.q_out, goto_q_row(h, r, checks_run - 1), r.qrow, hipMemcpyDeviceToDevice, h->stream));
-    if (r.o.dist_traj && r.io->goal_dist && checks_run > 0)
-        HIP_TRY(hipMemcpyAsync(r.io->goal_dist, static_cast<char*>(r.o.dist_traj) + (size_t)(checks_run - 1) * r.drow, r.drow, hipMemcpyDeviceToDevice, h->stream));
-    return VFIK_OK;
-}
-}  // namespace
-
-int vfik_goto(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
-    int rc = goto_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    GotoRun r;
-    if ((rc = goto_begin(h, io, o, r)) != VFIK_OK) return rc;
-    for (int k = 0; k < r.n_checks; ++k)
-        if ((rc = goto_block(h, r, k)) != VFIK_OK) return rc;
-    return goto_end(h, r, r.n_checks);
-}
-
-// Host-pointer form: every member of io and of the options in ONE device buffer of the handle (grown on demand, members 256-byte aligned),
-// copied in before the first block and out after the last one executed.
-int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, int poll_checks, int* checks_run) {
-    int rc = goto_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    const int n_checks = o->n_cycles / o->stride;
-    const size_t qrow = (size_t)h->B * h->n * h->esz, drow = (size_t)h->B * 2 * h->esz;
-    IoStaging st(*io, h->B, h->io_dims());
-    // beside io's members.  Under a gate: q_out is written for every arm (goto_end), a gated arm's rows of the distance trace never, its q
-    // rows always (they repeat its start).  pending is staged without an array of the caller's too: the early exit reads it.
-    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
-    st.add(vfik::X_ARRIVED, o->arrived, (size_t)h->B * sizeof(int32_t), false);
-    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
-    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
-    st.add(vfik::X_DIST_TRAJ, o->dist_traj, (size_t)n_checks * drow, true);
-    st.layout();
-    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
-    st.map(h->goto_stage.p);
-    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
-    if (io->active && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    const vfik_io d = st.device_io();
-    vfik_goto_opts od = *o;
-    od.arrived = static_cast<int32_t*>(st.extra(vfik::X_ARRIVED).dev);
-    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
-    od.q_out = st.extra(vfik::X_Q_OUT).dev;
-    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
-    od.dist_traj = st.extra(vfik::X_DIST_TRAJ).dev;
-    GotoRun r;
-    if ((rc = goto_begin(h, &d, &od, r)) != VFIK_OK) return rc;
-    int done = 0;
-    while (done < n_checks) {
-        if ((rc = goto_block(h, r, done)) != VFIK_OK) return rc;
-        ++done;
-        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
-            int32_t left = -1;
-            HIP_TRY(hipMemcpyAsync(&left, r.pending + (done - 1), sizeof left, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (left == 0) break;   // everybody the caller lets run is there
-        }
-    }
-    if ((rc = goto_end(h, r, done)) != VFIK_OK) return rc;
-    IoStaging back = st;   // what goes back: of pending and the traces the checks that ran (st keeps the sizes its layout was made of)
-    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
-    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
-    back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
-    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (checks_run) *checks_run = done;
-    return VFIK_OK;
-}
-
-// ---- waypoint lists (a script of gotoFrame calls, handlers.py:346-387) ---------------------------------
-size_t vfik_follow_opts_size(void) { return sizeof(vfik_follow_opts); }
-
-namespace {
-// vfik_goto's options inside a vfik_follow's: the blocks, the gate and the traces are the goto's (arrived: unused)
-vfik_goto_opts follow_goto_opts(const vfik_follow_opts* o) {
-    vfik_goto_opts g{};
-    g.n_cycles = o->n_cycles; g.stride = o->stride; g.dt = o->dt;
-    g.clamp_to_limits = o->clamp_to_limits; g.hold = o->hold;
-    g.pos_prec = o->pos_prec; g.rot_prec = o->rot_prec;
-    g.arrived = o->next;
-    g.pending = o->pending; g.q_out = o->q_out; g.q_traj = o->q_traj; g.dist_traj = o->dist_traj;
-    return g;
-}
-
-struct FollowRun {
-    GotoRun g;
-    vfik_follow_opts o;
-};
-
-// everything that can refuse the call, before anything is enqueued
-int follow_check(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o) {
+int follow_check(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, TimedMove& m) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!o || !o->way16 || !o->reached || !o->next) return fail(VFIK_E_ARG, "vfik_follow: the options, their way16[B][W][16], reached[B][W] and next[B] are required");
     if (o->n_way < 1) return fail(VFIK_E_ARG, "n_way %d: a path has at least one waypoint", o->n_way);
     if (reinterpret_cast<uintptr_t>(o->way16) % 16) return fail(VFIK_E_ARG, "way16 must be 16-byte aligned: the kernel loads its rows in 16-byte pieces");
     if (!(o->via_pos_prec >= 0.0) || !(o->via_rot_prec >= 0.0))
         return fail(VFIK_E_ARG, "via precision (%g m, %g rad) must not be negative or NaN", o->via_pos_prec, o->via_rot_prec);
-    const vfik_goto_opts g = follow_goto_opts(o);
-    return goto_check(h, io, &g);
+    m = timed_of(io, o, false, true);
+    m.n_way = o->n_way;
+    m.prec[0] = o->pos_prec; m.prec[1] = o->rot_prec; m.via_prec[0] = o->via_pos_prec; m.via_prec[1] = o->via_rot_prec;
+    m.x[vfik::X_WAY16] = const_cast<void*>(o->way16); m.x[vfik::X_REACHED] = o->reached; m.x[vfik::X_NEXT] = o->next;
+    m.x[vfik::X_DIST_TRAJ] = o->dist_traj; m.x[vfik::X_WAY_TRAJ] = o->way_traj;
+    return timed_check(h, m);
 }
 
-// after the shared checks, on the pointer the kernel reads (the host form: its staged copy)
-int follow_begin(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, FollowRun& r) {
-    r.o = *o;
-    const vfik_goto_opts go = follow_goto_opts(o);
-    const int rc = goto_reserve(h, io, &go, r.g, true);
-    if (rc != VFIK_OK) return rc;
-    r.g.gated = true;   // (an arm without a path is kept out: the blocks always run under the gate)
-    vfik::FollowArgs f{};
-    f.reached = o->reached; f.next = o->next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
-    f.active = io->active;
-    f.way16 = o->way16;
-    f.goal = h->d_goal;
-    f.B = h->B; f.W = o->n_way; f.k = -1;
-    f.Bpad = h->Bpad;
-    hipError_t e = vfik::launch_follow(h->io_dtype, f, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-// block k and its check
-int follow_block(vfik_handle* h, const FollowRun& r, int k) {
-    BlockRows w;
-    const int rc = goto_cycles(h, r.g, k, w);
-    if (rc != VFIK_OK) return rc;
-    const vfik_follow_opts& o = r.o;
-    vfik::FollowArgs f{};
-    f.reached = o.reached; f.next = o.next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
-    f.active = r.g.io->active;
-    f.way16 = o.way16;
-    f.dist = w.dist; f.dist_prev = w.dist_prev; f.q_prev = w.q_prev; f.q_now = w.q_now;
-    f.goal = h->d_goal;
-    f.pending = r.g.pending + k;
-    f.way_now = o.way_traj ? o.way_traj + (size_t)k * h->B : nullptr;
-    f.way_prev = (o.way_traj && k > 0) ? o.way_traj + (size_t)(k - 1) * h->B : nullptr;
-    f.pos_prec = o.pos_prec; f.rot_prec = o.rot_prec; f.via_pos_prec = o.via_pos_prec; f.via_rot_prec = o.via_rot_prec;
-    f.B = h->B; f.n = h->n; f.W = o.n_way; f.k = k; f.stride = o.stride; f.hold = o.hold ? 1 : 0;
-    f.Bpad = h->Bpad;
-    hipError_t e = vfik::launch_follow(h->io_dtype, f, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-}  // namespace
-
-int vfik_follow(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o) {
-    int rc = follow_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    FollowRun r;
-    if ((rc = follow_begin(h, io, o, r)) != VFIK_OK) return rc;
-    for (int k = 0; k < r.g.n_checks; ++k)
-        if ((rc = follow_block(h, r, k)) != VFIK_OK) return rc;
-    return goto_end(h, r.g, r.g.n_checks);
-}
-
-// Host-pointer form, as vfik_goto_host: every member of io and of the options in the handle's staging buffer, way16 copied in with the inputs
-// (the alignment rule holds for the caller's array here too, although the kernel reads the staged copy).
-int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, int poll_checks, int* checks_run) {
-    int rc = follow_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    const int n_checks = o->n_cycles / o->stride;
-    const size_t qrow = (size_t)h->B * h->n * h->esz, drow = (size_t)h->B * 2 * h->esz, wrow = (size_t)h->B * sizeof(int32_t);
-    IoStaging st(*io, h->B, h->io_dims());
-    // gated as vfik_goto_host's; reached and next are written for every arm by the pass in front of block 0, a row of way_traj only for arms that ran
-    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
-    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
-    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
-    st.add(vfik::X_DIST_TRAJ, o->dist_traj, (size_t)n_checks * drow, true);
-    st.add(vfik::X_WAY16, const_cast<void*>(o->way16), (size_t)h->B * o->n_way * 16 * h->esz, false, false, true);
-    st.add(vfik::X_REACHED, o->reached, (size_t)h->B * o->n_way * sizeof(int32_t), false);
-    st.add(vfik::X_NEXT, o->next, wrow, false);
-    st.add(vfik::X_WAY_TRAJ, o->way_traj, (size_t)n_checks * wrow, true);
-    st.layout();
-    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
-    st.map(h->goto_stage.p);
-    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
-    // an arm without a path is kept out like a gated one: its output rows go in before the blocks then, too
-    bool kept_out = io->active != nullptr;
-    for (size_t b = 0, row = (size_t)o->n_way * 16; b < (size_t)h->B && !kept_out; ++b)
-        kept_out = h->esz == 4 ? std::isnan(static_cast<const float*>(o->way16)[b * row]) : std::isnan(static_cast<const double*>(o->way16)[b * row]);
-    if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    const vfik_io d = st.device_io();
-    vfik_follow_opts od = *o;
-    od.way16 = st.extra(vfik::X_WAY16).dev;
-    od.reached = static_cast<int32_t*>(st.extra(vfik::X_REACHED).dev);
-    od.next = static_cast<int32_t*>(st.extra(vfik::X_NEXT).dev);
-    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
-    od.q_out = st.extra(vfik::X_Q_OUT).dev;
-    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
-    od.dist_traj = st.extra(vfik::X_DIST_TRAJ).dev;
-    od.way_traj = static_cast<int32_t*>(st.extra(vfik::X_WAY_TRAJ).dev);
-    FollowRun r;
-    if ((rc = follow_begin(h, &d, &od, r)) != VFIK_OK) return rc;
-    int done = 0;
-    while (done < n_checks) {
-        if ((rc = follow_block(h, r, done)) != VFIK_OK) return rc;
-        ++done;
-        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
-            int32_t left = -1;
-            HIP_TRY(hipMemcpyAsync(&left, r.g.pending + (done - 1), sizeof left, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (left == 0) break;   // every arm that takes part is at its last waypoint
-        }
-    }
-    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
-    IoStaging back = st;   // of pending and the traces the checks that ran
-    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
-    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
-    back.extra(vfik::X_DIST_TRAJ).bytes = (size_t)done * drow;
-    back.extra(vfik::X_WAY_TRAJ).bytes = (size_t)done * wrow;
-    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (checks_run) *checks_run = done;
-    return VFIK_OK;
-}
-
-// ---- joint-space goto and posture lists (set_ref_js, handlers.py:544-576) ---------------------------------
-size_t vfik_goto_js_opts_size(void) { return sizeof(vfik_goto_js_opts); }
-size_t vfik_follow_js_opts_size(void) { return sizeof(vfik_follow_js_opts); }
-
-namespace {
-// vfik_goto's options inside a joint form's: the blocks, the gate and the q rows are the goto's (no precision pair, no distance trace)
-extern "C++" {
-template <typename O>
-vfik_goto_opts js_goto_opts(const O* o, int32_t* arrived) {
-    vfik_goto_opts g{};
-    g.n_cycles = o->n_cycles; g.stride = o->stride; g.dt = o->dt;
-    g.clamp_to_limits = o->clamp_to_limits; g.hold = o->hold;
-    g.arrived = arrived;
-    g.pending = o->pending; g.q_out = o->q_out; g.q_traj = o->q_traj;
-    return g;
-}
-}
-
-int js_prec_check(const vfik_handle* h, const double* prec, const char* what) {
-    for (int i = 0; i < h->n; ++i)
+// prec[n] of a joint form, given and none of it negative or NaN, into the move
+int js_prec(const vfik_handle* h, const double* prec, const char* form, const char* what, double* into) {
+    if (!prec) return fail(VFIK_E_ARG, "%s: prec[n], the goal precision per joint, is required", form);
+    for (int i = 0; i < h->n; ++i) {
         if (!(prec[i] >= 0.0)) return fail(VFIK_E_ARG, "%s[%d] = %g: a goal precision must not be negative or NaN", what, i, prec[i]);
+        into[i] = prec[i];
+    }
     return VFIK_OK;
 }
 
-struct GotoJsRun {
-    GotoRun g;
-    vfik_goto_js_opts o;
-};
-
-// everything that can refuse the call, before anything is enqueued
-int goto_js_check(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o) {
+int goto_js_check(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, TimedMove& m) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!o || !o->arrived) return fail(VFIK_E_ARG, "vfik_goto_js: the options and their arrived[B] are required");
-    const vfik_goto_opts g = js_goto_opts(o, o->arrived);
-    const int rc = goto_check(h, io, &g);
+    m = timed_of(io, o, true, false);
+    m.x[vfik::X_ARRIVED] = o->arrived; m.x[vfik::X_DIFF] = o->diff;
+    const int rc = timed_check(h, m);
     if (rc != VFIK_OK) return rc;
     if (!io->q_ref) return fail(VFIK_E_ARG, "vfik_goto_js needs io->q_ref, the joint reference of every arm");
-    if (!o->prec) return fail(VFIK_E_ARG, "vfik_goto_js: prec[n], the goal precision per joint, is required");
-    return js_prec_check(h, o->prec, "prec");
+    return js_prec(h, o->prec, "vfik_goto_js", "prec", m.prec);
 }
 
-vfik::ArriveJsArgs goto_js_args(vfik_handle* h, const GotoJsRun& r, int k) {
-    vfik::ArriveJsArgs g{};
-    g.arrived = r.o.arrived;
-    g.gate = h->d_goto_gate;
-    g.active = r.g.io->active;
-    for (int i = 0; i < h->n; ++i) g.prec[i] = r.o.prec[i];
-    g.B = h->B; g.n = h->n; g.k = k; g.stride = r.o.stride; g.hold = r.o.hold ? 1 : 0;
-    return g;
-}
-
-int goto_js_begin(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, GotoJsRun& r) {
-    r.o = *o;
-    const vfik_goto_opts go = js_goto_opts(o, o->arrived);
-    const int rc = goto_reserve(h, io, &go, r.g, false, true);
-    if (rc != VFIK_OK) return rc;
-    hipError_t e = vfik::launch_arrive_js(h->io_dtype, goto_js_args(h, r, -1), h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive_js launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-// block k and its check
-int goto_js_block(vfik_handle* h, const GotoJsRun& r, int k) {
-    BlockRows w;
-    const int rc = goto_cycles(h, r.g, k, w);
-    if (rc != VFIK_OK) return rc;
-    vfik::ArriveJsArgs g = goto_js_args(h, r, k);
-    g.ref = r.g.io->q_ref;
-    g.q_prev = w.q_prev;
-    g.q_now = w.q_now;
-    g.diff = r.o.diff;
-    g.pending = r.g.pending + k;
-    hipError_t e = vfik::launch_arrive_js(h->io_dtype, g, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "arrive_js launch: %s", hipGetErrorString(e));
-    return VFIK_OK;
-}
-
-struct FollowJsRun {
-    GotoRun g;
-    vfik_follow_js_opts o;
-};
-
-int follow_js_check(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o) {
+int follow_js_check(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, TimedMove& m) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!o || !o->wayq || !o->reached || !o->next) return fail(VFIK_E_ARG, "vfik_follow_js: the options, their wayq[B][W][n], reached[B][W] and next[B] are required");
     if (o->n_way < 1) return fail(VFIK_E_ARG, "n_way %d: a list has at least one posture", o->n_way);
     if (reinterpret_cast<uintptr_t>(o->wayq) % h->esz) return fail(VFIK_E_ARG, "wayq must be aligned to its element type");
-    const vfik_goto_opts g = js_goto_opts(o, o->next);
-    const int rc = goto_check(h, io, &g);
+    m = timed_of(io, o, true, true);
+    m.n_way = o->n_way;
+    m.x[vfik::X_WAYQ] = const_cast<void*>(o->wayq); m.x[vfik::X_REACHED] = o->reached; m.x[vfik::X_NEXT] = o->next;
+    m.x[vfik::X_DIFF] = o->diff; m.x[vfik::X_WAY_TRAJ] = o->way_traj;
+    const int rc = timed_check(h, m);
     if (rc != VFIK_OK) return rc;
     if (io->q_ref) return fail(VFIK_E_ARG, "vfik_follow_js supplies io->q_ref itself (the handle's reference row): leave it NULL");
-    if (!o->prec) return fail(VFIK_E_ARG, "vfik_follow_js: prec[n], the goal precision per joint, is required");
-    if (js_prec_check(h, o->prec, "prec") != VFIK_OK) return VFIK_E_ARG;
-    return o->via_prec ? js_prec_check(h, o->via_prec, "via_prec") : (int)VFIK_OK;
+    if (js_prec(h, o->prec, "vfik_follow_js", "prec", m.prec) != VFIK_OK) return VFIK_E_ARG;
+    return js_prec(h, o->via_prec ? o->via_prec : o->prec, "vfik_follow_js", "via_prec", m.via_prec);
 }
 
-vfik::FollowJsArgs follow_js_args(vfik_handle* h, const FollowJsRun& r, int k) {
-    const vfik_follow_js_opts& o = r.o;
-    vfik::FollowJsArgs f{};
-    f.reached = o.reached; f.next = o.next; f.len = h->d_follow_len; f.gate = h->d_goto_gate;
-    f.active = r.g.io->active;
-    f.wayq = o.wayq;
-    f.ref = h->d_js_ref;
-    for (int i = 0; i < h->n; ++i) {
-        f.prec[i] = o.prec[i];
-        f.via_prec[i] = o.via_prec ? o.via_prec[i] : o.prec[i];
+vfik::TimedDims timed_dims(const vfik_handle* h, const TimedMove& m) { return {(size_t)h->B, (size_t)h->n, h->esz, (size_t)m.n_way, (size_t)m.n_checks}; }
+
+// the handle's buffers this move needs (first call: never under stream capture) and pending[] zeroed
+int timed_reserve(vfik_handle* h, TimedMove& m) {
+    const vfik_io* io = m.io;
+    const size_t qrow = (size_t)h->B * h->n * h->esz, pend = (size_t)m.n_checks * sizeof(int);
+    const bool need_pending = !m.x[vfik::X_PENDING] && h->goto_pending.bytes < pend;
+    const bool need_dist = !m.joint && !m.x[vfik::X_DIST_TRAJ] && !io->goal_dist && !h->d_goto_dist;
+    const bool need_q = !m.x[vfik::X_Q_TRAJ] && !h->d_gotoq[0];
+    // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
+    const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
+                       (m.x[vfik::X_Q_TRAJ] && m.n_checks > 1 && (reinterpret_cast<uintptr_t>(m.x[vfik::X_Q_TRAJ]) % 16 || qrow % 16));
+    const bool need_ref = m.joint && m.list && !h->d_js_ref;   // the row a posture list's blocks read as io->q_ref
+    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (m.list && !h->d_follow_len) || need_ref) {
+        if (refuse_capture(h->stream, "vfik_goto / vfik_follow: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such call before capturing the stream"))
+            return VFIK_E_STATE;
+        if (m.list && !h->d_follow_len && dev_alloc(h, (void**)&h->d_follow_len, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
+        if (need_ref && dev_alloc(h, &h->d_js_ref, (qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
+        if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
+        // (synchronised: an earlier goto may still count into the smaller array)
+        if (need_pending && reserve(h, h->goto_pending, pend, true, true)) return VFIK_E_HIP;
+        if (need_dist && dev_alloc(h, &h->d_goto_dist, (size_t)h->B * 2 * h->esz, false)) return VFIK_E_HIP;
+        for (int k = 0; need_q && k < 2; ++k)
+            if (!h->d_gotoq[k] && dev_alloc(h, &h->d_gotoq[k], (qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
+        if (odd_q && !h->d_qalign && dev_alloc(h, &h->d_qalign, (qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
     }
-    f.B = h->B; f.n = h->n; f.W = o.n_way; f.k = k; f.stride = o.stride; f.hold = o.hold ? 1 : 0;
-    return f;
-}
-
-int follow_js_begin(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, FollowJsRun& r) {
-    r.o = *o;
-    const vfik_goto_opts go = js_goto_opts(o, o->next);
-    const int rc = goto_reserve(h, io, &go, r.g, true, true);
-    if (rc != VFIK_OK) return rc;
-    r.g.gated = true;   // (an arm without a list is kept out: the blocks always run under the gate)
-    r.g.q_ref = h->d_js_ref;
-    hipError_t e = vfik::launch_follow_js(h->io_dtype, follow_js_args(h, r, -1), h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow_js launch: %s", hipGetErrorString(e));
+    if (!m.x[vfik::X_PENDING]) m.x[vfik::X_PENDING] = h->goto_pending.p;
+    HIP_TRY(hipMemsetAsync(m.x[vfik::X_PENDING], 0, pend, h->stream));
     return VFIK_OK;
 }
 
-// block k and its check
-int follow_js_block(vfik_handle* h, const FollowJsRun& r, int k) {
-    BlockRows w;
-    const int rc = goto_cycles(h, r.g, k, w);
-    if (rc != VFIK_OK) return rc;
-    vfik::FollowJsArgs f = follow_js_args(h, r, k);
-    f.q_prev = w.q_prev; f.q_now = w.q_now;
-    f.diff = r.o.diff;
-    f.pending = r.g.pending + k;
-    f.way_now = r.o.way_traj ? r.o.way_traj + (size_t)k * h->B : nullptr;
-    f.way_prev = (r.o.way_traj && k > 0) ? r.o.way_traj + (size_t)(k - 1) * h->B : nullptr;
-    hipError_t e = vfik::launch_follow_js(h->io_dtype, f, h->stream);
-    if (e != hipSuccess) return fail(VFIK_E_HIP, "follow_js launch: %s", hipGetErrorString(e));
+// the check after block k; k < 0 (w == NULL): the pass in front of block 0, which sets the gate and the arms' state
+int timed_launch_check(vfik_handle* h, const TimedMove& m, int k, const vfik::BlockRows* w) {
+    vfik::CheckArgs g{};
+    g.gate = h->d_goto_gate;
+    g.active = m.io->active;
+    g.B = h->B; g.n = h->n; g.W = m.n_way; g.k = k; g.stride = m.stride; g.hold = m.hold ? 1 : 0;
+    g.Bpad = h->Bpad;
+    if (w) {
+        g.pending = static_cast<int32_t*>(m.x[vfik::X_PENDING]) + k;
+        g.q_prev = w->q_prev; g.q_now = w->q_now;
+        g.dist = w->dist; g.dist_prev = w->dist_prev;
+        g.way_now = w->way_now; g.way_prev = w->way_prev;
+    }
+    g.arrived = static_cast<int32_t*>(m.x[vfik::X_ARRIVED]);
+    g.reached = static_cast<int32_t*>(m.x[vfik::X_REACHED]);
+    g.next = static_cast<int32_t*>(m.x[vfik::X_NEXT]);
+    g.len = h->d_follow_len;
+    g.way = m.x[m.joint ? vfik::X_WAYQ : vfik::X_WAY16];
+    g.goal = h->d_goal;
+    g.ref = m.list ? h->d_js_ref : const_cast<void*>(m.io->q_ref);
+    g.diff = m.x[vfik::X_DIFF];
+    std::memcpy(g.prec, m.prec, sizeof g.prec);   // (all of both: the Cartesian pair sits in [0], [1] whatever n is)
+    std::memcpy(g.via_prec, m.via_prec, sizeof g.via_prec);
+    hipError_t e = vfik::launch_check(h->io_dtype, m.joint, m.list, g, h->stream);
+    if (e != hipSuccess) {
+        static const char* const name[2][2] = {{"arrive", "follow"}, {"arrive_js", "follow_js"}};
+        return fail(VFIK_E_HIP, "%s launch: %s", name[m.joint][m.list], hipGetErrorString(e));
+    }
     return VFIK_OK;
+}
+
+int timed_begin(vfik_handle* h, TimedMove& m) {
+    const int rc = timed_reserve(h, m);
+    return rc != VFIK_OK ? rc : timed_launch_check(h, m, -1, nullptr);
+}
+
+// block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
+int timed_block(vfik_handle* h, const TimedMove& m, int k) {
+    const vfik::BlockRows w = vfik::block_rows(m, timed_dims(h, m), k, h->d_gotoq, h->d_goto_dist);
+    vfik_io b = *m.io;
+    b.q = w.q_prev;
+    b.goal_dist = w.dist;
+    if (m.joint && m.list) b.q_ref = h->d_js_ref;
+    b.active = m.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
+    const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0);
+    return rc != VFIK_OK ? rc : timed_launch_check(h, m, k, &w);
+}
+
+// q_out: the row the last executed block wrote; io->goal_dist beside a trace: the trace's last row
+int timed_end(vfik_handle* h, const TimedMove& m, int checks_run) {
+    if (checks_run < 1) return VFIK_OK;
+    const vfik::TimedDims d = timed_dims(h, m);
+    const vfik::BlockRows w = vfik::block_rows(m, d, checks_run - 1, h->d_gotoq, h->d_goto_dist);
+    if (m.x[vfik::X_Q_OUT]) HIP_TRY(hipMemcpyAsync(m.x[vfik::X_Q_OUT], w.q_now, vfik::extra_bytes(vfik::X_Q_OUT, d, 1), hipMemcpyDeviceToDevice, h->stream));
+    if (m.x[vfik::X_DIST_TRAJ] && m.io->goal_dist)
+        HIP_TRY(hipMemcpyAsync(m.io->goal_dist, w.dist, vfik::extra_bytes(vfik::X_DIST_TRAJ, d, 1), hipMemcpyDeviceToDevice, h->stream));
+    return VFIK_OK;
+}
+
+// the device-pointer forms, after their check
+int timed_run(vfik_handle* h, TimedMove& m) {
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = timed_begin(h, m);
+    for (int k = 0; rc == VFIK_OK && k < m.n_checks; ++k) rc = timed_block(h, m, k);
+    return rc != VFIK_OK ? rc : timed_end(h, m, m.n_checks);
+}
+
+// an arm whose list has no item (NaN in the first element of its first row, of row_len elements) is kept out like a gated one
+bool any_arm_kept_out(const vfik_handle* h, const void* way, size_t row_len) {
+    for (size_t b = 0; b < (size_t)h->B; ++b)
+        if (h->esz == 4 ? std::isnan(static_cast<const float*>(way)[b * row_len]) : std::isnan(static_cast<const double*>(way)[b * row_len])) return true;
+    return false;
 }
 
 // the early exit of the host forms: pending[done - 1] read back after every poll_checks checks
-int poll_pending(vfik_handle* h, const GotoRun& r, int done, int32_t* left) {
-    HIP_TRY(hipMemcpyAsync(left, r.pending + (done - 1), sizeof *left, hipMemcpyDeviceToHost, h->stream));
+int poll_pending(vfik_handle* h, const TimedMove& m, int done, int32_t* left) {
+    HIP_TRY(hipMemcpyAsync(left, static_cast<int32_t*>(m.x[vfik::X_PENDING]) + (done - 1), sizeof *left, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return VFIK_OK;
+}
+
+// The host-pointer forms, after their check: every member of io and of the options in ONE device buffer of the handle (grown on demand, members
+// 256-byte aligned), copied in before the first block and out after the last one executed.  A list is copied in with the inputs (way16's
+// alignment rule holds for the caller's array too, although the kernel reads the staged copy).  Under a gate the caller's rows of the gated
+// outputs go in before the blocks (vfik_io_layout.h: IO_EXTRAS).
+int timed_run_host(vfik_handle* h, TimedMove& m, int poll_checks, int* checks_run) {
+    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipSetDevice(h->device));
+    const vfik::TimedDims d = timed_dims(h, m);
+    IoStaging st(*m.io, h->B, h->io_dims());
+    vfik::timed_stage(st, m, d);
+    st.layout();
+    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
+    st.map(h->goto_stage.p);
+    int rc = copy_members(st, IoStaging::INPUTS, h->stream);
+    if (rc != VFIK_OK) return rc;
+    const bool kept_out = m.io->active || (m.list && any_arm_kept_out(h, m.x[m.joint ? vfik::X_WAYQ : vfik::X_WAY16], d.W * (m.joint ? d.n : 16)));
+    if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    const vfik_io dev_io = st.device_io();
+    m.io = &dev_io;
+    vfik::timed_rewire(st, m);
+    if ((rc = timed_begin(h, m)) != VFIK_OK) return rc;
+    int done = 0;
+    while (done < m.n_checks) {
+        if ((rc = timed_block(h, m, done)) != VFIK_OK) return rc;
+        ++done;
+        if (poll_checks > 0 && done % poll_checks == 0 && done < m.n_checks) {
+            int32_t left = -1;
+            if ((rc = poll_pending(h, m, done, &left)) != VFIK_OK) return rc;
+            if (left == 0) break;   // every arm that takes part and the caller lets run is there, or at its last item
+        }
+    }
+    if ((rc = timed_end(h, m, done)) != VFIK_OK) return rc;
+    IoStaging back = st;   // what goes back: of pending and the traces the checks that ran (st keeps the sizes its layout was made of)
+    vfik::timed_cut(back, d, done);
+    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (checks_run) *checks_run = done;
     return VFIK_OK;
 }
 }  // namespace
 
+int vfik_goto(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o) {
+    TimedMove m;
+    const int rc = goto_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run(h, m);
+}
+int vfik_goto_host(vfik_handle* h, const vfik_io* io, const vfik_goto_opts* o, int poll_checks, int* checks_run) {
+    TimedMove m;
+    const int rc = goto_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
+}
+int vfik_follow(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o) {
+    TimedMove m;
+    const int rc = follow_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run(h, m);
+}
+int vfik_follow_host(vfik_handle* h, const vfik_io* io, const vfik_follow_opts* o, int poll_checks, int* checks_run) {
+    TimedMove m;
+    const int rc = follow_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
+}
 int vfik_goto_js(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o) {
-    int rc = goto_js_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    GotoJsRun r;
-    if ((rc = goto_js_begin(h, io, o, r)) != VFIK_OK) return rc;
-    for (int k = 0; k < r.g.n_checks; ++k)
-        if ((rc = goto_js_block(h, r, k)) != VFIK_OK) return rc;
-    return goto_end(h, r.g, r.g.n_checks);
+    TimedMove m;
+    const int rc = goto_js_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run(h, m);
 }
-
-// Host-pointer form, as vfik_goto_host: io's members (q_ref among its inputs) and the options' arrays in the handle's staging buffer.  diff goes
-// in under a gate: a gated arm keeps its row.
 int vfik_goto_js_host(vfik_handle* h, const vfik_io* io, const vfik_goto_js_opts* o, int poll_checks, int* checks_run) {
-    int rc = goto_js_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    const int n_checks = o->n_cycles / o->stride;
-    const size_t qrow = (size_t)h->B * h->n * h->esz;
-    IoStaging st(*io, h->B, h->io_dims());
-    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
-    st.add(vfik::X_ARRIVED, o->arrived, (size_t)h->B * sizeof(int32_t), false);
-    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
-    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
-    st.add(vfik::X_DIFF, o->diff, qrow, true);
-    st.layout();
-    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
-    st.map(h->goto_stage.p);
-    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
-    if (io->active && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    const vfik_io d = st.device_io();
-    vfik_goto_js_opts od = *o;
-    od.arrived = static_cast<int32_t*>(st.extra(vfik::X_ARRIVED).dev);
-    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
-    od.q_out = st.extra(vfik::X_Q_OUT).dev;
-    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
-    od.diff = st.extra(vfik::X_DIFF).dev;
-    GotoJsRun r;
-    if ((rc = goto_js_begin(h, &d, &od, r)) != VFIK_OK) return rc;
-    int done = 0;
-    while (done < n_checks) {
-        if ((rc = goto_js_block(h, r, done)) != VFIK_OK) return rc;
-        ++done;
-        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
-            int32_t left = -1;
-            if ((rc = poll_pending(h, r.g, done, &left)) != VFIK_OK) return rc;
-            if (left == 0) break;   // everybody the caller lets run is there
-        }
-    }
-    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
-    IoStaging back = st;   // of pending and the trace the checks that ran
-    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
-    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
-    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (checks_run) *checks_run = done;
-    return VFIK_OK;
+    TimedMove m;
+    const int rc = goto_js_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
 }
-
 int vfik_follow_js(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o) {
-    int rc = follow_js_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    FollowJsRun r;
-    if ((rc = follow_js_begin(h, io, o, r)) != VFIK_OK) return rc;
-    for (int k = 0; k < r.g.n_checks; ++k)
-        if ((rc = follow_js_block(h, r, k)) != VFIK_OK) return rc;
-    return goto_end(h, r.g, r.g.n_checks);
+    TimedMove m;
+    const int rc = follow_js_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run(h, m);
 }
-
-// Host-pointer form, as vfik_follow_host: wayq copied in with the inputs
 int vfik_follow_js_host(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, int poll_checks, int* checks_run) {
-    int rc = follow_js_check(h, io, o);
-    if (rc != VFIK_OK) return rc;
-    if (poll_checks < 0) return fail(VFIK_E_ARG, "poll_checks %d: 0 (never) or a positive count of checks", poll_checks);
-    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
-    HIP_TRY(hipSetDevice(h->device));
-    const int n_checks = o->n_cycles / o->stride;
-    const size_t qrow = (size_t)h->B * h->n * h->esz, wrow = (size_t)h->B * sizeof(int32_t);
-    IoStaging st(*io, h->B, h->io_dims());
-    st.add(vfik::X_Q_OUT, o->q_out, qrow, false);
-    st.add(vfik::X_PENDING, o->pending, (size_t)n_checks * sizeof(int32_t), false, true);
-    st.add(vfik::X_Q_TRAJ, o->q_traj, (size_t)n_checks * qrow, false);
-    st.add(vfik::X_REACHED, o->reached, (size_t)h->B * o->n_way * sizeof(int32_t), false);
-    st.add(vfik::X_NEXT, o->next, wrow, false);
-    st.add(vfik::X_WAY_TRAJ, o->way_traj, (size_t)n_checks * wrow, true);
-    st.add(vfik::X_DIFF, o->diff, qrow, true);
-    st.add(vfik::X_WAYQ, const_cast<void*>(o->wayq), (size_t)o->n_way * qrow, false, false, true);
-    st.layout();
-    if (reserve(h, h->goto_stage, st.total, true, true)) return VFIK_E_HIP;
-    st.map(h->goto_stage.p);
-    if ((rc = copy_members(st, IoStaging::INPUTS, h->stream)) != VFIK_OK) return rc;
-    // an arm without a list is kept out like a gated one: its output rows go in before the blocks then, too
-    bool kept_out = io->active != nullptr;
-    for (size_t b = 0, row = (size_t)o->n_way * h->n; b < (size_t)h->B && !kept_out; ++b)
-        kept_out = h->esz == 4 ? std::isnan(static_cast<const float*>(o->wayq)[b * row]) : std::isnan(static_cast<const double*>(o->wayq)[b * row]);
-    if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    const vfik_io d = st.device_io();
-    vfik_follow_js_opts od = *o;
-    od.wayq = st.extra(vfik::X_WAYQ).dev;
-    od.reached = static_cast<int32_t*>(st.extra(vfik::X_REACHED).dev);
-    od.next = static_cast<int32_t*>(st.extra(vfik::X_NEXT).dev);
-    od.pending = static_cast<int32_t*>(st.extra(vfik::X_PENDING).dev);
-    od.q_out = st.extra(vfik::X_Q_OUT).dev;
-    od.q_traj = st.extra(vfik::X_Q_TRAJ).dev;
-    od.diff = st.extra(vfik::X_DIFF).dev;
-    od.way_traj = static_cast<int32_t*>(st.extra(vfik::X_WAY_TRAJ).dev);
-    FollowJsRun r;
-    if ((rc = follow_js_begin(h, &d, &od, r)) != VFIK_OK) return rc;
-    int done = 0;
-    while (done < n_checks) {
-        if ((rc = follow_js_block(h, r, done)) != VFIK_OK) return rc;
-        ++done;
-        if (poll_checks > 0 && done % poll_checks == 0 && done < n_checks) {
-            int32_t left = -1;
-            if ((rc = poll_pending(h, r.g, done, &left)) != VFIK_OK) return rc;
-            if (left == 0) break;   // every arm that takes part is at its last posture
-        }
-    }
-    if ((rc = goto_end(h, r.g, done)) != VFIK_OK) return rc;
-    IoStaging back = st;   // of pending and the traces the checks that ran
-    back.extra(vfik::X_PENDING).bytes = (size_t)done * sizeof(int32_t);
-    back.extra(vfik::X_Q_TRAJ).bytes = (size_t)done * qrow;
-    back.extra(vfik::X_WAY_TRAJ).bytes = (size_t)done * wrow;
-    if ((rc = copy_members(back, IoStaging::OUTPUTS, h->stream)) != VFIK_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (checks_run) *checks_run = done;
-    return VFIK_OK;
+    TimedMove m;
+    const int rc = follow_js_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
 }
 
 // ---- pipelined host path -------------------------------------------------------------------------

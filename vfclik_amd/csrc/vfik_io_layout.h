@@ -168,4 +168,87 @@ struct IoStaging {
     }
 };
 
+// ---- timed moves: vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js and their host forms ----
+// ONE description of a move between its checks and its last block.  The forms differ on two axes: the rule is the Cartesian distance pair or
+// the per-joint band (joint), the target one goal or a list with reached, next and len (list).
+struct TimedMove {
+    const vfik_io* io;
+    bool joint, list;
+    int n_cycles, stride, clamp, hold, n_way, n_checks;
+    double dt;
+    void* x[N_IO_EXTRA];   // the options' arrays, each under its IoExtra (device pointers; NULL: not given, or not one of this form's)
+    // joint: goal_precision per joint; Cartesian: [0] metres, [1] radians.  via_prec: a list's, at every item but an arm's last
+    double prec[VFIK_MAX_JOINTS], via_prec[VFIK_MAX_JOINTS];
+    bool gated;            // the blocks run under the handle's gate (hold, the caller gates, or a list -- an arm without one is kept out)
+};
+
+struct TimedDims { size_t B, n, esz, W, n_checks; };   // arms, joints, bytes of an I/O element, items per list, checks
+
+// What the host forms do with each IoExtra (IO_EXTRAS[X] describes TimedMove::x[X]).  row: the bytes of the whole array, or of ONE check's row of
+// a per-check trace -- which has n_checks of them and goes back cut to the checks that ran.  gated: an output that arms can leave unwritten
+// under the gate; always: staged without an array of the caller's too; input: copied in with io's inputs.
+struct IoExtraInfo {
+    size_t (*row)(const TimedDims&);
+    bool gated, always, input, per_check;
+};
+constexpr IoExtraInfo IO_EXTRAS[N_IO_EXTRA] = {
+    /* X_Q_OUT     */ {[](const TimedDims& d) { return d.B * d.n * d.esz; }, false, false, false, false},   // written for every arm at the end
+    /* X_ARRIVED   */ {[](const TimedDims& d) { return d.B * sizeof(int32_t); }, false, false, false, false},
+    /* X_PENDING   */ {[](const TimedDims&) { return sizeof(int32_t); }, false, true, false, true},         // the early exit reads it
+    /* X_Q_TRAJ    */ {[](const TimedDims& d) { return d.B * d.n * d.esz; }, false, false, false, true},    // a gated arm's rows repeat its start
+    /* X_DIST_TRAJ */ {[](const TimedDims& d) { return d.B * 2 * d.esz; }, true, false, false, true},
+    /* X_WAY16     */ {[](const TimedDims& d) { return d.B * d.W * 16 * d.esz; }, false, false, true, false},
+    /* X_REACHED   */ {[](const TimedDims& d) { return d.B * d.W * sizeof(int32_t); }, false, false, false, false},   // reached and next: written
+    /* X_NEXT      */ {[](const TimedDims& d) { return d.B * sizeof(int32_t); }, false, false, false, false},         // for every arm in front of block 0
+    /* X_WAY_TRAJ  */ {[](const TimedDims& d) { return d.B * sizeof(int32_t); }, true, false, false, true},
+    /* X_DIFF      */ {[](const TimedDims& d) { return d.B * d.n * d.esz; }, true, false, false, false},    // a gated arm keeps its row
+    /* X_WAYQ      */ {[](const TimedDims& d) { return d.B * d.W * d.n * d.esz; }, false, false, true, false},
+};
+inline size_t extra_bytes(IoExtra x, const TimedDims& d, size_t checks) { return IO_EXTRAS[x].row(d) * (IO_EXTRAS[x].per_check ? checks : 1); }
+
+// the extras a form stages, as bits 1 << IoExtra
+constexpr unsigned timed_extras(bool joint, bool list) {
+    return 1u << X_Q_OUT | 1u << X_PENDING | 1u << X_Q_TRAJ | 1u << (joint ? X_DIFF : X_DIST_TRAJ) |
+           (list ? 1u << X_REACHED | 1u << X_NEXT | 1u << X_WAY_TRAJ | 1u << (joint ? X_WAYQ : X_WAY16) : 1u << X_ARRIVED);
+}
+
+// The move's extras into a staging and its arrays rewired to their staged addresses (between the two: layout() and map()); the sizes of what
+// goes back after `done` checks.
+inline void timed_stage(IoStaging& st, const TimedMove& m, const TimedDims& d) {
+    for (int x = 0; x < N_IO_EXTRA; ++x)
+        if (timed_extras(m.joint, m.list) >> x & 1)
+            st.add((IoExtra)x, m.x[x], extra_bytes((IoExtra)x, d, d.n_checks), IO_EXTRAS[x].gated, IO_EXTRAS[x].always, IO_EXTRAS[x].input);
+}
+inline void timed_rewire(IoStaging& st, TimedMove& m) {
+    for (int x = 0; x < N_IO_EXTRA; ++x) m.x[x] = st.extra((IoExtra)x).dev;
+}
+inline void timed_cut(IoStaging& back, const TimedDims& d, size_t done) {
+    for (int x = 0; x < N_IO_EXTRA; ++x)
+        if (IO_EXTRAS[x].per_check) back.extra((IoExtra)x).bytes = extra_bytes((IoExtra)x, d, done);
+}
+
+// the rows of block k: the q it reads and writes, its goal_dist, and the trace's rows in front of it (NULL: no trace, or k = 0)
+struct BlockRows {
+    const void* q_prev;
+    void* q_now;
+    void* dist;
+    const void* dist_prev;
+    int32_t* way_now;
+    const int32_t* way_prev;
+};
+// q: the trace's rows, or the handle's pair by turns (pingpong); block 0 reads io->q.  dist: the trace's row, or io->goal_dist, or the handle's
+// row (handle_dist) -- a joint form has no distance row: its blocks' goal_dist is the caller's business.
+inline BlockRows block_rows(const TimedMove& m, const TimedDims& d, int k, void* const pingpong[2], void* handle_dist) {
+    auto row = [&](IoExtra x, int i) { return m.x[x] && i >= 0 ? static_cast<char*>(m.x[x]) + (size_t)i * IO_EXTRAS[x].row(d) : nullptr; };
+    auto q_row = [&](int i) { return m.x[X_Q_TRAJ] ? (void*)row(X_Q_TRAJ, i) : pingpong[i & 1]; };
+    BlockRows w;
+    w.q_prev = k == 0 ? m.io->q : q_row(k - 1);
+    w.q_now = q_row(k);
+    w.dist = m.x[X_DIST_TRAJ] ? row(X_DIST_TRAJ, k) : (m.io->goal_dist || m.joint ? m.io->goal_dist : handle_dist);
+    w.dist_prev = row(X_DIST_TRAJ, k - 1);
+    w.way_now = reinterpret_cast<int32_t*>(row(X_WAY_TRAJ, k));
+    w.way_prev = reinterpret_cast<const int32_t*>(row(X_WAY_TRAJ, k - 1));
+    return w;
+}
+
 }  // namespace vfik

@@ -549,86 +549,47 @@ struct SceneMoveArgs {
     int n_fun, n_hem, n_att, map_planes;
 };
 hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream);
-// vfik_goto: the arrival check that runs after block k of a goto (arrive_kernel, vfik_kernel.hip).  k < 0: the pass in front of block 0 --
-// arrived[b] = -1, gate[b] = the caller's gate -- and nothing else.
-struct ArriveArgs {
-    int* arrived;               // [B] cycle index of the arm's first successful check, -1 = not yet
+// The check that runs after block k of a timed move (check_kernel<T, JOINT, LIST>, vfik_kernel.hip), for all four forms: vfik_goto (Cartesian
+// rule, one goal), vfik_follow (Cartesian rule, a LIST of goal frames), vfik_goto_js (joint rule, io->q_ref) and vfik_follow_js (joint rule, a LIST
+// of postures).  A list form's check that finds an arm at item next[b] notes the cycle in reached[b][next], advances next[b] and sends the arm
+// to the following item: its frame into the arm's goal block (move_goal_row's stores), or its posture into the arm's row of `ref`.
+// k < 0: the pass in front of block 0 and nothing else -- one goal: arrived[b] = -1, gate[b] = the caller's gate; a list: reached = -1, next = 0,
+// len[b] = the arm's list length (leading rows of way[b] whose first element is not NaN), gate[b] = the caller's gate && len > 0, and item 0 into
+// the goal blocks of those arms, or into `ref` (there NaN for an arm kept out).
+// What every launch reads comes first (the dispatch object is compiled with kernel-argument preload); a member of the other rule or target is
+// not read.
+struct CheckArgs {
     int* gate;                  // [B] the handle's gate: what block k ran under on entry, what block k + 1 runs under on exit
     const int* active;          // [B] the caller's gate, or NULL = every arm
+    int* pending;               // &pending[k]: zeroed on the stream in front of the call
+    int B, n, W, k, stride, hold;   // W: items per list
+    long Bpad;
+    const void* q_prev;         // [B][n] the q row block k read
+    void* q_now;                // [B][n] the q row block k wrote
+    // What one form reads lies together, so that the Cartesian one-goal check finds its arguments in the first 120 bytes, as before the four
+    // checks had one struct, and the joint one's in one run up to `diff`: one goal, the Cartesian rule, the precisions, the joint rule's rows, then a
+    // list's members and its via precisions.
+    int* arrived;               // one goal: [B] cycle index of the arm's first successful check, -1 = not yet
+    // the Cartesian rule
     void* dist;                 // [B][2] goal_dist of block k (metres, degrees)
     const void* dist_prev;      // [B][2] the trace's row k - 1, or NULL (no trace, or k = 0): what an arm that did not run repeats
-    const void* q_prev;         // [B][n] the q row block k read
-    void* q_now;                // [B][n] the q row block k wrote
-    const void* goal;           // the goal block's 4 quad planes: plane 3, component 0 is its `present` flag
-    int* pending;               // &pending[k]: zeroed on the stream in front of the goto
-    double pos_prec, rot_prec;  // metres, radians
-    int B, n, k, stride, hold;
-    long Bpad;
-};
-hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream);
-// vfik_follow: ArriveArgs' sibling for arms that carry a LIST of goal frames (follow_kernel, vfik_kernel.hip).  The check that finds an arm at
-// waypoint next[b] notes the cycle in reached[b][next], advances next[b] and writes the frame of the following waypoint into the arm's goal
-// block -- move_goal_row's stores.  k < 0: the pass in front of block 0 -- reached = -1, next = 0, len[b] = the arm's path length (leading
-// rows of way16[b] whose first element is not NaN), gate[b] = the caller's gate && len > 0, waypoint 0 into the goal blocks of those arms.
-struct FollowArgs {
-    int* reached;               // [B][W] cycle index of the check that found the arm at waypoint w, -1 = not yet
-    int* next;                  // [B] waypoints reached so far = the index of the one under way
-    int* len;                   // [B] path lengths, a buffer of the handle: written by the k < 0 pass, read by every check
-    int* gate;                  // [B] the handle's gate, as ArriveArgs'
-    const int* active;          // [B] the caller's gate, or NULL = every arm
-    const void* way16;          // [B][W][16] the goal frames in order, 16-byte aligned
-    void* dist;                 // [B][2] goal_dist of block k (metres, degrees)
-    const void* dist_prev;      // [B][2] the trace's row k - 1, or NULL
-    const void* q_prev;         // [B][n] the q row block k read
-    void* q_now;                // [B][n] the q row block k wrote
-    void* goal;                 // the goal block's 4 quad planes: planes 0..2 are written, plane 3 component 0 is the `present` flag
-    int* pending;               // &pending[k]: zeroed on the stream in front of the call
-    int* way_now;               // [B] row k of way_traj -- the waypoint `dist` was measured against -- or NULL
-    const int* way_prev;        // [B] row k - 1 of way_traj, or NULL (no trace, or k = 0)
-    double pos_prec, rot_prec;          // metres, radians: at an arm's last waypoint
-    double via_pos_prec, via_rot_prec;  // at every waypoint before it
-    int B, n, W, k, stride, hold;
-    long Bpad;
-};
-hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream);
-// vfik_goto_js: ArriveArgs' sibling for the joint-space wait of set_ref_js (arrive_js_kernel, vfik_kernel.hip): the check reads the arm's row of
-// the reference the caller sent and the q row block k wrote, no distance row and no goal block.  k < 0: as ArriveArgs'.
-struct ArriveJsArgs {
-    int* arrived;               // [B] cycle index of the arm's first successful check, -1 = not yet
-    int* gate;                  // [B] the handle's gate, as ArriveArgs'
-    const int* active;          // [B] the caller's gate, or NULL = every arm
-    const void* ref;            // [B][n] io->q_ref as the caller sent it: a row that starts with NaN never arrives
-    const void* q_prev;         // [B][n] the q row block k read
-    void* q_now;                // [B][n] the q row block k wrote
+    void* goal;                 // the goal block's 4 quad planes: plane 3, component 0 is its `present` flag; a list writes planes 0..2
+    // joint: goal_precision per joint, entries at or beyond n are not read; Cartesian: [0] metres, [1] radians
+    double prec[VFIK_MAX_JOINTS];       // one goal, and at an arm's last item
+    // the joint rule
+    void* ref;                  // [B][n] one goal: io->q_ref as the caller sent it (read only), a row that starts with NaN never arrives;
+                                //        a list: the handle's reference row, the posture the arm is under way to, min(next, len - 1)
     void* diff;                 // [B][n] ref - q of every arm that ran block k, or NULL
-    int* pending;               // &pending[k]: zeroed on the stream in front of the call
-    double prec[VFIK_MAX_JOINTS];   // goal_precision per joint; entries at or beyond n are not read
-    int B, n, k, stride, hold;
-};
-hipError_t launch_arrive_js(int io_dtype, const ArriveJsArgs& g, hipStream_t stream);
-// vfik_follow_js: FollowArgs' sibling for arms that carry a LIST of postures (follow_js_kernel, vfik_kernel.hip).  The check that finds an arm at
-// posture next[b] notes the cycle in reached[b][next], advances next[b] and writes the following posture into the arm's row of `ref`, the
-// reference row of the handle that every block reads as io->q_ref.  k < 0: reached = -1, next = 0, len[b] = the arm's list length (leading rows of
-// wayq[b] whose first element is not NaN), gate[b] = the caller's gate && len > 0, and posture 0 -- for an arm kept out, NaN -- into `ref`.
-struct FollowJsArgs {
-    int* reached;               // [B][W] cycle index of the check that found the arm at posture w, -1 = not yet
-    int* next;                  // [B] postures reached so far = the index of the one under way
+    // a list
+    int* reached;               // [B][W] cycle index of the check that found the arm at item w, -1 = not yet
+    int* next;                  // [B] items reached so far = the index of the one under way
     int* len;                   // [B] list lengths, a buffer of the handle: written by the k < 0 pass, read by every check
-    int* gate;                  // [B] the handle's gate, as ArriveArgs'
-    const int* active;          // [B] the caller's gate, or NULL = every arm
-    const void* wayq;           // [B][W][n] the postures in order
-    void* ref;                  // [B][n] the handle's reference row: the posture the arm is under way to, min(next, len - 1)
-    const void* q_prev;         // [B][n] the q row block k read
-    void* q_now;                // [B][n] the q row block k wrote
-    void* diff;                 // [B][n] ref - q of every arm that ran block k, or NULL
-    int* pending;               // &pending[k]: zeroed on the stream in front of the call
-    int* way_now;               // [B] row k of way_traj -- the posture this check was made against -- or NULL
+    const void* way;            // Cartesian: way16 [B][W][16], the goal frames in order, 16-byte aligned; joint: wayq [B][W][n], the postures
+    int* way_now;               // [B] row k of way_traj -- the item this check was made against -- or NULL
     const int* way_prev;        // [B] row k - 1 of way_traj, or NULL (no trace, or k = 0)
-    double prec[VFIK_MAX_JOINTS];       // at an arm's last posture
-    double via_prec[VFIK_MAX_JOINTS];   // at every posture before it
-    int B, n, W, k, stride, hold;
+    double via_prec[VFIK_MAX_JOINTS];   // a list: at every item before an arm's last
 };
-hipError_t launch_follow_js(int io_dtype, const FollowJsArgs& g, hipStream_t stream);
+hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

@@ -14,7 +14,7 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, arrive_kernel, follow_kernel, arrive_js_kernel, follow_js_kernel.
+// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, check_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -2533,109 +2533,6 @@ __global__ void __launch_bounds__(256) track_kernel(const T* pose, const T* v6, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// vfik_goto: the arrival check of the reference's "send a goal, then wait until the arm is there" calls (handlers.py:346-440: gotoFrame
-// reads the object-0 entry of /dmonitor/distOut until pos_dist < goal_precision[0] and orient_dist * pi / 180 < goal_precision[1],
-// handlers.py:374-381), batched: one thread per arm after block k of a goto -- `stride` control cycles that ran under gate[] and left
-// their goal_dist row in `dist` and the integrated joint angles in q_now.
-//   the arm did not run (gate[b] == 0): the cycle kernel stored nothing for it -- its q row and, in a trace, its distance row repeat;
-//   it ran and has not arrived yet: arrived when both STRICT compares hold in double (NaN never arrives), at cycle (k + 1) * stride - 1,
-//     the 0-based cycle whose tool pose the distances were measured at.  An arm without a goal block never arrives: its goal_dist is
-//     measured against the zero frame of an empty block (a tool near the origin would pass), so the block's `present` flag decides;
-//   next block's gate: the caller's, and with `hold` not once the arm arrived;
-//   pending[k]: the arms the caller lets run that have not arrived -- a wave ballot, one atomic add per wave.
-// Rows of n elements per lane, as the cycle kernel's q_out store; no LDS, no scratch.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) arrive_kernel(const ArriveArgs g) {
-    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
-    bool under_way = false;
-    if (b < g.B) {
-        const bool ua = !g.active || g.active[b] != 0;
-        if (g.k < 0) {   // (uniform: the pass in front of block 0)
-            g.arrived[b] = -1;
-            g.gate[b] = ua ? 1 : 0;
-            return;
-        }
-        int arr = g.arrived[b];
-        T* const dn = static_cast<T*>(g.dist) + (long)b * 2;
-        if (g.gate[b] == 0) {
-            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
-            T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
-            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
-            if (g.dist_prev) {
-                const T* const dp = static_cast<const T*>(g.dist_prev) + (long)b * 2;
-                dn[0] = dp[0];
-                dn[1] = dp[1];
-            }
-        } else if (arr < 0) {
-            const bool present = static_cast<const T*>(g.goal)[(3 * g.Bpad + b) * 4] != (T)0;
-            const double d = (double)dn[0];
-            const double a = ((double)dn[1] * M_PI) / 180.0;
-            if (present && d < g.pos_prec && a < g.rot_prec) {
-                arr = (g.k + 1) * g.stride - 1;
-                g.arrived[b] = arr;
-            }
-        }
-        g.gate[b] = (ua && !(g.hold && arr >= 0)) ? 1 : 0;
-        under_way = ua && arr < 0;
-    } else if (g.k < 0) {
-        return;
-    }
-    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
-}
-
-// ------------------------------------------------------------------------------------------------
-// vfik_goto_js: the wait of the reference's joint-space motion call, HandleJController.set_ref_js(js, wait, goal_precision)
-// (handlers.py:544-576), batched: it sends js to /jpctrl/ref and reads /bridge/encoders until
-//     ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
-// and returns (result, js - q).  arrive_kernel's sibling, one thread per arm after block k: `ref` is the arm's row of io->q_ref as the caller
-// sent it (not the clamped value the controller keeps), q the row the block integrated.  Both edges are computed as written, in double on the
-// io-typed values, both compares non-strict; NaN in q or in the row fails a compare, so it never arrives -- a row that starts with NaN (an arm
-// without a controller) included.  diff = (T)(ref - q) for every arm that ran the block; an arm that did not repeats its q row and keeps its
-// diff row.  Gate, hold, arrived and pending[k] as arrive_kernel.  The precisions come by value and are indexed by the uniform loop counter
-// alone: scalar loads from the kernel arguments.  No LDS, no scratch.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) arrive_js_kernel(const ArriveJsArgs g) {
-    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
-    bool under_way = false;
-    if (b < g.B) {
-        const bool ua = !g.active || g.active[b] != 0;
-        if (g.k < 0) {   // (uniform: the pass in front of block 0)
-            g.arrived[b] = -1;
-            g.gate[b] = ua ? 1 : 0;
-            return;
-        }
-        int arr = g.arrived[b];
-        T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
-        if (g.gate[b] == 0) {
-            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
-            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
-        } else {
-            const T* const rf = static_cast<const T*>(g.ref) + (long)b * g.n;
-            T* const df = g.diff ? static_cast<T*>(g.diff) + (long)b * g.n : nullptr;
-            bool ok = true;
-            for (int i = 0; i < g.n; ++i) {
-                const double r = (double)rf[i], q = (double)qn[i], p = g.prec[i];
-                ok = ok & ((r - p) <= q) & ((r + p) >= q);
-                if (df) df[i] = (T)(r - q);
-            }
-            if (arr < 0 && ok) {
-                arr = (g.k + 1) * g.stride - 1;
-                g.arrived[b] = arr;
-            }
-        }
-        g.gate[b] = (ua && !(g.hold && arr >= 0)) ? 1 : 0;
-        under_way = ua && arr < 0;
-    } else if (g.k < 0) {
-        return;
-    }
-    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
-}
-
-// ------------------------------------------------------------------------------------------------
 // Distance monitor of scripts/monitor_distance (monitor_distance:76-84,148-167), batched: for every arm
 // and every object frame it was told about (/dmonitor/objectsIn: the goal is object 0, obstacles
 // follow), the xyz distance between the tool pose and the object and the rotation angle between their
@@ -2901,19 +2798,43 @@ __global__ void __launch_bounds__(256) move_scene_kernel(const SceneMoveArgs s) 
 }
 
 // ------------------------------------------------------------------------------------------------
-// vfik_follow: a user of the reference sends a LIST of gotoFrame calls -- approach, grasp, lift, place -- each the moment the previous one
-// returned true (handlers.py:346-387).  arrive_kernel's check for arms that carry such a list, way16[B][W][16]: one thread per arm after
-// block k, the same distance row, the same strict compares in double (NaN never arrives), the same `present` rule.  An arm found at
-// waypoint next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its path goes on -- the frame of waypoint next + 1
-// in its goal block: move_goal_row's three quad stores (lanes run over arms: a wave's stores to a plane lie in one 1 KiB row; plane 3 --
-// present, slow-down, force, speedScale -- stays), loaded as whole quads by the arriving lanes alone.  At most one waypoint per check: the
-// distance to the new goal exists only after the next block (gotoFrame drops its first read for the same reason, handlers.py:365-384).
-//   precision    (via_pos_prec, via_rot_prec) while a waypoint follows, (pos_prec, rot_prec) at the arm's last one;
-//   gate         the caller's && len > 0 && !(hold && next == len); an arm the gate kept out repeats its q, distance and waypoint rows;
-//   pending[k]   arms that take part and have next < len -- a wave ballot, one atomic add per wave;
-//   way_now[b]   the waypoint the distance row of this check was measured against: min(next, len - 1) on entry.
-// k < 0 (uniform): reached = -1, next = 0, len = leading rows of way16[b] that do not start with NaN, the gate, and waypoint 0 into the goal
-// block of every arm that takes part and has one.  No LDS, no scratch, no register array.
+// The check after block k of a timed move -- `stride` control cycles that ran under gate[] and left the integrated joint angles in q_now: one
+// thread per arm, one kernel for two RULES (JOINT) and two TARGETS (LIST).
+// The Cartesian rule (vfik_goto, vfik_follow): the arrival check of the reference's "send a goal, then wait until the arm is there" calls
+//   (handlers.py:346-440: gotoFrame reads the object-0 entry of /dmonitor/distOut until pos_dist < goal_precision[0] and
+//   orient_dist * pi / 180 < goal_precision[1], handlers.py:374-381) on the goal_dist row the block left in `dist`.  Both compares STRICT, in
+//   double (NaN never arrives), and only while the arm is under way.  An arm without a goal block never arrives: its goal_dist is measured
+//   against the zero frame of an empty block (a tool near the origin would pass), so the block's `present` flag decides.
+// The joint rule (vfik_goto_js, vfik_follow_js): the wait of the reference's joint-space motion call, HandleJController.set_ref_js(js, wait,
+//   goal_precision) (handlers.py:544-576), which sends js to /jpctrl/ref and reads /bridge/encoders until
+//       ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
+//   and returns (result, js - q).  `ref` is the arm's row of the reference as the caller sent it (not the clamped value the controller keeps), q the
+//   row the block integrated.  Both edges are computed as written, in double on the io-typed values, both compares non-strict; NaN in q or in
+//   the row fails a compare, so it never arrives -- a row that starts with NaN (an arm without a controller) included.  diff = (T)(ref - q) for
+//   every arm that ran the block, also after it arrived or finished its list.  The precisions come by value and are indexed by the uniform
+//   loop counter alone: scalar loads from the kernel arguments.
+// One goal: arrived[b] = (k + 1) * stride - 1 at the arm's first successful check, the 0-based cycle whose tool pose / joint angles were measured.
+// A list (vfik_follow: a user of the reference sends a LIST of gotoFrame calls -- approach, grasp, lift, place -- each the moment the previous
+//   one returned true, handlers.py:346-387; vfik_follow_js: a script of set_ref_js calls -- home posture, pre-grasp posture, ...), way[B][W][16]
+//   or [B][W][n]: an arm found at item next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its list goes on -- the
+//   following item as its target.  A frame goes into its goal block: move_goal_row's three quad stores (lanes run over arms: a wave's stores to a
+//   plane lie in one 1 KiB row; plane 3 -- present, slow-down, force, speedScale -- stays), loaded as whole quads by the arriving lanes alone.  A
+//   posture goes into its row of `ref`, the reference row of the HANDLE that every block reads as io->q_ref, copied element by element from
+//   wayq, so the rule reads the posture as the caller sent it.  At most one item per check: the distance to the new goal exists only after the
+//   next block (gotoFrame drops its first read for the same reason, handlers.py:365-384), and the controller has not moved towards the new
+//   posture yet.
+//     precision    via_prec while an item follows, prec at the arm's last one (joint: and past it, last = next >= len - 1);
+//     way_now[b]   the item this check was made against: min(next, len - 1) on entry.
+//   One goal is a list of one item here: len = 1, next = arrived >= 0.
+// For every form:
+//   the arm did not run (gate[b] == 0): the cycle kernel stored nothing for it -- its q row and, in a trace, its distance and item-index rows
+//     repeat, it keeps its diff;
+//   next block's gate: the caller's && len > 0 && !(hold && next == len) -- with `hold` not once the arm arrived or finished its list;
+//   pending[k]: the arms that take part and have next < len -- a wave ballot, one atomic add per wave.
+// k < 0 (uniform): one goal: arrived = -1; a list: reached = -1, next = 0, len = leading rows of way[b] that do not start with NaN; the gate; and
+// item 0 into the goal block of every arm that takes part and has one, or into the arm's row of `ref` -- NaN for an arm that does not take part:
+// no controller, the io->q_ref convention.
+// Rows of n elements per lane, as the cycle kernel's q_out store; no LDS, no scratch, no register array.
 // ------------------------------------------------------------------------------------------------
 // a quad as ONE value (a struct copy through MoveQuad would stay a 16 / 32-byte private object here: the frame's three loads come before the
 // stores they may alias); 16-byte aligned for either I/O type, which is what way16 and the planes guarantee
@@ -2930,121 +2851,102 @@ __device__ __forceinline__ void follow_goal_store(T* goal, int b, long Qp, const
     g[2 * Qp] = r2;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) follow_kernel(const FollowArgs g) {
+template <typename T, bool JOINT, bool LIST>
+__global__ void __launch_bounds__(256) check_kernel(const CheckArgs g) {
     const int b = (int)(blockIdx.x * 256 + threadIdx.x);
     bool under_way = false;
     if (b < g.B) {
         const bool ua = !g.active || g.active[b] != 0;
-        const T* const way = static_cast<const T*>(g.way16) + (long)b * g.W * 16;
+        const int row = JOINT ? g.n : 16;   // elements of a list's item
+        const T* const way = static_cast<const T*>(g.way) + (long)b * g.W * row;
         T* const goal = static_cast<T*>(g.goal);
         const long Qp = g.Bpad;   // quads per plane
-        const bool present = goal[(3 * Qp + b) * 4] != (T)0;
-        if (g.k < 0) {   // (uniform: the pass in front of block 0)
-            int L = 0;
-            while (L < g.W && way[(long)L * 16] == way[(long)L * 16]) ++L;
-            for (int w = 0; w < g.W; ++w) g.reached[(long)b * g.W + w] = -1;
-            g.next[b] = 0;
-            g.len[b] = L;
-            const bool in = ua && L > 0;
-            g.gate[b] = in ? 1 : 0;
-            if (in && present) follow_goal_store<T>(goal, b, Qp, way);
-            return;
-        }
-        const int L = g.len[b];
-        const bool in = ua && L > 0;
-        int nx = g.next[b];
-        T* const dn = static_cast<T*>(g.dist) + (long)b * 2;
-        if (g.gate[b] == 0) {
-            const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
-            T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
-            for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
-            if (g.dist_prev) {
-                const T* const dp = static_cast<const T*>(g.dist_prev) + (long)b * 2;
-                dn[0] = dp[0];
-                dn[1] = dp[1];
-            }
-            if (g.way_prev) g.way_now[b] = g.way_prev[b];
-        } else {
-            if (g.way_now) g.way_now[b] = nx < L ? nx : L - 1;
-            if (nx < L) {
-                const bool last = nx == L - 1;
-                const double d = (double)dn[0];
-                const double a = ((double)dn[1] * M_PI) / 180.0;
-                if (present && d < (last ? g.pos_prec : g.via_pos_prec) && a < (last ? g.rot_prec : g.via_rot_prec)) {
-                    g.reached[(long)b * g.W + nx] = (g.k + 1) * g.stride - 1;
-                    ++nx;
-                    g.next[b] = nx;
-                    if (nx < L) follow_goal_store<T>(goal, b, Qp, way + (long)nx * 16);
-                }
-            }
-        }
-        g.gate[b] = (in && !(g.hold && nx == L)) ? 1 : 0;
-        under_way = in && nx < L;
-    } else if (g.k < 0) {
-        return;
-    }
-    const int cnt = __popcll(__ballot(under_way));   // lanes at or beyond B count nothing
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(g.pending, cnt);
-}
-
-// ------------------------------------------------------------------------------------------------
-// vfik_follow_js: a script of set_ref_js calls -- home posture, pre-grasp posture, ... (handlers.py:544-576) -- as follow_kernel's state machine
-// with arrive_js_kernel's rule, for arms that carry a list of postures wayq[B][W][n].  `ref` is the reference row of the HANDLE that every block
-// reads as io->q_ref: it holds the posture the arm is under way to, min(next, len - 1), copied element by element from wayq, so the rule reads
-// the posture as the caller sent it.  An arm found at posture next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its
-// list goes on -- the following posture into its row.  At most one posture per check: the controller has not moved towards the new one yet.
-//   precision    via_prec while a posture follows, prec at the arm's last one;
-//   gate         the caller's && len > 0 && !(hold && next == len); an arm the gate kept out repeats its q and posture-index rows, keeps its diff;
-//   pending[k]   arms that take part and have next < len -- a wave ballot, one atomic add per wave;
-//   way_now[b]   the posture this check was made against: min(next, len - 1) on entry.
-// k < 0 (uniform): reached = -1, next = 0, len = leading rows of wayq[b] that do not start with NaN, the gate, and posture 0 into the arm's row --
-// NaN for an arm that does not take part: no controller, the io->q_ref convention.  No LDS, no scratch.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) follow_js_kernel(const FollowJsArgs g) {
-    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
-    bool under_way = false;
-    if (b < g.B) {
-        const bool ua = !g.active || g.active[b] != 0;
-        const T* const way = static_cast<const T*>(g.wayq) + (long)b * g.W * g.n;
         T* const rf = static_cast<T*>(g.ref) + (long)b * g.n;
+        // the goal block's flag: a list asks for it here, beside next and len, so that the rule does not wait for it behind them
+        bool present = false;
+        if constexpr (LIST && !JOINT) present = goal[(3 * Qp + b) * 4] != (T)0;
         if (g.k < 0) {   // (uniform: the pass in front of block 0)
-            int L = 0;
-            while (L < g.W && way[(long)L * g.n] == way[(long)L * g.n]) ++L;
-            for (int w = 0; w < g.W; ++w) g.reached[(long)b * g.W + w] = -1;
-            g.next[b] = 0;
-            g.len[b] = L;
-            const bool in = ua && L > 0;
+            bool in = ua;
+            if constexpr (LIST) {
+                int L = 0;
+                while (L < g.W && way[(long)L * row] == way[(long)L * row]) ++L;
+                for (int w = 0; w < g.W; ++w) g.reached[(long)b * g.W + w] = -1;
+                g.next[b] = 0;
+                g.len[b] = L;
+                in = ua && L > 0;
+            } else {
+                g.arrived[b] = -1;
+            }
             g.gate[b] = in ? 1 : 0;
-            for (int i = 0; i < g.n; ++i) rf[i] = in ? way[i] : (T)__builtin_nan("");
+            if constexpr (LIST && JOINT) {
+                for (int i = 0; i < g.n; ++i) rf[i] = in ? way[i] : (T)__builtin_nan("");
+            } else if constexpr (LIST) {
+                if (in && present) follow_goal_store<T>(goal, b, Qp, way);
+            }
             return;
         }
-        const int L = g.len[b];
+        int L = 1, nx;
+        if constexpr (LIST) {
+            L = g.len[b];
+            nx = g.next[b];
+        } else {
+            nx = g.arrived[b] >= 0 ? 1 : 0;
+        }
         const bool in = ua && L > 0;
-        int nx = g.next[b];
         T* const qn = static_cast<T*>(g.q_now) + (long)b * g.n;
         if (g.gate[b] == 0) {
             const T* const qp = static_cast<const T*>(g.q_prev) + (long)b * g.n;
             for (int i = 0; i < g.n; ++i) qn[i] = qp[i];
-            if (g.way_prev) g.way_now[b] = g.way_prev[b];
-        } else {
-            if (g.way_now) g.way_now[b] = nx < L ? nx : L - 1;
-            T* const df = g.diff ? static_cast<T*>(g.diff) + (long)b * g.n : nullptr;
-            const bool last = nx >= L - 1;
-            bool ok = true;
-            for (int i = 0; i < g.n; ++i) {
-                const double r = (double)rf[i], q = (double)qn[i], p = last ? g.prec[i] : g.via_prec[i];
-                ok = ok & ((r - p) <= q) & ((r + p) >= q);
-                if (df) df[i] = (T)(r - q);
+            if constexpr (!JOINT) {
+                if (g.dist_prev) {
+                    T* const dn = static_cast<T*>(g.dist) + (long)b * 2;
+                    const T* const dp = static_cast<const T*>(g.dist_prev) + (long)b * 2;
+                    dn[0] = dp[0];
+                    dn[1] = dp[1];
+                }
             }
-            if (nx < L && ok) {
-                g.reached[(long)b * g.W + nx] = (g.k + 1) * g.stride - 1;
-                ++nx;
-                g.next[b] = nx;
-                if (nx < L) {
-                    const T* const nw = way + (long)nx * g.n;
-                    for (int i = 0; i < g.n; ++i) rf[i] = nw[i];
+            if constexpr (LIST) {
+                if (g.way_prev) g.way_now[b] = g.way_prev[b];
+            }
+        } else {
+            if constexpr (LIST) {
+                if (g.way_now) g.way_now[b] = nx < L ? nx : L - 1;
+            }
+            const bool last = !LIST || nx >= L - 1;
+            bool there = false;
+            if constexpr (JOINT) {
+                T* const df = g.diff ? static_cast<T*>(g.diff) + (long)b * g.n : nullptr;
+                bool ok = true;
+                for (int i = 0; i < g.n; ++i) {
+                    const double r = (double)rf[i], q = (double)qn[i], p = last ? g.prec[i] : g.via_prec[i];
+                    ok = ok & ((r - p) <= q) & ((r + p) >= q);
+                    if (df) df[i] = (T)(r - q);
+                }
+                there = nx < L && ok;
+            } else if (nx < L) {
+                const T* const dn = static_cast<const T*>(g.dist) + (long)b * 2;
+                if constexpr (!LIST) present = goal[(3 * Qp + b) * 4] != (T)0;
+                const double d = (double)dn[0];
+                const double a = ((double)dn[1] * M_PI) / 180.0;
+                there = present && d < (last ? g.prec[0] : g.via_prec[0]) && a < (last ? g.prec[1] : g.via_prec[1]);
+            }
+            if (there) {
+                const int cycle = (g.k + 1) * g.stride - 1;
+                if constexpr (LIST) {
+                    g.reached[(long)b * g.W + nx] = cycle;
+                    ++nx;
+                    g.next[b] = nx;
+                    if (nx < L) {
+                        const T* const nw = way + (long)nx * row;
+                        if constexpr (JOINT) {
+                            for (int i = 0; i < g.n; ++i) rf[i] = nw[i];
+                        } else {
+                            follow_goal_store<T>(goal, b, Qp, nw);
+                        }
+                    }
+                } else {
+                    g.arrived[b] = cycle;
+                    nx = 1;
                 }
             }
         }
@@ -3971,31 +3873,20 @@ hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* 
     return hipGetLastError();
 }
 
-hipError_t launch_arrive(int io_dtype, const ArriveArgs& g, hipStream_t stream) {
+hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream) {
     const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
-    if (io_dtype == 32) hipLaunchKernelGGL(arrive_kernel<float>, grid, blk, 0, stream, g);
-    else hipLaunchKernelGGL(arrive_kernel<double>, grid, blk, 0, stream, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_follow(int io_dtype, const FollowArgs& g, hipStream_t stream) {
-    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
-    if (io_dtype == 32) hipLaunchKernelGGL(follow_kernel<float>, grid, blk, 0, stream, g);
-    else hipLaunchKernelGGL(follow_kernel<double>, grid, blk, 0, stream, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_arrive_js(int io_dtype, const ArriveJsArgs& g, hipStream_t stream) {
-    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
-    if (io_dtype == 32) hipLaunchKernelGGL(arrive_js_kernel<float>, grid, blk, 0, stream, g);
-    else hipLaunchKernelGGL(arrive_js_kernel<double>, grid, blk, 0, stream, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_follow_js(int io_dtype, const FollowJsArgs& g, hipStream_t stream) {
-    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
-    if (io_dtype == 32) hipLaunchKernelGGL(follow_js_kernel<float>, grid, blk, 0, stream, g);
-    else hipLaunchKernelGGL(follow_js_kernel<double>, grid, blk, 0, stream, g);
+    auto launch = [&](auto t) {
+        typedef decltype(t) T;
+        if (joint) {
+            if (list) hipLaunchKernelGGL((check_kernel<T, true, true>), grid, blk, 0, stream, g);
+            else hipLaunchKernelGGL((check_kernel<T, true, false>), grid, blk, 0, stream, g);
+        } else {
+            if (list) hipLaunchKernelGGL((check_kernel<T, false, true>), grid, blk, 0, stream, g);
+            else hipLaunchKernelGGL((check_kernel<T, false, false>), grid, blk, 0, stream, g);
+        }
+    };
+    if (io_dtype == 32) launch(0.0f);
+    else launch(0.0);
     return hipGetLastError();
 }
 }  // namespace vfik

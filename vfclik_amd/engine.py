@@ -546,14 +546,73 @@ class Engine:
         """Asynchronous device-pointer form of :meth:`rollout_host`."""
         self._chk(self.lib.vfik_rollout(self.h, C.byref(io), int(n_cycles), float(dt), 1 if clamp else 0, C.c_void_p(_ptr(q_out))))
 
-    # -- batched goto (vfik_goto: handlers.py:346-440 for the batch) --------------------------------
-    def _goto_opts(self, n_cycles, dt, precision, stride, hold, clamp):
-        pos, rot = precision
-        o = _abi.GotoOpts()
+    # -- timed moves: batched goto, waypoint lists and their joint-space forms (vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js:
+    #    handlers.py:346-440 and set_ref_js, handlers.py:544-576, for the batch) --------------------------------------------------
+    @staticmethod
+    def _move_opts(cls, n_cycles, dt, stride, hold, clamp):
+        o = cls()
         o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
         o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
-        o.pos_prec, o.rot_prec = float(pos), float(rot)
         return o
+
+    def _check_dev(self, specs):
+        """Contiguity, dtype and shape of the device arrays of a goto / follow call: (name, array, shape or None, dtype name) each."""
+        for name, x, shape, dt_name in specs:
+            if x is None or isinstance(x, int):
+                continue
+            if not x.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            if str(x.dtype).split(".")[-1] != dt_name or (shape is not None and tuple(x.shape) != shape):
+                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
+
+    def _dev_specs(self, o, **arrays):
+        """:meth:`_check_dev`'s specs of the options' arrays by their names, for the device forms."""
+        B, n, ft, n_checks = self.batch, self.n, self.io_dtype.name, o.n_cycles // max(o.stride, 1)
+        shapes = {"arrived": ((B,), "int32"), "reached": ((B, getattr(o, "n_way", 0)), "int32"), "next": ((B,), "int32"),
+                  "pending": ((n_checks,), "int32"), "q_out": ((B, n), ft), "diff": ((B, n), ft), "q_traj": ((n_checks, B, n), ft),
+                  "dist_traj": ((n_checks, B, 2), ft), "way_traj": ((n_checks, B), "int32"), "way": (None, ft), "wayq": (None, ft)}
+        return tuple((k, x) + shapes[k] for k, x in arrays.items())
+
+    @staticmethod
+    def _list_len(name, x, well_formed, form, items, n_way):
+        """n_way of a device form's list argument (way or wayq): a tensor's own, which an n_way beside it must agree with; a raw address
+        needs n_way."""
+        if isinstance(x, int):
+            if n_way is None:
+                raise ValueError("a raw %s address needs n_way" % name)
+            return n_way
+        if not well_formed(x):
+            raise ValueError("%s must be %s, got %s" % (name, form, tuple(x.shape)))
+        if n_way is not None and n_way != x.shape[1]:
+            raise ValueError("%s: %d %s per arm, n_way says %d" % (name, x.shape[1], items, n_way))
+        return x.shape[1]
+
+    def _move_host(self, fn, io, o, out, keep, poll, arrays, traces):
+        """The tail of the host forms: ``q``, the options' ``arrays`` and ``traces`` (by name) allocated with their fill values and wired
+        into ``o``, the call, ``checks_run``, and ``pending`` and the traces cut to the checks that ran."""
+        B, n, ft, n_checks = self.batch, self.n, self.io_dtype, max(o.n_cycles // max(o.stride, 1), 0)
+        kinds = {"arrived": ((B,), np.int32, -1), "reached": ((B, getattr(o, "n_way", 0)), np.int32, -1), "next": ((B,), np.int32, 0),
+                 "pending": ((n_checks,), np.int32, 0), "diff": ((B, n), ft, 0), "q_traj": ((n_checks, B, n), ft, 0),
+                 "dist_traj": ((n_checks, B, 2), ft, 0), "way_traj": ((n_checks, B), np.int32, -1)}
+        out["q"] = keep["q"].copy()
+        o.q_out = out["q"].ctypes.data
+        for k in arrays + traces:
+            shape, dtype, fill = kinds[k]
+            out[k] = np.full(shape, fill, dtype=dtype)
+            setattr(o, k, out[k].ctypes.data)
+        ran = C.c_int(0)
+        self._chk(fn(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
+        out["checks_run"] = int(ran.value)
+        for k in ("pending",) + traces:
+            out[k] = out[k][:out["checks_run"]]
+        return out
+
+    def _js_precision(self, precision, name="precision"):
+        """goal_precision per joint as the library reads it: float64 (n,), each >= 0 and not NaN."""
+        p = np.ascontiguousarray(precision, dtype=np.float64)
+        if p.shape != (self.n,):
+            raise ValueError("%s must be a sequence of %d values (one per joint), got shape %s" % (name, self.n, p.shape))
+        return p
 
     def goto(self, io, n_cycles, dt, precision, stride=1, hold=False, clamp=False, arrived=None, pending=None, q_out=None, q_traj=None,
              dist_traj=None):
@@ -565,18 +624,9 @@ class Engine:
         ``hold``: an arm that arrived takes no further cycle."""
         if arrived is None:
             raise ValueError("goto needs arrived, an int32 (batch,) device array")
-        n_checks = int(n_cycles) // max(int(stride), 1)
-        for name, x, shape, dt_name in (("arrived", arrived, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
-                                        ("q_out", q_out, (self.batch, self.n), self.io_dtype.name),
-                                        ("q_traj", q_traj, (n_checks, self.batch, self.n), self.io_dtype.name),
-                                        ("dist_traj", dist_traj, (n_checks, self.batch, 2), self.io_dtype.name)):
-            if x is None or isinstance(x, int):
-                continue
-            if not x.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-            if str(x.dtype).split(".")[-1] != dt_name or tuple(x.shape) != shape:
-                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
-        o = self._goto_opts(n_cycles, dt, precision, stride, hold, clamp)
+        o = self._move_opts(_abi.GotoOpts, n_cycles, dt, stride, hold, clamp)
+        self._check_dev(self._dev_specs(o, arrived=arrived, pending=pending, q_out=q_out, q_traj=q_traj, dist_traj=dist_traj))
+        o.pos_prec, o.rot_prec = map(float, precision)
         o.arrived, o.pending, o.q_out, o.q_traj, o.dist_traj = _ptr(arrived), _ptr(pending), _ptr(q_out), _ptr(q_traj), _ptr(dist_traj)
         self._chk(self.lib.vfik_goto(self.h, C.byref(io), C.byref(o)))
 
@@ -588,34 +638,15 @@ class Engine:
         (checks_run, B, 2).  ``poll`` > 0: after every ``poll`` checks the count of arms still under way is read back and the goto ends
         once it is 0 -- ``checks_run`` then tells how far it went.  Arms gated off by ``active`` never run and never arrive."""
         io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
-        o = self._goto_opts(n_cycles, dt, precision, stride, hold, clamp)
-        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
-        out["q"] = keep["q"].copy()
-        out["arrived"] = np.full(self.batch, -1, dtype=np.int32)
-        out["pending"] = np.zeros(n_checks, dtype=np.int32)
-        o.q_out, o.arrived, o.pending = out["q"].ctypes.data, out["arrived"].ctypes.data, out["pending"].ctypes.data
-        if trajectory:
-            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
-            out["dist_traj"] = np.zeros((n_checks, self.batch, 2), dtype=self.io_dtype)
-            o.q_traj, o.dist_traj = out["q_traj"].ctypes.data, out["dist_traj"].ctypes.data
-        ran = C.c_int(0)
-        self._chk(self.lib.vfik_goto_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
-        out["checks_run"] = int(ran.value)
-        for k in ("pending", "q_traj", "dist_traj"):
-            if k in out:
-                out[k] = out[k][:out["checks_run"]]
-        return out
+        o = self._move_opts(_abi.GotoOpts, n_cycles, dt, stride, hold, clamp)
+        o.pos_prec, o.rot_prec = map(float, precision)
+        return self._move_host(self.lib.vfik_goto_host, io, o, out, keep, poll, ("arrived", "pending"),
+                               ("q_traj", "dist_traj") if trajectory else ())
 
-    # -- waypoint lists (vfik_follow: a script of gotoFrame calls for the batch) ---------------------
-    def _follow_opts(self, n_way, n_cycles, dt, precision, via_precision, stride, hold, clamp):
-        pos, rot = precision
-        via_pos, via_rot = precision if via_precision is None else via_precision
-        o = _abi.FollowOpts()
-        o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
-        o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
-        o.pos_prec, o.rot_prec, o.via_pos_prec, o.via_rot_prec = float(pos), float(rot), float(via_pos), float(via_rot)
-        o.n_way = int(n_way)
-        return o
+    @staticmethod
+    def _follow_precision(o, precision, via_precision):
+        o.pos_prec, o.rot_prec = map(float, precision)
+        o.via_pos_prec, o.via_rot_prec = map(float, precision if via_precision is None else via_precision)
 
     def follow(self, io, way, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, reached=None, next=None,
                pending=None, q_out=None, q_traj=None, dist_traj=None, way_traj=None, n_way=None):
@@ -632,28 +663,13 @@ class Engine:
         layer does not learn of it, as with :meth:`move_fields`: a later ``set_fields`` from the mirror puts the old goal back."""
         if reached is None or next is None:
             raise ValueError("follow needs reached, an int32 (batch, n_way) device array, and next, an int32 (batch,) one")
-        if not isinstance(way, int):
-            if way.dim() not in (3, 4) or way.shape[0] != self.batch or way.numel() != self.batch * way.shape[1] * 16:
-                raise ValueError("way must be (batch, n_way, 16) or (batch, n_way, 4, 4), got %s" % (tuple(way.shape),))
-            if n_way is not None and n_way != way.shape[1]:
-                raise ValueError("way: %d waypoints per arm, n_way says %d" % (way.shape[1], n_way))
-            n_way = way.shape[1]
-        elif n_way is None:
-            raise ValueError("a raw way address needs n_way")
-        n_checks = int(n_cycles) // max(int(stride), 1)
-        ft = self.io_dtype.name
-        for name, x, shape, dt_name in (("way", way, None, ft), ("reached", reached, (self.batch, n_way), "int32"),
-                                        ("next", next, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
-                                        ("q_out", q_out, (self.batch, self.n), ft), ("q_traj", q_traj, (n_checks, self.batch, self.n), ft),
-                                        ("dist_traj", dist_traj, (n_checks, self.batch, 2), ft),
-                                        ("way_traj", way_traj, (n_checks, self.batch), "int32")):
-            if x is None or isinstance(x, int):
-                continue
-            if not x.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-            if str(x.dtype).split(".")[-1] != dt_name or (shape is not None and tuple(x.shape) != shape):
-                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
-        o = self._follow_opts(n_way, n_cycles, dt, precision, via_precision, stride, hold, clamp)
+        n_way = self._list_len("way", way, lambda w: w.dim() in (3, 4) and w.shape[0] == self.batch and w.numel() == self.batch * w.shape[1] * 16,
+                               "(batch, n_way, 16) or (batch, n_way, 4, 4)", "waypoints", n_way)
+        o = self._move_opts(_abi.FollowOpts, n_cycles, dt, stride, hold, clamp)
+        o.n_way = int(n_way)
+        self._check_dev(self._dev_specs(o, way=way, reached=reached, next=next, pending=pending, q_out=q_out, q_traj=q_traj,
+                                        dist_traj=dist_traj, way_traj=way_traj))
+        self._follow_precision(o, precision, via_precision)
         o.way16, o.reached, o.next, o.pending = _ptr(way), _ptr(reached), _ptr(next), _ptr(pending)
         o.q_out, o.q_traj, o.dist_traj, o.way_traj = _ptr(q_out), _ptr(q_traj), _ptr(dist_traj), _ptr(way_traj)
         self._chk(self.lib.vfik_follow(self.h, C.byref(io), C.byref(o)))
@@ -675,50 +691,11 @@ class Engine:
             buf[...] = w
             w = buf
         io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
-        o = self._follow_opts(w.shape[1], n_cycles, dt, precision, via_precision, stride, hold, clamp)
-        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
-        out["q"] = keep["q"].copy()
-        out["reached"] = np.full((self.batch, w.shape[1]), -1, dtype=np.int32)
-        out["next"] = np.zeros(self.batch, dtype=np.int32)
-        out["pending"] = np.zeros(n_checks, dtype=np.int32)
-        o.way16, o.q_out, o.reached, o.next, o.pending = (w.ctypes.data, out["q"].ctypes.data, out["reached"].ctypes.data,
-                                                          out["next"].ctypes.data, out["pending"].ctypes.data)
-        if trajectory:
-            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
-            out["dist_traj"] = np.zeros((n_checks, self.batch, 2), dtype=self.io_dtype)
-            out["way_traj"] = np.full((n_checks, self.batch), -1, dtype=np.int32)
-            o.q_traj, o.dist_traj, o.way_traj = out["q_traj"].ctypes.data, out["dist_traj"].ctypes.data, out["way_traj"].ctypes.data
-        ran = C.c_int(0)
-        self._chk(self.lib.vfik_follow_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
-        out["checks_run"] = int(ran.value)
-        for k in ("pending", "q_traj", "dist_traj", "way_traj"):
-            if k in out:
-                out[k] = out[k][:out["checks_run"]]
-        return out
-
-    # -- joint-space goto and posture lists (vfik_goto_js / vfik_follow_js: set_ref_js, handlers.py:544-576, for the batch) --------
-    def _js_precision(self, precision, name="precision"):
-        """goal_precision per joint as the library reads it: float64 (n,), each >= 0 and not NaN."""
-        p = np.ascontiguousarray(precision, dtype=np.float64)
-        if p.shape != (self.n,):
-            raise ValueError("%s must be a sequence of %d values (one per joint), got shape %s" % (name, self.n, p.shape))
-        return p
-
-    def _js_opts(self, cls, n_cycles, dt, stride, hold, clamp):
-        o = cls()
-        o.n_cycles, o.stride, o.dt = int(n_cycles), int(stride), float(dt)
-        o.clamp_to_limits, o.hold = (1 if clamp else 0), (1 if hold else 0)
-        return o
-
-    def _check_dev(self, specs):
-        """Contiguity, dtype and shape of the device arrays of a goto / follow call: (name, array, shape or None, dtype name) each."""
-        for name, x, shape, dt_name in specs:
-            if x is None or isinstance(x, int):
-                continue
-            if not x.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-            if str(x.dtype).split(".")[-1] != dt_name or (shape is not None and tuple(x.shape) != shape):
-                raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt_name, shape, x.dtype, tuple(x.shape)))
+        o = self._move_opts(_abi.FollowOpts, n_cycles, dt, stride, hold, clamp)
+        self._follow_precision(o, precision, via_precision)
+        o.n_way, o.way16 = w.shape[1], w.ctypes.data
+        return self._move_host(self.lib.vfik_follow_host, io, o, out, keep, poll, ("reached", "next", "pending"),
+                               ("q_traj", "dist_traj", "way_traj") if trajectory else ())
 
     def goto_js(self, io, n_cycles, dt, precision, stride=1, hold=False, clamp=False, arrived=None, pending=None, q_out=None, q_traj=None,
                 diff=None):
@@ -730,13 +707,9 @@ class Engine:
         with ``F_MIXER``)."""
         if arrived is None:
             raise ValueError("goto_js needs arrived, an int32 (batch,) device array")
-        n_checks = int(n_cycles) // max(int(stride), 1)
-        ft = self.io_dtype.name
-        self._check_dev((("arrived", arrived, (self.batch,), "int32"), ("pending", pending, (n_checks,), "int32"),
-                         ("q_out", q_out, (self.batch, self.n), ft), ("q_traj", q_traj, (n_checks, self.batch, self.n), ft),
-                         ("diff", diff, (self.batch, self.n), ft)))
+        o = self._move_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
+        self._check_dev(self._dev_specs(o, arrived=arrived, pending=pending, q_out=q_out, q_traj=q_traj, diff=diff))
         prec = self._js_precision(precision)
-        o = self._js_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
         o.prec = prec.ctypes.data
         o.arrived, o.pending, o.q_out, o.q_traj, o.diff = _ptr(arrived), _ptr(pending), _ptr(q_out), _ptr(q_traj), _ptr(diff)
         self._chk(self.lib.vfik_goto_js(self.h, C.byref(io), C.byref(o)))
@@ -751,24 +724,18 @@ class Engine:
             raise ValueError("goto_js_host needs q_ref, the joint reference of every arm")
         io, out, keep = self._host_io(q, null_control, q_ref, None, active, q_lo, q_hi, want)
         prec = self._js_precision(precision)
-        o = self._js_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
-        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
-        out["q"] = keep["q"].copy()
-        out["arrived"] = np.full(self.batch, -1, dtype=np.int32)
-        out["pending"] = np.zeros(n_checks, dtype=np.int32)
-        out["diff"] = np.zeros((self.batch, self.n), dtype=self.io_dtype)
+        o = self._move_opts(_abi.GotoJsOpts, n_cycles, dt, stride, hold, clamp)
         o.prec = prec.ctypes.data
-        o.q_out, o.arrived, o.pending, o.diff = out["q"].ctypes.data, out["arrived"].ctypes.data, out["pending"].ctypes.data, out["diff"].ctypes.data
-        if trajectory:
-            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
-            o.q_traj = out["q_traj"].ctypes.data
-        ran = C.c_int(0)
-        self._chk(self.lib.vfik_goto_js_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
-        out["checks_run"] = int(ran.value)
-        for k in ("pending", "q_traj"):
-            if k in out:
-                out[k] = out[k][:out["checks_run"]]
-        return out
+        return self._move_host(self.lib.vfik_goto_js_host, io, o, out, keep, poll, ("arrived", "pending", "diff"),
+                               ("q_traj",) if trajectory else ())
+
+    def _follow_js_precision(self, o, precision, via_precision):
+        """The two precision arrays into the options; returned because the options hold their addresses only (the caller keeps them until
+        the call is over)."""
+        prec = self._js_precision(precision)
+        via = None if via_precision is None else self._js_precision(via_precision, "via_precision")
+        o.prec, o.via_prec = prec.ctypes.data, (None if via is None else via.ctypes.data)
+        return prec, via
 
     def follow_js(self, io, wayq, n_cycles, dt, precision, via_precision=None, stride=1, hold=False, clamp=False, reached=None, next=None,
                   pending=None, q_out=None, q_traj=None, diff=None, way_traj=None, n_way=None):
@@ -780,24 +747,13 @@ class Engine:
         on this device, or raw addresses (``wayq`` then with ``n_way``)."""
         if reached is None or next is None:
             raise ValueError("follow_js needs reached, an int32 (batch, n_way) device array, and next, an int32 (batch,) one")
-        if not isinstance(wayq, int):
-            if wayq.dim() != 3 or wayq.shape[0] != self.batch or wayq.shape[2] != self.n:
-                raise ValueError("wayq must be (batch, n_way, %d), got %s" % (self.n, tuple(wayq.shape)))
-            if n_way is not None and n_way != wayq.shape[1]:
-                raise ValueError("wayq: %d postures per arm, n_way says %d" % (wayq.shape[1], n_way))
-            n_way = wayq.shape[1]
-        elif n_way is None:
-            raise ValueError("a raw wayq address needs n_way")
-        n_checks = int(n_cycles) // max(int(stride), 1)
-        ft = self.io_dtype.name
-        self._check_dev((("wayq", wayq, None, ft), ("reached", reached, (self.batch, n_way), "int32"), ("next", next, (self.batch,), "int32"),
-                         ("pending", pending, (n_checks,), "int32"), ("q_out", q_out, (self.batch, self.n), ft),
-                         ("q_traj", q_traj, (n_checks, self.batch, self.n), ft), ("diff", diff, (self.batch, self.n), ft),
-                         ("way_traj", way_traj, (n_checks, self.batch), "int32")))
-        prec = self._js_precision(precision)
-        via = None if via_precision is None else self._js_precision(via_precision, "via_precision")
-        o = self._js_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
-        o.prec, o.via_prec, o.n_way = prec.ctypes.data, (None if via is None else via.ctypes.data), int(n_way)
+        n_way = self._list_len("wayq", wayq, lambda w: w.dim() == 3 and w.shape[0] == self.batch and w.shape[2] == self.n,
+                               "(batch, n_way, %d)" % self.n, "postures", n_way)
+        o = self._move_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
+        o.n_way = int(n_way)
+        self._check_dev(self._dev_specs(o, wayq=wayq, reached=reached, next=next, pending=pending, q_out=q_out, q_traj=q_traj, diff=diff,
+                                        way_traj=way_traj))
+        kept = self._follow_js_precision(o, precision, via_precision)  # noqa: F841
         o.wayq, o.reached, o.next, o.pending = _ptr(wayq), _ptr(reached), _ptr(next), _ptr(pending)
         o.q_out, o.q_traj, o.diff, o.way_traj = _ptr(q_out), _ptr(q_traj), _ptr(diff), _ptr(way_traj)
         self._chk(self.lib.vfik_follow_js(self.h, C.byref(io), C.byref(o)))
@@ -813,29 +769,11 @@ class Engine:
             raise ValueError("wayq must be (batch, n_way, %d), got %s" % (self.n, w.shape))
         w = np.ascontiguousarray(w, dtype=self.io_dtype)
         io, out, keep = self._host_io(q, null_control, None, None, active, q_lo, q_hi, want)
-        prec = self._js_precision(precision)
-        via = None if via_precision is None else self._js_precision(via_precision, "via_precision")
-        o = self._js_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
-        n_checks = max(o.n_cycles // max(o.stride, 1), 0)
-        out["q"] = keep["q"].copy()
-        out["reached"] = np.full((self.batch, w.shape[1]), -1, dtype=np.int32)
-        out["next"] = np.zeros(self.batch, dtype=np.int32)
-        out["pending"] = np.zeros(n_checks, dtype=np.int32)
-        out["diff"] = np.zeros((self.batch, self.n), dtype=self.io_dtype)
-        o.prec, o.via_prec, o.n_way = prec.ctypes.data, (None if via is None else via.ctypes.data), w.shape[1]
-        o.wayq, o.q_out, o.reached, o.next, o.pending, o.diff = (w.ctypes.data, out["q"].ctypes.data, out["reached"].ctypes.data,
-                                                                 out["next"].ctypes.data, out["pending"].ctypes.data, out["diff"].ctypes.data)
-        if trajectory:
-            out["q_traj"] = np.zeros((n_checks, self.batch, self.n), dtype=self.io_dtype)
-            out["way_traj"] = np.full((n_checks, self.batch), -1, dtype=np.int32)
-            o.q_traj, o.way_traj = out["q_traj"].ctypes.data, out["way_traj"].ctypes.data
-        ran = C.c_int(0)
-        self._chk(self.lib.vfik_follow_js_host(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
-        out["checks_run"] = int(ran.value)
-        for k in ("pending", "q_traj", "way_traj"):
-            if k in out:
-                out[k] = out[k][:out["checks_run"]]
-        return out
+        o = self._move_opts(_abi.FollowJsOpts, n_cycles, dt, stride, hold, clamp)
+        kept = self._follow_js_precision(o, precision, via_precision)  # noqa: F841
+        o.n_way, o.wayq = w.shape[1], w.ctypes.data
+        return self._move_host(self.lib.vfik_follow_js_host, io, o, out, keep, poll, ("reached", "next", "pending", "diff"),
+                               ("q_traj", "way_traj") if trajectory else ())
 
     def make_io(self, q, null_control=None, q_ref=None, q_cmded=None, active=None, q_lo=None, q_hi=None, **outs):
         """IO block from device pointers (torch tensors on this device, or raw addresses).  active: int32 [B]."""
