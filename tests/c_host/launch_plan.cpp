@@ -72,7 +72,6 @@ int main() {
         a.has_funnel = (int)get("funnel", 0);
         a.mixed = (int)get("mixed", 0);
         a.uni = (int)get("uni", 0);
-        a.pers = (int)get("pers", 0);
         a.waves2 = (int)get("waves2", 0);
         const bool ns = a.flags & VFIK_F_NULLSPACE;
         const vfik::CyclePlan p = vfik::plan_cycle(a, nj, io, ns, block);

@@ -19,10 +19,10 @@ CSRC = os.path.join(ROOT, "vfclik_amd", "csrc")
 LIB = os.path.join(CSRC, "libvfik_hip.so")
 OBJDUMP = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-objdump")
 
-# template parameters in the order the kernels declare them (vfik_kernel.hip)
+# template parameters in the order the kernels declare them (vfik_kernel.hip); RESERVED: the removed persistent launch's slot, false in every kernel
 PARAMS = {
-    "cycle_kernel_s": ("T", "NJ", "NS", "PL", "ROLL", "FASTF", "LEAN", "CF", "PERS", "FUN", "WAVES", "UNI", "D"),
-    "cycle_kernel_x": ("T", "NJ", "NS", "PL", "ROLL", "FASTF", "LEAN", "CF", "PERS", "FUN", "WAVES", "UNI", "MIXO", "D"),
+    "cycle_kernel_s": ("T", "NJ", "NS", "PL", "ROLL", "FASTF", "LEAN", "CF", "RESERVED", "FUN", "WAVES", "UNI", "D"),
+    "cycle_kernel_x": ("T", "NJ", "NS", "PL", "ROLL", "FASTF", "LEAN", "CF", "RESERVED", "FUN", "WAVES", "UNI", "MIXO", "D"),
     "cycle_kernel_m": ("T", "NJ", "NS", "LEAN", "FUN", "D"),
     "cycle_sub8_kernel": ("T", "NJ", "NS", "D"),
     "cycle_sub8_kernel_x": ("T", "NJ", "NS", "D"),
@@ -86,6 +86,7 @@ def library_variants(lib=LIB):
         heavy = len({group_of(parse(n))[1:] for n in names}) > 1
         for n in names:
             v = parse(n + HEAVY if heavy else n)
+            assert not v.args.get("RESERVED", False), "%s: the reserved template slot is true" % n
             if v.name in found or (n if heavy else n + HEAVY) in found:
                 raise AssertionError("%s is in two code objects of the library" % n)
             found[v.name] = v

@@ -1,7 +1,6 @@
 """Batches beyond one wave per SIMD: the two-waves-per-SIMD build of the lean launch (cycle_kernel, WAVES 2: the default there) and
-the persistent launch (cycle_kernel, PERS, VFIK_PERSISTENT=1: one wave per SIMD striding over the 64-arm chunks, the next chunk's
-inputs in flight into a second LDS area).  Parity against the oracle and against the launch in rounds of one wave per SIMD
-(VFIK_TWO_WAVES=0) on ragged batch sizes: waves with one, two and three chunks, a partial last chunk."""
+the launch in rounds of one wave per SIMD (VFIK_TWO_WAVES=0).  Parity against the oracle and between the two on ragged batch sizes:
+one to three rounds, a partial last wave.  (Until the persistent launch was removed this file ran it as a third mode.)"""
 import os
 
 import numpy as np
@@ -26,12 +25,12 @@ def env():
     return e
 
 
-MODES = ("rounds", "two", "pers")
+MODES = ("rounds", "two")
 
 
 def _engine(env, chain, B, nobs, params, mode):
-    """A handle whose big lean launches go in rounds of one wave per SIMD, as two waves per SIMD, or persistent."""
-    want = {"VFIK_PERSISTENT": "1" if mode == "pers" else "0", "VFIK_TWO_WAVES": "1" if mode == "two" else "0"}
+    """A handle whose big lean launches go in rounds of one wave per SIMD, or as two waves per SIMD."""
+    want = {"VFIK_TWO_WAVES": "1" if mode == "two" else "0"}
     old = {k: os.environ.get(k) for k in want}
     os.environ.update(want)
     try:
@@ -46,7 +45,7 @@ def _engine(env, chain, B, nobs, params, mode):
 
 
 @pytest.mark.parametrize("B,nobs", [(65536 + 64 * 3 + 17, 8), (131072 + 5, 8), (65536 * 2 + 64 * 700, 3), (65537, 11), (200000, 0)])
-def test_persistent_launch_matches_oracle_and_rounds(env, B, nobs):
+def test_big_launch_matches_oracle_and_rounds(env, B, nobs):
     chain = env.robots.lwr()
     params = env.abi.default_params()
     w = env.synth.make_workload(chain, B, nobs, seed=21, io_dtype=np.float32)
@@ -58,19 +57,18 @@ def test_persistent_launch_matches_oracle_and_rounds(env, B, nobs):
         outs[mode] = eng.step_host(w["q"], want=("qdot_out", "status"))
         kernels[mode] = eng.launched_kernels()
         eng.close()
-    # each mode took its own kernel: the lean variant of WAVES 1 (rounds), 2, or the persistent one (PERS)
+    # each mode took its own kernel: the lean variant of WAVES 1 (rounds) or 2; the reserved slot in front of them is false
     for mode in MODES:
         assert len(kernels[mode]) == 1, (mode, kernels[mode])
         k = kernels[mode].pop()
         assert k.startswith("cycle_kernel_s<float, 7, false,"), (mode, k)
-        pers, waves = k.split(", ")[8], k.split(", ")[10]
-        assert (pers, waves) == {"rounds": ("false", "1"), "two": ("false", "2"), "pers": ("true", "1")}[mode], (mode, k)
+        reserved, waves = k.split(", ")[8], k.split(", ")[10]
+        assert (reserved, waves) == {"rounds": ("false", "1"), "two": ("false", "2")}[mode], (mode, k)
     for mode in MODES:
         err = np.abs(outs[mode]["qdot_out"].astype(np.float64) - ref["qdot_out"])
         assert err.max() < 1e-6, (mode, float(err.max()), int(np.argmax(err.max(axis=1))))
         assert np.array_equal(outs[mode]["status"], ref["status"])
     # same arithmetic in every launch (another schedule): equal to rounding of the float32 store
-    assert np.abs(outs["pers"]["qdot_out"] - outs["rounds"]["qdot_out"]).max() < 1e-6
     assert np.abs(outs["two"]["qdot_out"] - outs["rounds"]["qdot_out"]).max() < 1e-6
 
 
@@ -92,10 +90,10 @@ def test_two_waves_build_of_the_other_lean_variants(env, robot, flags):
     assert np.array_equal(got["status"], ref["status"])
 
 
-@pytest.mark.parametrize("mode", ["two", "pers"])
+@pytest.mark.parametrize("mode", ["two"])
 def test_big_launch_with_the_nullspace_module_keeps_its_state(env, mode):
     """The default process set (nullspace + mixer) at 150 000 arms, three cycles: the sign memory of every arm advances
-    through the two-waves / the persistent launch exactly as through the oracle's state."""
+    through the two-waves launch exactly as through the oracle's state."""
     chain = env.robots.lwr()
     f = env.abi
     params = f.default_params(flags=f.F_NULLSPACE | f.F_MIXER)
@@ -118,7 +116,7 @@ def test_big_launch_with_the_nullspace_module_keeps_its_state(env, mode):
         eng.step(eng.make_io(qd, qdot_out=out, status=st))
         torch.cuda.synchronize()
         (k,) = eng.launched_kernels()
-        assert k.startswith("cycle_kernel_s<float, 7, true,") and (k.split(", ")[8], k.split(", ")[10]) == (("true", "1") if mode == "pers" else ("false", "2")), k
+        assert k.startswith("cycle_kernel_s<float, 7, true,") and (k.split(", ")[8], k.split(", ")[10]) == ("false", "2"), k
         ref = env.oc.cycle_batch(chain, params, q32.astype(np.float64), w["fields"], w["nfields"], states=states, want=("qdot_out", "status"))
         err = np.abs(out.cpu().numpy().astype(np.float64) - ref["qdot_out"])
         assert err.max() < 1e-6, (t, float(err.max()))

@@ -25,7 +25,7 @@ GROUPS = [(n, t, ns) for n in (6, 7, 10, 14) for t in (32, 64) for ns in (False,
 ROWS = ("qdot_vf", "qdot_null", "qdot_out", "pose", "pose_nt", "qdist", "status")
 LEAN = ("qdot_out", "status")
 B_SMALL = 64 * 3 + 13           # a partial last wave, not a multiple of 8 either (the eight-lanes kernel's blocks)
-B_BIG = 65536 + 64 * 2 + 37     # beyond one wave per SIMD (256 CUs): the persistent and the two-waves launches
+B_BIG = 65536 + 64 * 2 + 37     # beyond one wave per SIMD (256 CUs): the two-waves launches
 ROLL_K, ROLL_DT = 6, 0.01
 FEATURE_MIN = 1e-3
 
@@ -102,8 +102,7 @@ class Recipe:
         self.fastf = a.get("FASTF", True)
         self.fun = a.get("FUN", False)
         self.uni = a.get("UNI", False)
-        self.pers = a.get("PERS", False)
-        self.big = self.pers or a.get("WAVES", 1) == 2
+        self.big = a.get("WAVES", 1) == 2
         self.B = B_BIG if self.big else B_SMALL
         lean = 3 if sub8 else a["LEAN"]
         self.roll = a.get("ROLL", False) or lean == 2
@@ -131,11 +130,11 @@ class Recipe:
         # (Honoured where the null space is one-dimensional only -- include/vfik.h, vfik_io.null_control: chains of up to 7 joints.)
         self.ctrl = self.ns and self.nj <= 7 and lean != 1 and not self.roll
         self.readback = self.ns and self.nj <= 7 and lean == 1 and not self.roll and not (self.flags & 2)
-        self.key = (self.pattern, self.plain, self.shared_tool, self.shared_wts, self.flags, self.fields, self.pers, self.B)
+        self.key = (self.pattern, self.plain, self.shared_tool, self.shared_wts, self.flags, self.fields, self.B)
 
     def __repr__(self):
-        return "Recipe(pattern=%s plain=%s tool=%s weights=%s flags=%d fields=%s pers=%s B=%d want=%s cap=%d limits=%s roll=%s)" % (
-            self.pattern, self.plain, self.shared_tool, self.shared_wts, self.flags, self.fields, self.pers, self.B, ",".join(self.want),
+        return "Recipe(pattern=%s plain=%s tool=%s weights=%s flags=%d fields=%s B=%d want=%s cap=%d limits=%s roll=%s)" % (
+            self.pattern, self.plain, self.shared_tool, self.shared_wts, self.flags, self.fields, self.B, ",".join(self.want),
             self.cap, self.limits, self.roll)
 
 
@@ -194,17 +193,7 @@ class Handle:
         self.q_hi = (np.tile(0.9 * hi, (B, 1)) - rng.uniform(0.0, 0.1, (B, n))).astype(dt).astype(np.float64)
         self.ctrl = rng.uniform(-1, 1, (B, 4)).astype(dt).astype(np.float64)
         self.q2 = np.clip(self.w["q"] + rng.normal(0, 0.05, (B, n)), 0.85 * lo, 0.85 * hi).astype(dt).astype(np.float64)
-        want_env = {"VFIK_PERSISTENT": "1" if r.pers else "0"}   # (read at vfik_create; tests/test_gpu_persistent.py does the same)
-        old = {k: os.environ.get(k) for k in want_env}
-        os.environ.update(want_env)
-        try:
-            self.eng = env.engine.Engine(self.chain, B, io_dtype=dt, max_slots=10, params=self.params)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    del os.environ[k]
-                else:
-                    os.environ[k] = v
+        self.eng = env.engine.Engine(self.chain, B, io_dtype=dt, max_slots=10, params=self.params)
         self.eng.set_fields(self.w["fields"], self.w["nfields"])
         if self.tool is not None:
             self.eng.set_tool(self.tool, per_arm=self.tool.ndim == 2)

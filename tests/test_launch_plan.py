@@ -3,7 +3,7 @@
 description takes, with its grid, block and LDS bytes.  Every route of the dispatch is in the table: each kernel family, the FUN /
 UNI / MIXO variants and the nullspace module's flag sets as compile-time constants, the DH-pattern bits and the cases that drop
 them, both I/O types, 6 / 7 / 10 / 14 joints, the eight-lanes kernel's caps on both sides, launches of more and fewer waves than
-the device has SIMDs, the persistent and the two-waves builds, the long chains' heavy object and the in-kernel / stepped rollout.
+the device has SIMDs, the two-waves build, the long chains' heavy object and the in-kernel / stepped rollout.
 
 A row: the launch (KArgs members; pointers 1 = given; defaults in the driver: 7 joints, float32 I/O, 4 096 arms, 256 threads a
 block, the straight-line field path, PLAIN, 1 024 SIMDs, the shipped eight-lanes caps), then what it takes."""
@@ -85,9 +85,7 @@ ROUTES = [
      'cycle_kernel_x<float, 7, false, false, false, true, 0, -1, false, false, 1, false, false, 0> grid=256 block=256 lds=117760'),
     ('nj=7 io=32 B=131072 dhp=1',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 1> grid=512 block=256 lds=117760'),
-    ('nj=7 io=32 B=131072 dhp=1 pers=1',
-     'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, true, false, 1, false, 0> grid=1024 block=64 lds=38400'),
-    ('nj=7 io=32 B=131072 dhp=1 pers=1 plain=2',
+    ('nj=7 io=32 B=131072 dhp=1 plain=2',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 3> grid=512 block=256 lds=117760'),
     ('nj=7 io=32 B=131072 dhp=1 waves2=1',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 2, false, 0> grid=512 block=256 lds=80896'),

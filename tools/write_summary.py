@@ -38,7 +38,7 @@ C3 / C3N 384 B x 65 536, C5 696 B x 65 536, C3F 600 B x 65 536, C5F 996 B x 65 5
 Kernel names: `cycle_kernel_s` = a lean variant entered through its ten scalar arguments (preloaded into SGPRs), `cycle_kernel_x` = any
 other variant (the same scalars in front of its argument block), `cycle_kernel_m` = the variants for differing decay orders; template
 parameters <io type, joints, nullspace module, PLAIN, rollout, straight-line field path, LEAN (1 lean, 3 publishing lean), compile-time
-flags, persistent, aux block, waves per SIMD, uniform repeller image, [order planes,] DH pattern>; of `cycle_sub8_kernel[_x]`: <io type,
+flags, reserved (false), aux block, waves per SIMD, uniform repeller image, [order planes,] DH pattern>; of `cycle_sub8_kernel[_x]`: <io type,
 joints, nullspace module, DH pattern>.
 
 **How the traces were taken.**  The traced commands replay their launches from a hipGraph (`--launch graph`, what the plain command's `auto`

@@ -70,13 +70,8 @@ struct vfik_handle {
     bool launched_lost = false;   // more distinct kernels than the record holds
     long epoch = 0;          // moves with every call that can change what a launch bakes in (vfik_launch_epoch)
     int n_simd = 1024;       // 4 per CU of this device
-    // Batches beyond one wave per SIMD may take the persistent launch (cycle_kernel PERS; VFIK_PERSISTENT=1).  Off by default:
-    // same-box A/B, lean C3 launches, rounds vs persistent: 131 072 arms 10.37 / 10.71 us, 262 144 20.47 / 20.56, 524 288
-    // 41.3 / 39.5 -- the wave is bound by its float64 instruction issue, not by the waits the prefetch removes
-    // (profiles/r03_batch_scaling.txt).
-    int pers = 0;
-    // What pays there instead: the lean kernels compiled for two waves per SIMD (cycle_kernel WAVES = 2; float I/O, chains of up to 7
-    // joints): 131 072 arms 10.4 -> 9.1 us, 524 288 38.4 -> 33.4 (same file).  VFIK_TWO_WAVES=0 keeps the rounds of one wave per SIMD.
+    // Batches beyond one wave per SIMD take the lean kernels compiled for two waves per SIMD (cycle_kernel WAVES = 2; float I/O, chains of up to 7
+    // joints): 131 072 arms 10.4 -> 9.1 us, 524 288 38.4 -> 33.4 (profiles/r03_batch_scaling.txt).  VFIK_TWO_WAVES=0 keeps the rounds of one wave per SIMD.
     int waves2 = 1;
     size_t esz = 4;
     hipStream_t stream = nullptr;
@@ -405,7 +400,6 @@ void fill_kargs(const vfik_handle* h, const vfik_io* io, vfik::KArgs& a) {
     a.funnel = h->d_funnel;
     a.slots_used_fast = h->slots_used_fast;
     a.has_funnel = h->any_funnel;
-    a.pers = h->pers;
     a.waves2 = h->waves2;
     a.uni = h->uni_ok && h->uni_allowed;
     a.uni_planes = 3 * ((std::max(1, h->max_slots) + 1) / 2);
@@ -520,7 +514,6 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
         if (b == 64 || b == 128 || b == 192 || b == 256) h->block = b;  // tuning knob; LDS per block = waves x 27-56 KB
     }
     if (const char* e = std::getenv("VFIK_SUB8_MAX_BATCH")) h->sub8_max_batch = h->sub8_max_batch_full = h->sub8_max_batch_ns = std::max(0, std::atoi(e));
-    if (const char* e = std::getenv("VFIK_PERSISTENT")) h->pers = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_TWO_WAVES")) h->waves2 = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_UNIFORM_IMAGE")) h->uni_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_MIXED_ORDERS")) h->mixed_allowed = std::atoi(e) != 0;
@@ -1173,7 +1166,7 @@ static void note_launch(vfik_handle* h, const vfik::CyclePlan& p, unsigned flags
     for (int i = 0; i < h->launched_n; ++i) {
         const vfik::CyclePlan& r = h->launched[i].p;
         if (h->launched[i].ns == ns && r.family == p.family && r.plain == p.plain && r.roll == p.roll && r.fastf == p.fastf && r.lean == p.lean && r.cf == p.cf &&
-            r.pers == p.pers && r.fun == p.fun && r.waves == p.waves && r.uni == p.uni && r.mixo == p.mixo && r.dhp == p.dhp && r.heavy == p.heavy)
+            r.fun == p.fun && r.waves == p.waves && r.uni == p.uni && r.mixo == p.mixo && r.dhp == p.dhp && r.heavy == p.heavy)
             return;
     }
     if (h->launched_n == vfik_handle::LAUNCHED_MAX) { h->launched_lost = true; return; }

@@ -210,7 +210,6 @@ struct KArgs {
     int uni;                     // 1: every decay repeller of the batch shares one safe distance and one force (KConst::rep_safe, dh[0].pad): lean launches read the uniform image
     int uni_planes;              // quad planes of the compact image = offset of the uniform image behind slots_fast
     int waves2;                  // 1: lean straight-line float launches of more than n_simd waves take the two-waves-per-SIMD build (VFIK_TWO_WAVES=0: never)
-    int pers;                    // 1: lean straight-line launches of more than n_simd waves take the persistent kernel (VFIK_PERSISTENT=0: never)
     // round 4: decay repellers whose INTEGER orders differ (README.old:75 documents order 20 beside the feeder's 5, object_feeder:302)
     const void* orders;          // order planes: 16 bytes per arm and plane = the decay orders of 16 slots of the compact image, one byte each
     int mixed;                   // 1: the batch's repellers do not share one order -- the straight-line path reads `orders` (MIXO kernel variants)
@@ -247,7 +246,6 @@ enum class CycleFamily {
     Refused,          // a rollout the kernels do not run in-kernel (rollout_in_kernel): the caller steps it (vfik_abi.cpp: launch_cycles)
     Sub8,             // eight lanes per arm (cycle_sub8_kernel): small batches of the outputs the per-arm processes publish
     Lean,             // q -> qdot_out on the straight-line field path (cycle_kernel_s, LEAN 1)
-    LeanPersistent,   // ... beyond one wave per SIMD: one wave per SIMD striding over the batch (PERS)
     LeanTwoWaves,     // ... beyond one wave per SIMD: two waves per SIMD (WAVES 2)
     PublishingLean,   // no per-arm option, the published rows at run time (cycle_kernel_x, LEAN 3)
     Mixo,             // decay orders that differ, lean or publishing-lean (cycle_kernel_m)
@@ -267,7 +265,7 @@ struct CyclePlan {
     bool plain, roll, fastf;
     int lean;        // 0 general, 1 lean, 2 a stepped rollout's cycle, 3 publishing lean
     int cf;          // the flag set as a compile-time constant, or -1
-    bool pers, fun;
+    bool fun;
     int waves;
     bool uni, mixo;
     int dhp;         // DH-pattern bits the variant is built with (bit 0 pattern, bit 1 shared tool, bit 2 shared IK weights)
@@ -314,10 +312,10 @@ inline bool sub8_served(const KArgs& a, bool ns) {
 }
 
 namespace plan_detail {
-struct Sizes { size_t bytes, lean, kin, tool, qstep; };
+struct Sizes { size_t bytes, lean, tool, qstep; };
 inline Sizes sizes(int io_bits, int nj) {
-    if (io_bits == 32) return {(size_t)Stage<float>::bytes(nj), (size_t)Stage<float>::lean_bytes(nj), (size_t)Stage<float>::kin_off(nj), (size_t)Stage<float>::tool_off(nj), (size_t)Stage<float>::QSTEP};
-    return {(size_t)Stage<double>::bytes(nj), (size_t)Stage<double>::lean_bytes(nj), (size_t)Stage<double>::kin_off(nj), (size_t)Stage<double>::tool_off(nj), (size_t)Stage<double>::QSTEP};
+    if (io_bits == 32) return {(size_t)Stage<float>::bytes(nj), (size_t)Stage<float>::lean_bytes(nj), (size_t)Stage<float>::tool_off(nj), (size_t)Stage<float>::QSTEP};
+    return {(size_t)Stage<double>::bytes(nj), (size_t)Stage<double>::lean_bytes(nj), (size_t)Stage<double>::tool_off(nj), (size_t)Stage<double>::QSTEP};
 }
 
 // The route of a plain (pl) or general launch.  `shared`: the PLAIN kernels with the batch's shared tool / IK weights in dhp's bits 1-2 --
@@ -350,14 +348,14 @@ inline bool route(const KArgs& a, int nj, int io_bits, bool ns, bool pl, int dhp
     // full size keeps it in rounds of one wave per SIMD (two waves per SIMD compete for the same HBM time; profiles/r02_batch_scaling.txt)
     const size_t lds_lean = (long)p.grid * (long)waves <= (long)a.n_simd ? waves * s.lean : lds_full;
     const size_t lds_fun = std::max(lds_lean, waves * (s.lean + 6 * s.qstep));   // + the aux block's six rows per wave
-    // the DH pattern a cycle_kernel variant is built with: the lean straight-line variants but the persistent one and
+    // the DH pattern a cycle_kernel variant is built with: the lean straight-line variants but
     // the two-waves one on the compact image (it spilled with the pattern); float64 I/O: the pattern alone, for the 7-joint chain
     auto use = [&](CycleFamily f, bool roll, int lean_v, size_t lds) {
         p.family = f;
         p.roll = roll;
         p.lean = lean_v;
         p.lds = lds;
-        const bool built = fastf && (roll ? lean_v == 1 : lean_v != 0) && !p.pers && !(p.waves == 2 && !p.uni);
+        const bool built = fastf && (roll ? lean_v == 1 : lean_v != 0) && !(p.waves == 2 && !p.uni);
         p.dhp = built ? (f32 ? dhp : (nj == 7 ? (dhp & 1) : 0)) : 0;
         return true;
     };
@@ -384,14 +382,6 @@ inline bool route(const KArgs& a, int nj, int io_bits, bool ns, bool pl, int dhp
         size_t lds = (long)p.grid <= (long)a.n_simd ? s.lean : s.bytes;
         if (fun) lds = std::max(lds, s.lean + 6 * s.qstep);
         return use(CycleFamily::Mixo, false, qdot_out_only(a, ns) ? 1 : 3, lds + 1024);
-    }
-    // batches beyond one wave per SIMD: the persistent launch, one wave per SIMD striding over the 64-arm chunks (float I/O, up to 7 joints)
-    if (!shared && f32 && nj <= 7 && lean && !fun && single_cycle(a) && a.pers && (long)((a.B + 63) / 64) > (long)a.n_simd) {
-        p.pers = true;
-        const size_t lds = s.lean + s.kin;   // two per-arm areas
-        p.grid = (unsigned)a.n_simd;
-        p.block = 64;
-        return use(CycleFamily::LeanPersistent, false, 1, lds);
     }
     if (lean && !a.q_out) {
         if (fun) return use(CycleFamily::Lean, false, 1, lds_fun);
@@ -470,14 +460,13 @@ inline std::string cycle_kernel_name(const CyclePlan& p, int nj, int io_bits, bo
             std::snprintf(s, sizeof s, "cycle_kernel_m<%s, %d, %s, %d, %s, %d>", t, nj, b(ns), p.lean, b(p.fun), p.dhp);
             return s;
         case CycleFamily::Lean:
-        case CycleFamily::LeanPersistent:
         case CycleFamily::LeanTwoWaves:
-            std::snprintf(s, sizeof s, "cycle_kernel_s<%s, %d, %s, true, false, true, 1, %d, %s, %s, %d, %s, %d>", t, nj, b(ns), p.cf, b(p.pers), b(p.fun), p.waves,
+            std::snprintf(s, sizeof s, "cycle_kernel_s<%s, %d, %s, true, false, true, 1, %d, false, %s, %d, %s, %d>", t, nj, b(ns), p.cf, b(p.fun), p.waves,
                           b(p.uni), p.dhp);
             return s;
         default:
-            std::snprintf(s, sizeof s, "cycle_kernel_x<%s, %d, %s, %s, %s, %s, %d, %d, %s, %s, %d, %s, false, %d>%s", t, nj, b(ns), b(p.plain), b(p.roll), b(p.fastf),
-                          p.lean, p.cf, b(p.pers), b(p.fun), p.waves, b(p.uni), p.dhp, p.heavy ? " [heavy]" : "");
+            std::snprintf(s, sizeof s, "cycle_kernel_x<%s, %d, %s, %s, %s, %s, %d, %d, false, %s, %d, %s, false, %d>%s", t, nj, b(ns), b(p.plain), b(p.roll), b(p.fastf),
+                          p.lean, p.cf, b(p.fun), p.waves, b(p.uni), p.dhp, p.heavy ? " [heavy]" : "");
             return s;
     }
 }

@@ -14,11 +14,11 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, persistent, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, check_kernel.
+// rollout, field path, LEAN, compile-time flags, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, check_kernel.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
-// variant from a patch file).  Every route switch is a run-time one (VFIK_BLOCK, VFIK_SUB8_MAX_BATCH, VFIK_PERSISTENT, VFIK_TWO_WAVES, ...).
+// variant from a patch file).  Every route switch is a run-time one (VFIK_BLOCK, VFIK_SUB8_MAX_BATCH, VFIK_TWO_WAVES, ...).
 //
 // Arithmetic is float64 whatever the io dtype (DESIGN.md "Precision").
 #include "vfik_kernel.h"
@@ -819,12 +819,6 @@ template <typename T> struct SlotLds {
 // CF = the feature flags as a compile-time constant, or -1: read from the launch.  The two flag sets the reference's
 // default process set produces with the nullspace module (vfclik:95-97: nullspace + mixer; C5 adds the joint-limit
 // task) get their own LEAN kernels, so that the branches of the other options are not in the code at all.
-// PERS = persistent launch for batches beyond one wave per SIMD (lean straight-line launches, float I/O, chains of up to 7
-// joints): the grid is one wave per SIMD, every wave strides over the 64-arm chunks of the batch, and while it computes
-// chunk k the requests of chunk k + 1 -- q, goal block, slot quads -- are in flight into a SECOND per-arm area of its LDS
-// region (they are issued between the joints of the kinematics, where the first chunk's slot requests go).  Launched in
-// rounds of one wave per SIMD instead, 131 072 arms cost 2.33 x the 65 536-arm launch: every round pays its own request
-// phase, q round trip and tail.
 // Lean single-cycle launches on the straight-line path take the 56-byte KLean instead of the 340-byte KArgs (vfik_kernel.h): the
 // handle's state is one arena whose layout follows from (io type, joints, Bpad).  (The diagnostic stamps build keeps KArgs.)
 #ifdef VFIK_STAMPS
@@ -864,10 +858,10 @@ template <typename T, int NJ> struct ArenaLayout {
 // vector instructions (C3 -5.3 % warm / -3.7 % cold, C3N -3.1 %, C3F -2.7 %: profiles/r04_ab_dhp.txt, before the swap lost its last
 // multiplications).  Built for the lean and the publishing-lean straight-line float variants (plan_cycle); every other variant, and every
 // chain that does not match a built pattern, runs the general DH form.
-template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF, bool PERS, bool FUN, int WAVES, bool UNI, bool MIXO, int DHP>
+template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF, bool FUN, int WAVES, bool UNI, bool MIXO, int DHP>
 __device__ __forceinline__ void
 cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::value, KLean, KArgs>::type& a_in) {
-    static_assert(DHP == 0 || (PLAIN && FASTF && (!ROLL || LEAN == 1) && !PERS && LEAN != 0 && (sizeof(T) == 4 || DHP == 1)), "DHP: the lean straight-line variants (single cycle, a stepped rollout's cycle, and the lean rollout); the option bits: float32 I/O");
+    static_assert(DHP == 0 || (PLAIN && FASTF && (!ROLL || LEAN == 1) && LEAN != 0 && (sizeof(T) == 4 || DHP == 1)), "DHP: the lean straight-line variants (single cycle, a stepped rollout's cycle, and the lean rollout); the option bits: float32 I/O");
     static_assert(!(DHP & 2) || LEAN != 2, "TOOLC: not in a stepped rollout's cycle");
     static_assert(!(DHP & 2) || !ROLL, "TOOLC: single-cycle variants only (a rollout with a tool is stepped)");
     // DHP bit 0: the chain's DH pattern (DhPattern<NJ, 1>); bit 1 (TOOLC): ONE tool for the whole batch, applied by the PLAIN kernel --
@@ -883,11 +877,10 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     constexpr bool WTSC = (DHP & 4) != 0;
     static_assert(!WTSC || (NJ <= 7 && !ROLL && LEAN != 2), "WTSC: single-cycle variants of chains of up to 7 joints");
     constexpr bool WEIGHTED = !PLAIN || WTSC;
-    static_assert(!MIXO || (FASTF && PLAIN && !ROLL && !PERS && !UNI && WAVES == 1 && (LEAN == 1 || LEAN == 3)), "MIXO: the lean single-cycle straight-line variants");
-    static_assert(!PERS || (LEAN == 1 && FASTF && PLAIN && !ROLL && sizeof(T) == 4 && NJ <= 7 && !FUN), "PERS: lean straight-line float launches only");
+    static_assert(!MIXO || (FASTF && PLAIN && !ROLL && !UNI && WAVES == 1 && (LEAN == 1 || LEAN == 3)), "MIXO: the lean single-cycle straight-line variants");
     static_assert(!FUN || (FASTF && PLAIN && !ROLL && (LEAN == 1 || LEAN == 3)), "FUN: the lean single-cycle straight-line variants");
-    static_assert(WAVES == 1 || (WAVES == 2 && LEAN == 1 && FASTF && PLAIN && !ROLL && !PERS && !FUN && sizeof(T) == 4 && NJ <= 7), "WAVES 2: lean straight-line float launches only");
-    static_assert(!UNI || (FASTF && PLAIN && !ROLL && !PERS && !FUN && (LEAN == 1 || LEAN == 3)), "UNI: the lean single-cycle straight-line variants");
+    static_assert(WAVES == 1 || (WAVES == 2 && LEAN == 1 && FASTF && PLAIN && !ROLL && !FUN && sizeof(T) == 4 && NJ <= 7), "WAVES 2: lean straight-line float launches only");
+    static_assert(!UNI || (FASTF && PLAIN && !ROLL && !FUN && (LEAN == 1 || LEAN == 3)), "UNI: the lean single-cycle straight-line variants");
     KArgs a;
     if constexpr (SmallArgs<LEAN, ROLL, FASTF, MIXO>::value) {
         a = KArgs{};
@@ -925,10 +918,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         if constexpr (LEAN == 1) a.status_or = 0;  // (a stepped rollout accumulates the status bits of its cycles)
         if constexpr (!ROLL && LEAN == 1) a.q_out = nullptr;  // (a rollout's q_out is its result)
     }
-    // PERS: one wave per block; chunk = 64 consecutive arms; lanes past the end of the batch compute arm B - 1 again and store nothing
-    const int nchunks = (a.B + 63) >> 6;
-    int chunk = PERS ? (int)blockIdx.x : 0;
-    int arm = PERS ? chunk * 64 + (int)threadIdx.x : (int)(blockIdx.x * a.block + threadIdx.x);
+    const int arm = (int)(blockIdx.x * a.block + threadIdx.x);
     const long Bs = a.B;
     constexpr unsigned DHP_SWAP = DhPattern<NJ, DHPAT>::SWAP, DHP_NONE = DhPattern<NJ, DHPAT>::NONE, DHP_D0 = DhPattern<NJ, DHPAT>::D0;
     constexpr bool TABSC = NJ <= 8;  // sin / cos through the LDS table (sincos_tab_n)
@@ -949,18 +939,17 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     constexpr int ORD_OFF = FUN_OFF + NFUN * Stage<T>::QSTEP;
     constexpr int REGION_BYTES = ((LEAN != 0 && FASTF) ? Stage<T>::lean_bytes(NJ) : Stage<T>::bytes(NJ)) + NFUN * Stage<T>::QSTEP + NORD * 1024;
     char* const region = lds_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * REGION_BYTES;
-    // per-arm inputs (goal block, first-chunk slot quads, q) of the chunk being computed: the head of the region, or
-    // (PERS, odd chunks of the wave) the second per-arm area behind the constants and the table
+    // per-arm inputs (goal block, first-chunk slot quads, q): the head of the region.  (A name of its own although it never moves: written
+    // as `region`, the FUN variants' scalar address arithmetic comes out in another order -- profiles/persistent_removed.txt)
     char* dreg = region;
-    constexpr int DAREA2 = Stage<T>::lean_bytes(NJ);      // offset of the second per-arm area; it is kin_off(NJ) bytes long
     const long Bp = a.Bpad;
     constexpr int QB = Stage<T>::QBYTES, Q16 = Stage<T>::Q16;
     constexpr int PRE = Stage<T>::PRE;
     const long planeB = Bp * QB;  // bytes of one quad plane
     constexpr int NQREQ = Stage<T>::q16(NJ) + Stage<T>::qrem(NJ) / 4;   // requests that bring one q vector
-    auto issue_q_piece = [&](int r, int armx, char* dr) {  // piece r of arm armx's q into the per-arm area dr
-        const char* qg = static_cast<const char*>(a.q) + (long)armx * NJ * sizeof(T);
-        char* qrow = dr + Stage<T>::Q_OFF;
+    auto issue_q_piece = [&](int r) {  // piece r of this arm's q
+        const char* qg = static_cast<const char*>(a.q) + (long)arm * NJ * sizeof(T);
+        char* qrow = dreg + Stage<T>::Q_OFF;
         constexpr int n16 = Stage<T>::q16(NJ);
         if (r < n16) __builtin_amdgcn_global_load_lds((GPtr)(qg + r * 16), (LPtr)(qrow + r * 1024), 16, 0, 0);
         else __builtin_amdgcn_global_load_lds((GPtr)(qg + n16 * 16 + (r - n16) * 4), (LPtr)(qrow + n16 * 1024 + (r - n16) * 256), 4, 0, 0);
@@ -985,7 +974,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // the batch's last row are not requested.
     // (the lean single-cycle variants at one wave per SIMD: elsewhere the few registers of the block form tipped variants that sit at their
     // register limit into scratch -- 12 to 130 B per lane in seven of them)
-    constexpr bool QBLK = !PERS && !ROLL && LEAN != 0 && WAVES == 1;
+    constexpr bool QBLK = !ROLL && LEAN != 0 && WAVES == 1;
     if constexpr (QBLK) {
         constexpr int BQ = NJ * (int)sizeof(T);              // bytes of one row
         constexpr int NBLK = (BQ + 15) / 16;                 // requests: 64 BQ bytes in pieces of 64 x 16
@@ -998,16 +987,10 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             if ((r * 64 + lane) * 16 < rows * BQ)
                 __builtin_amdgcn_global_load_lds((GPtr)(qb + r * 1024), (LPtr)(qrow + r * 1024), 16, 0, 0);
     }
-    if constexpr (!PERS) {
-        if (arm >= a.B) return;
-    }
+    if (arm >= a.B) return;
     // Fresh-q gate (vf:312-313, nullspace:162-163): an arm whose joint angles did not arrive this cycle stores
     // nothing.  Requested first, consumed at the stores: every counted wait below covers this oldest request.
     int act = 1;
-    if constexpr (PERS) {
-        act = arm < a.B;
-        arm = arm < a.B ? arm : a.B - 1;
-    }
     if (a.active) act = a.active[arm];
     if (a.tool_stride) {          // per-arm tools ([3][Bpad] quads); a shared tool sits in KConst
         const char* tg = static_cast<const char*>(a.tool);
@@ -1021,7 +1004,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     }
     if constexpr (!QBLK) {
 #pragma unroll
-        for (int r = 0; r < NQREQ; ++r) issue_q_piece(r, arm, dreg);
+        for (int r = 0; r < NQREQ; ++r) issue_q_piece(r);
     }
     // The goal and slot requests are issued later, between the joints of the kinematics: a load costs
     // the issuing wave ~50 cycles while the CU's four waves queue on the one address unit
@@ -1033,10 +1016,10 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     constexpr int QPC = UNI ? PRE : (FASTF ? 3 * PRE / 2 : 2 * PRE);       // slot quads per chunk
     const char* const goal0 = static_cast<const char*>(a.goal);
     const char* const slots0 = static_cast<const char*>(FASTF ? a.slots_fast : a.slots);
-    auto issue_goal_quad = [&](int k, int armx, char* dr) {
-        stage_quad<T>(goal0 + k * planeB, (unsigned)armx * (unsigned)QB, dr, Stage<T>::GOAL_OFF + k * Stage<T>::QSTEP);
+    auto issue_goal_quad = [&](int k) {
+        stage_quad<T>(goal0 + k * planeB, (unsigned)arm * (unsigned)QB, dreg, Stage<T>::GOAL_OFF + k * Stage<T>::QSTEP);
     };
-    auto issue_slot_quad_of = [&](int idx, int armx, char* dr) {  // idx in [0, QPC): quad idx of the first chunk of slots
+    auto issue_slot_quad = [&](int idx) {  // idx in [0, QPC): quad idx of the first chunk of slots
         // quads past the slots in use re-request plane 0 (cache hit) and are masked below, so the
         // number of outstanding requests is a compile-time constant for the counted waits
         // (Round 3 tried a wave-uniform fast path without the per-quad compare / select when every slot of the window is in use --
@@ -1044,30 +1027,19 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         // (UNI: plane 0 of the uniform image is an EMPTY slot for every arm -- radius -inf --, slot m sits in plane m + 1: a quad past the
         // slots in use is then harmless by itself and the chunk needs no mask)
         const bool in = UNI ? idx < npre : (FASTF ? 2 * (idx / 3) < npre : (idx >> 1) < npre);
-        stage_quad<T>(slots0 + (in ? (long)(UNI ? idx + 1 : idx) * planeB : 0), (unsigned)armx * (unsigned)QB, dr, Stage<T>::slot_off(idx, NJ));
+        stage_quad<T>(slots0 + (in ? (long)(UNI ? idx + 1 : idx) * planeB : 0), (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
     };
-    auto issue_slot_quad = [&](int idx) { issue_slot_quad_of(idx, arm, dreg); };
     constexpr int N_SLOT = QPC * Q16;                       // requests issued after the goal
-    // The wave has to sit out q's round trip (~500 cycles) anyway: the goal block and the first EARLY_Q
-    // slot quads are requested into that wait, the remaining slot quads between the joints.
+    // The wave has to sit out q's round trip (~500 cycles) anyway: the goal block is requested into that wait, the slot quads between
+    // the joints.
     // (long chains have two rows of constants and five q pieces in front already: nothing early there, C5 -1.3 %)
-    // PERS: the first chunk's requests all go out here; the slots between the joints are the NEXT chunk's requests.
     // Round 4: NO slot quad goes out early any more (until then six of them were requested into q's round trip).  With the inputs in HBM every
     // wave's ~20 requests of the launch's first half microsecond compete for the same bandwidth -- 16.5 MB in all, 2-3 us of HBM time -- and
     // what a wave needs FIRST (q: 1.8 MB over the batch, then the goal block) queued behind slot data it needs last: slot quads requested
     // between the joints instead, C3 cold 5.57 -> 5.21 us (-6.5 %), three early 5.44; warm +-0 (profiles/r04_ab_early_q.txt).
-    constexpr int EARLY_Q = PERS ? QPC : 0;
-    constexpr int SLOTQ_PER_JOINT = (QPC - EARLY_Q + NJ - 1) / NJ;  // slot quads requested after each joint
-    // PERS: request r of a chunk's NPF = q pieces, goal quads, slot quads, in that order (float I/O: one request a quad)
-    constexpr int NPF = PERS ? NQREQ + 4 + QPC : 0;
-    constexpr int PF_PER_JOINT = (NPF + NJ - 1) / NJ;
-    auto issue_prefetch = [&](int r, int armx, char* dr) {
-        if (r < NQREQ) issue_q_piece(r, armx, dr);
-        else if (r < NQREQ + 4) issue_goal_quad(r - NQREQ, armx, dr);
-        else issue_slot_quad_of(r - NQREQ - 4, armx, dr);
-    };
+    constexpr int SLOTQ_PER_JOINT = (QPC + NJ - 1) / NJ;  // slot quads requested after each joint
 #pragma unroll
-    for (int k = 0; k < 4; ++k) issue_goal_quad(k, arm, dreg);
+    for (int k = 0; k < 4; ++k) issue_goal_quad(k);
     if constexpr (FUN) {  // the funnel block, right behind the goal block: the goal's wait covers it
         const char* fg = static_cast<const char*>(a.funnel);
 #pragma unroll
@@ -1079,8 +1051,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         __builtin_amdgcn_global_load_lds((GPtr)og, (LPtr)(region + ORD_OFF), 16, 0, 2);
     };
     if constexpr (MIXO) issue_orders(0);  // (behind the goal / aux blocks: the goal's wait covers it)
-#pragma unroll
-    for (int idx = 0; idx < EARLY_Q; ++idx) issue_slot_quad(idx);
 
     // The members of the argument block the rest of the cycle needs, in one batch of scalar loads behind the requests (cycle_kernel_x:
     // left alone, the compiler fetches each where it is first used -- a round trip to the kernarg segment every time)
@@ -1093,9 +1063,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // ---------------- A3: forward kinematics (vf:316-318) -------------------------------------
     double q[NJ], sn[NJ], cs[NJ];
     const KConst<NJ>* const kl = reinterpret_cast<const KConst<NJ>*>(region + Stage<T>::kin_off(NJ));  // kinematics block only
-    bool has_next = false;    // PERS: this wave has another chunk of arms after the current one (wave-uniform)
-    int arm_next = 0;         // PERS: this lane's arm of that chunk (clamped to the batch)
-    char* dreg_next = region;
     auto read_q = [&]() {
         const char* qrow = dreg + Stage<T>::Q_OFF;
         if constexpr (QBLK) {   // the wave's rows as they lie in memory
@@ -1115,11 +1082,9 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             }
         }
     };
-    if constexpr (!PERS) {
-        VFIK_WAIT_VM((4 + NFUN + EARLY_Q) * Q16 + NORD);  // constants, table, tool and q have landed (the goal, funnel, order and early slot requests may still be out)
-        STAMP(2);
-        read_q();
-    }
+    VFIK_WAIT_VM((4 + NFUN) * Q16 + NORD);  // constants, table, tool and q have landed (the goal, funnel and order requests may still be out)
+    STAMP(2);
+    read_q();
     // nullspace sign memory (nullspace:91-92) lives in registers across the cycles of a launch
     int sig_r = 1;
     bool has_vec = false;  // lastvec holds a vector (false until the first cycle with a unique nullspace direction)
@@ -1165,21 +1130,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     };
     if constexpr (NULLSP && NJ <= 7 && ROLL) load_null_state();
     const int ncyc = ROLL ? a.n_cycles : 1;
-    for (;;) {  // PERS: the wave's chunks of arms; otherwise one pass
-    if constexpr (PERS) {
-        // Top of a chunk.  First chunk: constants, table and q have landed (goal and slots may still be out).  Later chunks:
-        // everything landed before the previous chunk's stores (the wait in front of them), and those few stores are
-        // younger than anything this wait looks at.
-        VFIK_WAIT_VM((4 + QPC) * Q16);
-        STAMP(2);
-        read_q();
-        status = 0;
-        const int nxt = chunk + (int)gridDim.x;
-        has_next = nxt < nchunks;
-        const int an = nxt * 64 + (int)threadIdx.x;
-        arm_next = an < a.B ? an : a.B - 1;
-        dreg_next = dreg == region ? region + DAREA2 : region;
-    }
     for (int cyc = 0; cyc < ncyc; ++cyc) {
     // The LDS addresses are made opaque once per cycle for long chains: otherwise the compiler hoists the
     // cycle-invariant reads (constants, goal, slots: ~200 doubles) out of the cycle loop and spills.
@@ -1308,14 +1258,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         }
 #pragma unroll
         for (int k = 0; k < SLOTQ_PER_JOINT; ++k)
-            if (first && EARLY_Q + i * SLOTQ_PER_JOINT + k < QPC) issue_slot_quad(EARLY_Q + i * SLOTQ_PER_JOINT + k);
-        if constexpr (PERS) {  // the next chunk's requests, into the other per-arm area, a few after every joint
-            if (has_next) {
-#pragma unroll
-                for (int k = 0; k < PF_PER_JOINT; ++k)
-                    if (i * PF_PER_JOINT + k < NPF) issue_prefetch(i * PF_PER_JOINT + k, arm_next, dreg_next);
-            }
-        }
+            if (first && i * SLOTQ_PER_JOINT + k < QPC) issue_slot_quad(i * SLOTQ_PER_JOINT + k);
     }
     if (!PLAIN) {   // trailing z-screw of the last fixed transform
         const double tc = klc->tail_c, ts = klc->tail_s, te = klc->tail_e;
@@ -1562,8 +1505,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     double speed;  // this arm's speedScale (vf:134-137,197-207), 4th component of the goal block's last quad
     // (Round 3 tried pinning the factorisation in front of this wait by tying the wait to its results: neutral in the cold
     // state, noisy-to-slower in the warm one; the compiler's own placement stays.)
-    if (PERS && has_next) VFIK_WAIT_VM(N_SLOT + NPF);
-    else
     VFIK_WAIT_VM(N_SLOT);  // goal block has landed
     {
         double gq[16];
@@ -1834,10 +1775,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                 }
                 }
             };
-            // the first chunk (requested during the kinematics, or -- PERS -- at the start of the launch / under the previous
-            // chunk of arms) has landed; PERS: the requests of the wave's NEXT chunk of arms are younger and stay out
-            if (PERS && has_next) VFIK_WAIT_VM(NPF);
-            else VFIK_WAIT_VM(0);
+            VFIK_WAIT_VM(0);  // the first chunk (requested during the kinematics) has landed
             chunk(0);
             // further chunks: kept out of line of the first so that the common (<= PRE slots) case is
             // straight-line code with no loop-carried register shuffling
@@ -2079,11 +2017,6 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
 
     PIN_ARR(qv, NJ);
     STAMP(6);
-    if constexpr (PERS) {
-        // The next chunk's inputs have landed (requested a field evaluation and an IK ago): from here on the only
-        // requests this wave leaves outstanding are its own stores, and the waits at the top of the next chunk pass.
-        if (has_next) VFIK_WAIT_VM(0);
-    }
     if constexpr (NJ >= 10 && !ROLL) {
         // Long chains: the joint angles are read from the wave's LDS rows AGAIN for the nullspace module, the mixer and the
         // outputs, instead of being held in 2 n registers through the field and the IK (the 14-joint kernels spill otherwise).
@@ -2379,30 +2312,21 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         if (a.status) a.status[arm] = a.status_or ? (a.status[arm] | status) : status;
     }
     STAMP(7);
-    if constexpr (!PERS) {
-        break;
-    } else {
-        if (!has_next) break;
-        chunk += (int)gridDim.x;
-        const int an = chunk * 64 + (int)threadIdx.x;
-        act = an < a.B;
-        arm = arm_next;
-        dreg = dreg_next;
-    }
-    }  // chunks of this wave (PERS)
 }
 
 // The kernel proper: the body above behind scalar kernel arguments -- those the command processor can preload into the wave's SGPRs
 // at dispatch (-amdgpu-kernarg-preload-count, Makefile; an argument block passed by value is never preloaded), which takes the
 // scalar-load round trip of the kernarg out of every wave's prologue.  The KLean variants: KLean's ten members alone ...
-template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool PERS = false, bool FUN = false, int WAVES = 1, bool UNI = false, int DHP = 0>
+// (RESERVED: the slot of the persistent launch, removed; it keeps the later parameters' positions, by which kernel names are read, and is false)
+template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool RESERVED = false, bool FUN = false, int WAVES = 1, bool UNI = false, int DHP = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 cycle_kernel_s(const void* base, const void* q, void* qdot_out, int* status, int B, int Bpad, int slots_used, int fast_order, unsigned flags, int block) {
     static_assert(SmallArgs<LEAN, ROLL, FASTF>::value, "scalar arguments: the KLean variants");
+    static_assert(!RESERVED, "the reserved slot is false");
     KLean k;
     k.base = base; k.q = q; k.qdot_out = qdot_out; k.status = status;
     k.B = B; k.Bpad = Bpad; k.slots_used = slots_used; k.fast_order = fast_order; k.flags = flags; k.block = block;
-    cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, PERS, FUN, WAVES, UNI, false, DHP>(k);
+    cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, FUN, WAVES, UNI, false, DHP>(k);
 }
 // The members of the handle's state arena and the launch's first arguments, from scalars (the arena's layout: vfik_kernel.h)
 template <typename T, int NJ>
@@ -2419,16 +2343,18 @@ __device__ __forceinline__ void args_from_scalars(KArgs& a, const void* base, co
 }
 // Every other variant: the same ten scalars IN FRONT of the argument block -- what the prologue needs to issue its first requests (the
 // arena's members, q, the sizes) arrives preloaded; the rest of the block is read by scalar loads that run under those requests.
-template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool PERS = false, bool FUN = false, int WAVES = 1, bool UNI = false, bool MIXO = false, int DHP = 0>
+// (RESERVED: the slot of the persistent launch, removed; it keeps the later parameters' positions, by which kernel names are read, and is false)
+template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF = -1, bool RESERVED = false, bool FUN = false, int WAVES = 1, bool UNI = false, bool MIXO = false, int DHP = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 cycle_kernel_x(const void* base, const void* q, void* qdot_out, const int* active, int B, int Bpad, int slots_used, int fast_order, unsigned flags, int block,
                const KArgs a_in) {
     static_assert(!SmallArgs<LEAN, ROLL, FASTF, MIXO>::value, "the KLean variants take cycle_kernel_s");
+    static_assert(!RESERVED, "the reserved slot is false");
     KArgs a = a_in;
     args_from_scalars<T, NJ>(a, base, q, qdot_out, a_in.status, B, Bpad, slots_used, flags);
     a.active = active;   // (the fresh-q gate is the first request of the prologue; status is stored last and stays in the block)
     a.fast_order = fast_order; a.block = block;
-    cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, PERS, FUN, WAVES, UNI, MIXO, DHP>(a);
+    cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, FUN, WAVES, UNI, MIXO, DHP>(a);
 }
 
 // The MIXO variants: the order planes' address is needed in the REQUEST phase, so it travels among the preloaded scalars too (read from
@@ -2443,7 +2369,7 @@ cycle_kernel_m(const void* base, const void* q, void* qdot_out, const int* activ
     a.active = active;
     a.orders = orders;
     a.fast_order = 0; a.block = 64;
-    cycle_body<T, NJ, NULLSP, true, false, true, LEAN, -1, false, FUN, 1, false, true, DHP>(a);
+    cycle_body<T, NJ, NULLSP, true, false, true, LEAN, -1, FUN, 1, false, true, DHP>(a);
 }
 
 // CommandMixer.read's weighted sum alone (command_mixer.py:78-82): out = sum_k cmd[k] * w[k], left to
@@ -3408,9 +3334,10 @@ template <typename T, int NJ, bool NS, int CF, bool FUN, bool UNI, int D>
 constexpr bool lean_built() { return dhp_lean<T, NJ>(D) && !(FUN && UNI) && (CF == -1 || (NS && NJ <= 7 && !FUN && D <= 1)); }
 
 // cycle_kernel_x: the prologue's arguments as preloaded scalars in front of the argument block
-template <typename T, int NJ, bool NS, bool PL, bool ROLL, bool FASTF, int LEAN, int CF, bool PERS, bool FUN, int WAVES, bool UNI, int D>
+template <typename T, int NJ, bool NS, bool PL, bool ROLL, bool FASTF, int LEAN, int CF, bool RESERVED, bool FUN, int WAVES, bool UNI, int D>
 void launch_x(const KArgs& a, const CyclePlan& p, hipStream_t stream) {
-    hipLaunchKernelGGL((cycle_kernel_x<T, NJ, NS, PL, ROLL, FASTF, LEAN, CF, PERS, FUN, WAVES, UNI, false, D>), dim3(p.grid), dim3(p.block), p.lds, stream, a.arena, a.q,
+    static_assert(!RESERVED, "the reserved slot (cycle_kernel_x) is false");
+    hipLaunchKernelGGL((cycle_kernel_x<T, NJ, NS, PL, ROLL, FASTF, LEAN, CF, false, FUN, WAVES, UNI, false, D>), dim3(p.grid), dim3(p.block), p.lds, stream, a.arena, a.q,
                        a.qdot_out, a.active, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block, a);
 }
 
@@ -3433,12 +3360,12 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
     const dim3 grid(p.grid), blk(p.block);
     bool launched = false;
     // cycle_kernel_s: the lean single-cycle straight-line variants (the diagnostic stamps build gives them the whole block: cycle_kernel_x)
-    auto lean_s = [&](auto CF, auto PERS, auto FUN, auto WAVES, auto UNI, auto D) {
+    auto lean_s = [&](auto CF, auto FUN, auto WAVES, auto UNI, auto D) {
         if constexpr (SmallArgs<1, false, true>::value)
-            hipLaunchKernelGGL((cycle_kernel_s<T, NJ, NS, true, false, true, 1, VFIK_V(CF), VFIK_V(PERS), VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>), grid, blk, p.lds,
+            hipLaunchKernelGGL((cycle_kernel_s<T, NJ, NS, true, false, true, 1, VFIK_V(CF), false, VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>), grid, blk, p.lds,
                                stream, a.arena, a.q, a.qdot_out, a.status, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block);
         else
-            launch_x<T, NJ, NS, true, false, true, 1, VFIK_V(CF), VFIK_V(PERS), VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
+            launch_x<T, NJ, NS, true, false, true, 1, VFIK_V(CF), false, VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
         launched = true;
     };
     switch (p.family) {
@@ -3463,7 +3390,7 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
         as_dhp(p.dhp, [&](auto D) { as_cf(p.cf, [&](auto CF) { as_bool(p.fun, [&](auto FUN) { as_bool(p.uni, [&](auto UNI) {
             if constexpr (lean_built<T, NJ, NS, VFIK_V(CF), VFIK_V(FUN), VFIK_V(UNI), VFIK_V(D)>()) {
                 if (p.lean == 1) {
-                    lean_s(CF, bool_c<false>(), FUN, int_c<1>(), UNI, D);
+                    lean_s(CF, FUN, int_c<1>(), UNI, D);
                 } else {
                     launch_x<T, NJ, NS, true, false, true, 3, VFIK_V(CF), false, VFIK_V(FUN), 1, VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
                     launched = true;
@@ -3471,14 +3398,11 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
             }
         }); }); }); });
         break;
-    case CycleFamily::LeanPersistent:
-        if constexpr (sizeof(T) == 4 && NJ <= 7) lean_s(int_c<-1>(), bool_c<true>(), bool_c<false>(), int_c<1>(), bool_c<false>(), int_c<0>());
-        break;
     case CycleFamily::LeanTwoWaves:   // (with the nullspace module on the uniform image only; on the compact image without the pattern)
         if constexpr (sizeof(T) == 4 && NJ <= 7) {
             as_dhp(p.dhp, [&](auto D) { as_cf(p.cf, [&](auto CF) { as_bool(p.uni, [&](auto UNI) {
                 if constexpr (VFIK_V(D) <= 1 && (VFIK_V(UNI) ? (VFIK_V(CF) == -1 || NS) : (!NS && VFIK_V(D) == 0 && VFIK_V(CF) == -1)))
-                    lean_s(CF, bool_c<false>(), bool_c<false>(), int_c<2>(), UNI, D);
+                    lean_s(CF, bool_c<false>(), int_c<2>(), UNI, D);
             }); }); });
         }
         break;
