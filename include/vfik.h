@@ -461,6 +461,62 @@ size_t vfik_follow_js_opts_size(void);
 int vfik_follow_js(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o);
 int vfik_follow_js_host(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, int poll_checks, int* checks_run);
 
+/* Motion scripts: frames and postures in ONE list per arm.  A pick-and-place script of the reference starts and ends with set_ref_js (home
+ * posture, pre-grasp posture), sends a list of gotoFrame calls between them, and around each change of kind switches the bridge's
+ * controller: HandleBridge.joint_controller() sends [0, 0, 1, 0] to /bridge/weight, cartesian_controller() [1, 1, 0, 0] (handlers.py:189-211,
+ * 481-497).  vfik_script is vfik_follow's state machine, step for step, over a list whose items are of either kind:
+ *   kind[b][w]   (vfik_types.h) VFIK_STEP_FRAME: way16[b][w] is a goal frame, vfik_follow's rule (both compares strict) with (pos_prec, rot_prec) or the
+ *                via pair; VFIK_STEP_POSTURE: wayq[b][w] is a posture, vfik_follow_js's rule as written (both edges non-strict, in double on
+ *                the io-typed values, against the posture as the caller sent it) with prec[n] or via_prec[n].  Any other value ends the arm's
+ *                script: L_b = the number of leading steps of kind 1 or 2, a zeroed array is "no script", and an arm with L_b == 0 is kept
+ *                out like one gated off.  way16 is read only at frame steps, wayq only at posture steps; no NaN convention applies.
+ *   send         a frame goes into the arm's goal block (vfik_follow's three quad stores, only where the block's `present` flag is set -- an
+ *                arm without a goal block never passes a frame step); a posture goes into the arm's row of the handle's reference row,
+ *                which every block reads as io->q_ref; and the mixer weights of channels 0..3 of the step's kind -- mix_frame or mix_posture
+ *                -- go into the arm's row of two quad planes of the handle's own, which every block reads as the per-arm mixer weights.
+ *                Until an arm's first posture its reference row starts with NaN: no controller, channel 2 stays the external command
+ *                (io->q_ref).  Over the frame steps behind a posture the row keeps that posture.
+ *   before block 0   reached = -1, next = 0, the gate, step 0 sent for every arm that takes part; weights 4, 5 and max_vel of every arm
+ *                from its vfik_set_mixer_weights / vfik_set_max_vel row where the handle has one, else the batch-wide vfik_params values.
+ *   after block k    the rule of the kind of step next[b] on every arm that ran; on success reached[b][next] = (k + 1) * stride - 1,
+ *                next += 1 and the following step is sent.  At most ONE step per check.  The via pairs hold at every step but the arm's last.
+ *   hold, io->active, pending[k] (arms that take part and have next < L_b), the gate of the next block, q_out, q_traj, way_traj: vfik_follow's.
+ *   dist_traj    the block's goal_dist row of every arm that ran, measured against the goal block as it stands: at a posture step the last
+ *                frame sent.  diff[b] = (T)(posture - q), written only by checks made at posture steps: at a frame step the arm keeps its row.
+ *   afterwards   nothing of the caller's mixer state has moved: the vfik_set_mixer_weights / vfik_set_max_vel rows, vfik_params and
+ *                vfik_launch_epoch stay, and a later call reads them as before.  The goal block is left at the last frame sent.  The cycle
+ *                kernels are those a vfik_rollout with io->q_ref on a handle with per-arm mixer weights launches.
+ * The handle's planes are allocated at the first call with its other goto buffers: never under capture (VFIK_E_STATE).
+ * VFIK_E_ARG, nothing enqueued: what vfik_follow refuses, kind / way16 / wayq / reached / next NULL, way16 not 16-byte aligned, wayq not
+ * aligned to its element type, a mixer weight that is not finite, a precision negative or NaN, prec NULL, io->q_ref GIVEN (the handle
+ * supplies it).  VFIK_E_STATE: the handle's params lack VFIK_F_MIXER -- a script switches controllers through the mixer. */
+typedef struct vfik_script_opts {
+    int32_t n_cycles, stride;         /* as vfik_goto_opts */
+    double  dt;
+    int32_t clamp_to_limits, hold;    /* hold: an arm that reached its LAST step takes no further cycle */
+    double  pos_prec, rot_prec;       /* frame steps: metres, radians, at an arm's last step */
+    double  via_pos_prec, via_rot_prec; /* ... and at every step before it */
+    const double* prec;               /* HOST [n]: posture steps, at an arm's last step */
+    const double* via_prec;           /* HOST [n]: ... and at every step before it; NULL = prec */
+    double  mix_frame[4];             /* mixer weights of channels 0..3 under way to a frame: the reference sends [1, 1, 0, 0] */
+    double  mix_posture[4];           /* ... and under way to a posture: [0, 0, 1, 0] */
+    int32_t n_way;                    /* W >= 1 */
+    const int32_t* kind;              /* in  [B][W] VFIK_STEP_FRAME, VFIK_STEP_POSTURE; any other value ends the arm's script */
+    const void* way16;                /* in  [B][W][16], io dtype, 16-byte aligned: read only at frame steps */
+    const void* wayq;                 /* in  [B][W][n], io dtype, element-aligned: read only at posture steps */
+    int32_t* reached;                 /* out [B][W], required */
+    int32_t* next;                    /* out [B], required */
+    int32_t* pending;                 /* out [n_checks], may be NULL */
+    void*   q_out; void* q_traj; void* dist_traj;   /* as vfik_follow_opts */
+    void*   diff;                     /* out [B][n], may be NULL */
+    int32_t* way_traj;                /* out [n_checks][B] the step the arm's check k was made against; may be NULL */
+} vfik_script_opts;
+/* sizeof(vfik_script_opts) as this library was built (vfik_struct_sizes keeps its four entries) */
+size_t vfik_script_opts_size(void);
+int vfik_script(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o);
+/* The same with HOST pointers (io and o alike), poll_checks and *checks_run as vfik_follow_host. */
+int vfik_script_host(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o, int poll_checks, int* checks_run);
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

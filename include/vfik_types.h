@@ -70,6 +70,10 @@ enum {
     VFIK_F_LIMITER = 1u << 3    /* bridge velocity limiter on the mixed command (bridge:188-195) */
 };
 
+/* the kinds of a motion script's steps (vfik.h: vfik_script_opts.kind); any other value ends an arm's script */
+#define VFIK_STEP_FRAME 1    /* a goal frame: gotoFrame, handlers.py:346-387 */
+#define VFIK_STEP_POSTURE 2  /* a posture: set_ref_js, handlers.py:544-576 */
+
 typedef struct vfik_params {
     double speed_scale;     /* vf speedScale, runtime range [0, 0.41] via /max_vel (vf:134,197-207) */
     double lambda;          /* DLS damping of getIKV (vf:461); build-defined default 0.1 */

@@ -79,6 +79,21 @@ class FollowJsOpts(C.Structure):
                 ("way_traj", C.c_void_p)]
 
 
+STEP_FRAME, STEP_POSTURE = 1, 2  # include/vfik_types.h: VFIK_STEP_FRAME, VFIK_STEP_POSTURE
+#: what HandleBridge.cartesian_controller() and joint_controller() send to /bridge/weight (handlers.py:189-211)
+MIX_FRAME, MIX_POSTURE = (1.0, 1.0, 0.0, 0.0), (0.0, 0.0, 1.0, 0.0)
+
+
+class ScriptOpts(C.Structure):
+    """``struct vfik_script_opts`` (include/vfik.h: vfik_script)."""
+    _fields_ = [("n_cycles", C.c_int32), ("stride", C.c_int32), ("dt", C.c_double), ("clamp_to_limits", C.c_int32), ("hold", C.c_int32),
+                ("pos_prec", C.c_double), ("rot_prec", C.c_double), ("via_pos_prec", C.c_double), ("via_rot_prec", C.c_double),
+                ("prec", C.c_void_p), ("via_prec", C.c_void_p), ("mix_frame", C.c_double * 4), ("mix_posture", C.c_double * 4),
+                ("n_way", C.c_int32), ("kind", C.c_void_p), ("way16", C.c_void_p), ("wayq", C.c_void_p), ("reached", C.c_void_p),
+                ("next", C.c_void_p), ("pending", C.c_void_p), ("q_out", C.c_void_p), ("q_traj", C.c_void_p), ("dist_traj", C.c_void_p),
+                ("diff", C.c_void_p), ("way_traj", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

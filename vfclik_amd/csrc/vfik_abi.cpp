@@ -116,7 +116,8 @@ struct vfik_handle {
     void* d_gotoq[2] = {nullptr, nullptr};
     DevBuf goto_stage;
     int* d_follow_len = nullptr;   // vfik_follow (which runs on vfik_goto's buffers): every arm's path length
-    void* d_js_ref = nullptr;      // vfik_follow_js: the reference row [B][n] its blocks read as io->q_ref (nobody else reads it)
+    void* d_js_ref = nullptr;      // vfik_follow_js, vfik_script: the reference row [B][n] their blocks read as io->q_ref (nobody else reads it)
+    void* d_script_mixw = nullptr; // vfik_script: the 2 quad planes its blocks read as the per-arm mixer weights (d_mixw_arm's layout; nobody else reads them)
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -598,7 +599,7 @@ void vfik_destroy(vfik_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->goto_stage.p, h->d_follow_len, h->d_js_ref};
+                    h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -1176,7 +1177,9 @@ static void note_launch(vfik_handle* h, const vfik::CyclePlan& p, unsigned flags
 }
 
 // status_or: the launch ORs its status bits into what io->status holds (block 2.. of a goto), as cycle 2.. of a stepped rollout does
-static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp, void* q_out, hipStream_t stream, int status_or = 0) {
+// mixw: per-arm mixer planes that stand in for the handle's (a script's own, vfik_script), or NULL
+static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp, void* q_out, hipStream_t stream, int status_or = 0,
+                         const void* mixw = nullptr) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (!io || !io->q) return fail(VFIK_E_ARG, "a control cycle needs io->q");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
@@ -1185,6 +1188,7 @@ static int launch_cycles(vfik_handle* h, const vfik_io* io, int n_cycles, double
     HIP_TRY(hipSetDevice(h->device));
     vfik::KArgs a;
     fill_kargs(h, io, a);
+    if (mixw) a.mixw = mixw;
     if (reinterpret_cast<uintptr_t>(io->q) % 16) {
         // The kernels fetch q in 16-byte pieces up to its length rounded up to 16 bytes (vfik_kernel.hip, QBLK): from a q that is not 16-byte
         // aligned the last piece could reach into the next page.  Such a q is staged through an aligned buffer of the handle.
@@ -1387,6 +1391,7 @@ size_t vfik_goto_opts_size(void) { return sizeof(vfik_goto_opts); }
 size_t vfik_follow_opts_size(void) { return sizeof(vfik_follow_opts); }
 size_t vfik_goto_js_opts_size(void) { return sizeof(vfik_goto_js_opts); }
 size_t vfik_follow_js_opts_size(void) { return sizeof(vfik_follow_js_opts); }
+size_t vfik_script_opts_size(void) { return sizeof(vfik_script_opts); }
 
 namespace {
 using vfik::TimedMove;
@@ -1487,6 +1492,38 @@ int follow_js_check(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts
     return js_prec(h, o->via_prec ? o->via_prec : o->prec, "vfik_follow_js", "via_prec", m.via_prec);
 }
 
+// a motion script: a waypoint list's move (its blocks, distance row and traces) with the joint rule's members beside it
+int script_check(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o, TimedMove& m) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!o || !o->kind || !o->way16 || !o->wayq || !o->reached || !o->next)
+        return fail(VFIK_E_ARG, "vfik_script: the options, their kind[B][W], way16[B][W][16], wayq[B][W][n], reached[B][W] and next[B] are required");
+    if (o->n_way < 1) return fail(VFIK_E_ARG, "n_way %d: a script has at least one step", o->n_way);
+    if (reinterpret_cast<uintptr_t>(o->way16) % 16) return fail(VFIK_E_ARG, "way16 must be 16-byte aligned: the kernel loads its rows in 16-byte pieces");
+    if (reinterpret_cast<uintptr_t>(o->wayq) % h->esz) return fail(VFIK_E_ARG, "wayq must be aligned to its element type");
+    if (reinterpret_cast<uintptr_t>(o->kind) % sizeof(int32_t)) return fail(VFIK_E_ARG, "kind must be aligned to int32");
+    if (!(o->via_pos_prec >= 0.0) || !(o->via_rot_prec >= 0.0))
+        return fail(VFIK_E_ARG, "via precision (%g m, %g rad) must not be negative or NaN", o->via_pos_prec, o->via_rot_prec);
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(o->mix_frame[k]) || !std::isfinite(o->mix_posture[k]))
+            return fail(VFIK_E_ARG, "mix_frame[%d] = %g, mix_posture[%d] = %g: a mixer weight must be finite", k, o->mix_frame[k], k, o->mix_posture[k]);
+    m = timed_of(io, o, false, true);
+    m.script = true;
+    m.n_way = o->n_way;
+    m.prec[0] = o->pos_prec; m.prec[1] = o->rot_prec; m.via_prec[0] = o->via_pos_prec; m.via_prec[1] = o->via_rot_prec;
+    for (int k = 0; k < 4; ++k) { m.mix[0][k] = o->mix_frame[k]; m.mix[1][k] = o->mix_posture[k]; }
+    m.x[vfik::X_KIND] = const_cast<int32_t*>(o->kind);
+    m.x[vfik::X_WAY16] = const_cast<void*>(o->way16); m.x[vfik::X_WAYQ] = const_cast<void*>(o->wayq);
+    m.x[vfik::X_REACHED] = o->reached; m.x[vfik::X_NEXT] = o->next;
+    m.x[vfik::X_DIST_TRAJ] = o->dist_traj; m.x[vfik::X_WAY_TRAJ] = o->way_traj; m.x[vfik::X_DIFF] = o->diff;
+    const int rc = timed_check(h, m);
+    if (rc != VFIK_OK) return rc;
+    if (io->q_ref) return fail(VFIK_E_ARG, "vfik_script supplies io->q_ref itself (the handle's reference row): leave it NULL");
+    if (js_prec(h, o->prec, "vfik_script", "prec", m.js_prec) != VFIK_OK) return VFIK_E_ARG;
+    if (js_prec(h, o->via_prec ? o->via_prec : o->prec, "vfik_script", "via_prec", m.js_via_prec) != VFIK_OK) return VFIK_E_ARG;
+    if (!(h->params.flags & VFIK_F_MIXER)) return fail(VFIK_E_STATE, "vfik_script switches controllers through the mixer: the handle's params lack VFIK_F_MIXER");
+    return VFIK_OK;
+}
+
 vfik::TimedDims timed_dims(const vfik_handle* h, const TimedMove& m) { return {(size_t)h->B, (size_t)h->n, h->esz, (size_t)m.n_way, (size_t)m.n_checks}; }
 
 // the handle's buffers this move needs (first call: never under stream capture) and pending[] zeroed
@@ -1499,12 +1536,14 @@ int timed_reserve(vfik_handle* h, TimedMove& m) {
     // a block reads io->q or a row of q_traj: one that is not 16-byte aligned goes through launch_cycles' staging buffer
     const bool odd_q = reinterpret_cast<uintptr_t>(io->q) % 16 ||
                        (m.x[vfik::X_Q_TRAJ] && m.n_checks > 1 && (reinterpret_cast<uintptr_t>(m.x[vfik::X_Q_TRAJ]) % 16 || qrow % 16));
-    const bool need_ref = m.joint && m.list && !h->d_js_ref;   // the row a posture list's blocks read as io->q_ref
-    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (m.list && !h->d_follow_len) || need_ref) {
+    const bool need_ref = ((m.joint && m.list) || m.script) && !h->d_js_ref;   // the row a posture list's or a script's blocks read as io->q_ref
+    const bool need_mixw = m.script && !h->d_script_mixw;                      // the planes a script's blocks read as the per-arm mixer weights
+    if (!h->d_goto_gate || need_pending || need_dist || need_q || (odd_q && !h->d_qalign) || (m.list && !h->d_follow_len) || need_ref || need_mixw) {
         if (refuse_capture(h->stream, "vfik_goto / vfik_follow: the handle's device buffers (gate, pending, distance row, q rows) are allocated at the first request -- make one such call before capturing the stream"))
             return VFIK_E_STATE;
         if (m.list && !h->d_follow_len && dev_alloc(h, (void**)&h->d_follow_len, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
         if (need_ref && dev_alloc(h, &h->d_js_ref, (qrow + 15) / 16 * 16, false)) return VFIK_E_HIP;
+        if (need_mixw && dev_alloc(h, &h->d_script_mixw, 2 * (size_t)h->Bpad * 4 * h->esz, true)) return VFIK_E_HIP;
         if (!h->d_goto_gate && dev_alloc(h, (void**)&h->d_goto_gate, (size_t)h->B * sizeof(int), false)) return VFIK_E_HIP;
         // (synchronised: an earlier goto may still count into the smaller array)
         if (need_pending && reserve(h, h->goto_pending, pend, true, true)) return VFIK_E_HIP;
@@ -1541,6 +1580,20 @@ int timed_launch_check(vfik_handle* h, const TimedMove& m, int k, const vfik::Bl
     g.diff = m.x[vfik::X_DIFF];
     std::memcpy(g.prec, m.prec, sizeof g.prec);   // (all of both: the Cartesian pair sits in [0], [1] whatever n is)
     std::memcpy(g.via_prec, m.via_prec, sizeof g.via_prec);
+    if (m.script) {
+        vfik::ScriptArgs s{};
+        s.c = g;
+        s.kind = static_cast<const int*>(m.x[vfik::X_KIND]);
+        s.wayq = m.x[vfik::X_WAYQ];
+        s.mixw = h->d_script_mixw;
+        s.bridge = h->d_mixw_arm;
+        s.bridge_u[0] = h->params.mix_w[4]; s.bridge_u[1] = h->params.mix_w[5]; s.bridge_u[2] = h->params.max_vel;
+        std::memcpy(s.mix, m.mix, sizeof s.mix);
+        std::memcpy(s.js_prec, m.js_prec, sizeof s.js_prec);
+        std::memcpy(s.js_via_prec, m.js_via_prec, sizeof s.js_via_prec);
+        const hipError_t es = vfik::launch_script(h->io_dtype, s, h->stream);
+        return es != hipSuccess ? fail(VFIK_E_HIP, "script launch: %s", hipGetErrorString(es)) : (int)VFIK_OK;
+    }
     hipError_t e = vfik::launch_check(h->io_dtype, m.joint, m.list, g, h->stream);
     if (e != hipSuccess) {
         static const char* const name[2][2] = {{"arrive", "follow"}, {"arrive_js", "follow_js"}};
@@ -1560,9 +1613,9 @@ int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     vfik_io b = *m.io;
     b.q = w.q_prev;
     b.goal_dist = w.dist;
-    if (m.joint && m.list) b.q_ref = h->d_js_ref;
+    if ((m.joint && m.list) || m.script) b.q_ref = h->d_js_ref;
     b.active = m.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
-    const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0);
+    const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0, m.script ? h->d_script_mixw : nullptr);
     return rc != VFIK_OK ? rc : timed_launch_check(h, m, k, &w);
 }
 
@@ -1600,6 +1653,13 @@ int poll_pending(vfik_handle* h, const TimedMove& m, int done, int32_t* left) {
     return VFIK_OK;
 }
 
+// a script's arm whose first step is of no kind has no script: kept out in the same way
+bool any_arm_without_script(const vfik_handle* h, const int32_t* kind, size_t W) {
+    for (size_t b = 0; b < (size_t)h->B; ++b)
+        if (kind[b * W] != VFIK_STEP_FRAME && kind[b * W] != VFIK_STEP_POSTURE) return true;
+    return false;
+}
+
 // The host-pointer forms, after their check: every member of io and of the options in ONE device buffer of the handle (grown on demand, members
 // 256-byte aligned), copied in before the first block and out after the last one executed.  A list is copied in with the inputs (way16's
 // alignment rule holds for the caller's array too, although the kernel reads the staged copy).  Under a gate the caller's rows of the gated
@@ -1616,8 +1676,13 @@ int timed_run_host(vfik_handle* h, TimedMove& m, int poll_checks, int* checks_ru
     st.map(h->goto_stage.p);
     int rc = copy_members(st, IoStaging::INPUTS, h->stream);
     if (rc != VFIK_OK) return rc;
-    const bool kept_out = m.io->active || (m.list && any_arm_kept_out(h, m.x[m.joint ? vfik::X_WAYQ : vfik::X_WAY16], d.W * (m.joint ? d.n : 16)));
+    const bool kept_out = m.io->active || (m.script ? any_arm_without_script(h, static_cast<const int32_t*>(m.x[vfik::X_KIND]), d.W)
+                                                    : m.list && any_arm_kept_out(h, m.x[m.joint ? vfik::X_WAYQ : vfik::X_WAY16], d.W * (m.joint ? d.n : 16)));
     if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
+    if (m.script && !kept_out) {   // an arm that meets no posture step keeps its diff row, under no gate at all
+        const IoStaging::Member& df = st.extra(vfik::X_DIFF);
+        if (df.present && df.host) HIP_TRY(hipMemcpyAsync(df.dev, df.host, df.bytes, hipMemcpyHostToDevice, h->stream));
+    }
     const vfik_io dev_io = st.device_io();
     m.io = &dev_io;
     vfik::timed_rewire(st, m);
@@ -1680,6 +1745,16 @@ int vfik_follow_js(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts*
 int vfik_follow_js_host(vfik_handle* h, const vfik_io* io, const vfik_follow_js_opts* o, int poll_checks, int* checks_run) {
     TimedMove m;
     const int rc = follow_js_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
+}
+int vfik_script(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o) {
+    TimedMove m;
+    const int rc = script_check(h, io, o, m);
+    return rc != VFIK_OK ? rc : timed_run(h, m);
+}
+int vfik_script_host(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o, int poll_checks, int* checks_run) {
+    TimedMove m;
+    const int rc = script_check(h, io, o, m);
     return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
 }
 

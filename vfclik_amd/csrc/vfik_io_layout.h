@@ -1,5 +1,5 @@
 // vfik_io_layout.h -- the ONE description of vfik_io for the host-pointer call forms (vfik_step_host, vfik_rollout_host, vfik_goto_host,
-// vfik_follow_host, vfik_goto_js_host, vfik_follow_js_host, vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
+// vfik_follow_host, vfik_goto_js_host, vfik_follow_js_host, vfik_script_host, vfik_submit_host): which member is an input, how many bytes it has, and where it lies in a staging buffer.  Pure arithmetic, no HIP:
 // vfik_abi.cpp does the copies, tests/c_host/io_layout.cpp checks the layout on the CPU.
 #pragma once
 
@@ -79,6 +79,7 @@ enum IoExtra {
     X_WAY_TRAJ,    // [n_checks][B] int32
     X_DIFF,        // [B][n]            vfik_goto_js_opts' and vfik_follow_js_opts' diff
     X_WAYQ,        // [B][W][n]         input, as X_WAY16: vfik_follow_js_opts
+    X_KIND,        // [B][W] int32      input: vfik_script_opts' kind -- a script stages way16, wayq and kind
     N_IO_EXTRA
 };
 constexpr int N_STAGED = N_IO + N_IO_EXTRA;
@@ -168,9 +169,10 @@ struct IoStaging {
     }
 };
 
-// ---- timed moves: vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js and their host forms ----
+// ---- timed moves: vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js, vfik_script and their host forms ----
 // ONE description of a move between its checks and its last block.  The forms differ on two axes: the rule is the Cartesian distance pair or
-// the per-joint band (joint), the target one goal or a list with reached, next and len (list).
+// the per-joint band (joint), the target one goal or a list with reached, next and len (list).  A script (vfik_script) is a Cartesian list
+// (joint false, list true: its blocks' distance row, its traces) whose items are of either kind: `script` adds the joint rule's members.
 struct TimedMove {
     const vfik_io* io;
     bool joint, list;
@@ -180,6 +182,10 @@ struct TimedMove {
     // joint: goal_precision per joint; Cartesian: [0] metres, [1] radians.  via_prec: a list's, at every item but an arm's last
     double prec[VFIK_MAX_JOINTS], via_prec[VFIK_MAX_JOINTS];
     bool gated;            // the blocks run under the handle's gate (hold, the caller gates, or a list -- an arm without one is kept out)
+    // a script: prec / via_prec hold the Cartesian pair of its frame steps, these the rest
+    bool script;
+    double js_prec[VFIK_MAX_JOINTS], js_via_prec[VFIK_MAX_JOINTS];   // the per-joint band of its posture steps
+    double mix[2][4];      // mixer weights of channels 0..3 while an arm is under way to a frame [0] or to a posture [1]
 };
 
 struct TimedDims { size_t B, n, esz, W, n_checks; };   // arms, joints, bytes of an I/O element, items per list, checks
@@ -203,6 +209,7 @@ constexpr IoExtraInfo IO_EXTRAS[N_IO_EXTRA] = {
     /* X_WAY_TRAJ  */ {[](const TimedDims& d) { return d.B * sizeof(int32_t); }, true, false, false, true},
     /* X_DIFF      */ {[](const TimedDims& d) { return d.B * d.n * d.esz; }, true, false, false, false},    // a gated arm keeps its row
     /* X_WAYQ      */ {[](const TimedDims& d) { return d.B * d.W * d.n * d.esz; }, false, false, true, false},
+    /* X_KIND      */ {[](const TimedDims& d) { return d.B * d.W * sizeof(int32_t); }, false, false, true, false},
 };
 inline size_t extra_bytes(IoExtra x, const TimedDims& d, size_t checks) { return IO_EXTRAS[x].row(d) * (IO_EXTRAS[x].per_check ? checks : 1); }
 
@@ -211,12 +218,16 @@ constexpr unsigned timed_extras(bool joint, bool list) {
     return 1u << X_Q_OUT | 1u << X_PENDING | 1u << X_Q_TRAJ | 1u << (joint ? X_DIFF : X_DIST_TRAJ) |
            (list ? 1u << X_REACHED | 1u << X_NEXT | 1u << X_WAY_TRAJ | 1u << (joint ? X_WAYQ : X_WAY16) : 1u << X_ARRIVED);
 }
+// ... and a move's: a script stages a waypoint list's and, for its posture steps, diff, wayq and kind
+constexpr unsigned timed_extras(const TimedMove& m) {
+    return timed_extras(m.joint, m.list) | (m.script ? 1u << X_DIFF | 1u << X_WAYQ | 1u << X_KIND : 0u);
+}
 
 // The move's extras into a staging and its arrays rewired to their staged addresses (between the two: layout() and map()); the sizes of what
 // goes back after `done` checks.
 inline void timed_stage(IoStaging& st, const TimedMove& m, const TimedDims& d) {
     for (int x = 0; x < N_IO_EXTRA; ++x)
-        if (timed_extras(m.joint, m.list) >> x & 1)
+        if (timed_extras(m) >> x & 1)
             st.add((IoExtra)x, m.x[x], extra_bytes((IoExtra)x, d, d.n_checks), IO_EXTRAS[x].gated, IO_EXTRAS[x].always, IO_EXTRAS[x].input);
 }
 inline void timed_rewire(IoStaging& st, TimedMove& m) {

@@ -579,6 +579,23 @@ struct CheckArgs {
     double via_prec[VFIK_MAX_JOINTS];   // a list: at every item before an arm's last
 };
 hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream);
+// The check of a motion script (vfik_script; script_kernel<T>, vfik_kernel.hip): vfik_follow's state machine over a list whose items are goal
+// frames or postures, kind[b][w] telling which.  `c` is read as a Cartesian list's check reads it -- way = way16, prec / via_prec = the distance
+// pair, ref = the handle's reference row, diff -- and the rest is the script's own: what the joint rule and the switch of controller need.
+// An arm found at step next[b] is sent to the following one: a frame into its goal block, a posture into its row of `ref`, and the mixer quad of
+// that step's kind into plane 0 of its row of `mixw`, which the script's blocks read as KArgs::mixw.  k < 0: the pass in front of block 0 also
+// fills plane 1 (w4 w5 max_vel) from the arm's row of `bridge`, or from `bridge_u` where the handle has no per-arm bridge state.
+struct ScriptArgs {
+    CheckArgs c;
+    const int* kind;            // [B][W] VFIK_STEP_FRAME, VFIK_STEP_POSTURE; anything else ends the arm's script
+    const void* wayq;           // [B][W][n] read at posture steps alone
+    void* mixw;                 // the script's 2 quad planes [2][Bpad]: w0..w3 | w4 w5 max_vel -
+    const void* bridge;         // the handle's per-arm planes (vfik_set_mixer_weights, vfik_set_max_vel), or NULL
+    double bridge_u[4];         // w4, w5, max_vel, 0 of every arm without them
+    double mix[2][4];           // w0..w3 under way to a frame [0], to a posture [1]
+    double js_prec[VFIK_MAX_JOINTS], js_via_prec[VFIK_MAX_JOINTS];   // the joint rule's band: at an arm's last step, at those before it
+};
+hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

@@ -90,6 +90,9 @@ def load_library(path=None):
         "vfik_follow_js_opts_size": (C.c_size_t, []),
         "vfik_follow_js": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowJsOpts)]),
         "vfik_follow_js_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.FollowJsOpts), C.c_int, C.POINTER(C.c_int)]),
+        "vfik_script_opts_size": (C.c_size_t, []),
+        "vfik_script": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.ScriptOpts)]),
+        "vfik_script_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.ScriptOpts), C.c_int, C.POINTER(C.c_int)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -139,7 +142,8 @@ def load_library(path=None):
         raise VfikError("struct layout mismatch: vfik_follow_opts is %d bytes in the library, %d in the Python mirror"
                         % (lib.vfik_follow_opts_size(), C.sizeof(_abi.FollowOpts)))
     for name, size, mirror in (("vfik_goto_js_opts", lib.vfik_goto_js_opts_size(), _abi.GotoJsOpts),
-                               ("vfik_follow_js_opts", lib.vfik_follow_js_opts_size(), _abi.FollowJsOpts)):
+                               ("vfik_follow_js_opts", lib.vfik_follow_js_opts_size(), _abi.FollowJsOpts),
+                               ("vfik_script_opts", lib.vfik_script_opts_size(), _abi.ScriptOpts)):
         if size != C.sizeof(mirror):
             raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
@@ -570,7 +574,8 @@ class Engine:
         B, n, ft, n_checks = self.batch, self.n, self.io_dtype.name, o.n_cycles // max(o.stride, 1)
         shapes = {"arrived": ((B,), "int32"), "reached": ((B, getattr(o, "n_way", 0)), "int32"), "next": ((B,), "int32"),
                   "pending": ((n_checks,), "int32"), "q_out": ((B, n), ft), "diff": ((B, n), ft), "q_traj": ((n_checks, B, n), ft),
-                  "dist_traj": ((n_checks, B, 2), ft), "way_traj": ((n_checks, B), "int32"), "way": (None, ft), "wayq": (None, ft)}
+                  "dist_traj": ((n_checks, B, 2), ft), "way_traj": ((n_checks, B), "int32"), "way": (None, ft), "wayq": (None, ft),
+                  "kind": ((B, getattr(o, "n_way", 0)), "int32")}
         return tuple((k, x) + shapes[k] for k, x in arrays.items())
 
     @staticmethod
@@ -774,6 +779,85 @@ class Engine:
         o.n_way, o.wayq = w.shape[1], w.ctypes.data
         return self._move_host(self.lib.vfik_follow_js_host, io, o, out, keep, poll, ("reached", "next", "pending", "diff"),
                                ("q_traj", "way_traj") if trajectory else ())
+
+    # -- motion scripts: frames and postures in one list per arm (vfik_script) ------------------------------------------------------
+    def _script_opts(self, n_cycles, dt, stride, hold, clamp, precision, via_precision, js_precision, js_via_precision, mix_frame,
+                     mix_posture):
+        """The options of a script without its arrays, and the precision arrays they point into (the caller keeps them until the call
+        is over)."""
+        o = self._move_opts(_abi.ScriptOpts, n_cycles, dt, stride, hold, clamp)
+        self._follow_precision(o, precision, via_precision)
+        prec = self._js_precision(js_precision, "js_precision")
+        via = None if js_via_precision is None else self._js_precision(js_via_precision, "js_via_precision")
+        o.prec, o.via_prec = prec.ctypes.data, (None if via is None else via.ctypes.data)
+        for name, dst, src in (("mix_frame", o.mix_frame, mix_frame), ("mix_posture", o.mix_posture, mix_posture)):
+            w = np.asarray(src, dtype=np.float64)
+            if w.shape != (4,):
+                raise ValueError("%s must be 4 mixer weights (channels 0..3), got shape %s" % (name, w.shape))
+            for i in range(4):
+                dst[i] = float(w[i])
+        return o, (prec, via)
+
+    def script(self, io, kind, way, wayq, n_cycles, dt, precision, js_precision, via_precision=None, js_via_precision=None,
+               mix_frame=_abi.MIX_FRAME, mix_posture=_abi.MIX_POSTURE, stride=1, hold=False, clamp=False, reached=None, next=None,
+               pending=None, q_out=None, q_traj=None, dist_traj=None, diff=None, way_traj=None, n_way=None):
+        """Run every arm's own motion script, asynchronously on the engine's stream (include/vfik.h: vfik_script): :meth:`follow`'s
+        state machine over a list whose steps are goal frames or postures.  ``kind``: int32 (B, W), ``_abi.STEP_FRAME`` or
+        ``_abi.STEP_POSTURE``, any other value ends the arm's script (an arm without a step is kept out); ``way``: (B, W, 16) or
+        (B, W, 4, 4), 16-byte aligned, read at frame steps; ``wayq``: (B, W, n), read at posture steps.  ``precision`` / ``via_precision``
+        = (metres, radians) as :meth:`follow`, ``js_precision`` / ``js_via_precision`` (length n) as :meth:`follow_js`.  ``mix_frame`` and
+        ``mix_posture``: the mixer weights of channels 0..3 an arm runs under on its way to a frame or to a posture -- by default what the
+        reference's cartesian_controller() and joint_controller() send.  ``io.q_ref`` must be left out.  ``reached`` int32 (B, W) and
+        ``next`` int32 (B,) are required; ``pending``, ``q_out``, ``q_traj``, ``dist_traj``, ``diff``, ``way_traj`` as :meth:`follow` and
+        :meth:`follow_js`.  Torch tensors on this device, or raw addresses (then with ``n_way``).  The engine needs ``F_MIXER``; its own
+        mixer weights and limiter speeds are read, never written."""
+        if reached is None or next is None:
+            raise ValueError("script needs reached, an int32 (batch, n_way) device array, and next, an int32 (batch,) one")
+        n_way = self._list_len("way", way, lambda w: w.dim() in (3, 4) and w.shape[0] == self.batch and w.numel() == self.batch * w.shape[1] * 16,
+                               "(batch, n_way, 16) or (batch, n_way, 4, 4)", "steps", n_way)
+        n_way = self._list_len("wayq", wayq, lambda w: w.dim() == 3 and w.shape[0] == self.batch and w.shape[2] == self.n,
+                               "(batch, n_way, %d)" % self.n, "steps", n_way)
+        o, kept = self._script_opts(n_cycles, dt, stride, hold, clamp, precision, via_precision, js_precision, js_via_precision,  # noqa: F841
+                                    mix_frame, mix_posture)
+        o.n_way = int(n_way)
+        self._check_dev(self._dev_specs(o, kind=kind, way=way, wayq=wayq, reached=reached, next=next, pending=pending, q_out=q_out,
+                                        q_traj=q_traj, dist_traj=dist_traj, diff=diff, way_traj=way_traj))
+        o.kind, o.way16, o.wayq, o.reached, o.next, o.pending = _ptr(kind), _ptr(way), _ptr(wayq), _ptr(reached), _ptr(next), _ptr(pending)
+        o.q_out, o.q_traj, o.dist_traj, o.diff, o.way_traj = _ptr(q_out), _ptr(q_traj), _ptr(dist_traj), _ptr(diff), _ptr(way_traj)
+        self._chk(self.lib.vfik_script(self.h, C.byref(io), C.byref(o)))
+
+    def script_host(self, q, kind, way, wayq, n_cycles, dt, precision, js_precision, via_precision=None, js_via_precision=None,
+                    mix_frame=_abi.MIX_FRAME, mix_posture=_abi.MIX_POSTURE, stride=1, hold=False, clamp=False, trajectory=False, poll=0,
+                    want=("qdot_out",), null_control=None, active=None, q_lo=None, q_hi=None):
+        """Host arrays in, host arrays out (vfik_script_host; synchronous).  ``kind`` (B, W), ``way`` (B, W, 16) or (B, W, 4, 4) and
+        ``wayq`` (B, W, n) as :meth:`script`, converted to int32 and the engine's dtype.  Returns what :meth:`follow_host` returns plus
+        ``diff`` (B, n): ``q``, ``reached`` (B, W), ``next`` (B,), ``pending``, ``checks_run``, the rows named in ``want`` and, with
+        ``trajectory``, ``q_traj``, ``dist_traj`` and ``way_traj``.  ``poll`` > 0 ends the call once every arm that takes part is at
+        its last step."""
+        kd = np.ascontiguousarray(kind, dtype=np.int32)
+        if kd.ndim != 2 or kd.shape[0] != self.batch or kd.shape[1] < 1:
+            raise ValueError("kind must be (batch, n_way), got %s" % (kd.shape,))
+        W = kd.shape[1]
+        w = np.asarray(way)
+        if w.ndim not in (3, 4) or w.shape[0] != self.batch or w.shape[1] != W or w.size != self.batch * W * 16:
+            raise ValueError("way must be (batch, %d, 16) or (batch, %d, 4, 4), got %s" % (W, W, w.shape))
+        w = np.ascontiguousarray(w, dtype=self.io_dtype).reshape(self.batch, W, 16)
+        if w.ctypes.data % 16:   # (as follow_host)
+            buf = np.empty(w.size + 4, dtype=self.io_dtype)
+            off = (-buf.ctypes.data % 16) // buf.itemsize
+            buf = buf[off:off + w.size].reshape(w.shape)
+            buf[...] = w
+            w = buf
+        wq = np.asarray(wayq)
+        if wq.shape != (self.batch, W, self.n):
+            raise ValueError("wayq must be (batch, %d, %d), got %s" % (W, self.n, wq.shape))
+        wq = np.ascontiguousarray(wq, dtype=self.io_dtype)
+        io, out, keep = self._host_io(q, null_control, None, None, active, q_lo, q_hi, want)
+        o, kept = self._script_opts(n_cycles, dt, stride, hold, clamp, precision, via_precision, js_precision, js_via_precision,  # noqa: F841
+                                    mix_frame, mix_posture)
+        o.n_way, o.kind, o.way16, o.wayq = W, kd.ctypes.data, w.ctypes.data, wq.ctypes.data
+        return self._move_host(self.lib.vfik_script_host, io, o, out, keep, poll, ("reached", "next", "pending", "diff"),
+                               ("q_traj", "dist_traj", "way_traj") if trajectory else ())
 
     def make_io(self, q, null_control=None, q_ref=None, q_cmded=None, active=None, q_lo=None, q_hi=None, **outs):
         """IO block from device pointers (torch tensors on this device, or raw addresses).  active: int32 [B]."""

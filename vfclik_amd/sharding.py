@@ -254,6 +254,15 @@ class ShardedEngine:
         qs_of, ways = self._rows(q, "q", global_rows), self._rows(np.asarray(wayq), "wayq", global_rows)
         return self._checked_host(lambda e, i, a: e.follow_js_host(qs_of[i], ways[i], n_cycles, dt, precision, **a), global_rows, kw)
 
+    def script_host(self, q, kind, way, wayq, n_cycles, dt, precision, js_precision, global_rows=True, **kw):
+        """Engine.script_host over this rank's arms, as :meth:`follow_host`: ``kind`` (rows, W), ``way`` (rows, W, 16) and ``wayq``
+        (rows, W, n) are sharded with the arms; the precisions and the two mixer quads are shared."""
+        import numpy as np
+        qs_of, kinds = self._rows(q, "q", global_rows), self._rows(np.asarray(kind), "kind", global_rows)
+        ways, wayqs = self._rows(np.asarray(way), "way", global_rows), self._rows(np.asarray(wayq), "wayq", global_rows)
+        return self._checked_host(lambda e, i, a: e.script_host(qs_of[i], kinds[i], ways[i], wayqs[i], n_cycles, dt, precision, js_precision, **a),
+                                  global_rows, kw)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
