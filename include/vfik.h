@@ -598,6 +598,12 @@ int vfik_field_path(vfik_handle* h);
  * (0.001 and -10 for every point obstacle and for the near-goal repeller: object_feeder:301-302,323,331): on field path 1 the lean
  * launches then read one quad (x y z radius) per repeller instead of 24 bytes, the pair from the batch constants.  0 otherwise. */
 int vfik_uniform_repellers(vfik_handle* h);
+/* 1 when, on top of vfik_uniform_repellers, the batch's repellers have decay order 5 and no arm has more than one chunk of them (8 with
+ * float32 I/O) -- goal + up to 8 point obstacles as the object feeder sends them (object_feeder:302,333): the lean launches
+ * (q -> qdot_out) of a float32 handle of up to 7 joints, at one wave per SIMD, then run the kernel's one-chunk order-5 body, which reads
+ * its 8 repeller planes without looking at the slots in use.  Same results either way.  0 otherwise: float64 I/O, longer chains, other
+ * orders, more obstacles, or the environment variable VFIK_ONE_CHUNK=0 at vfik_create (tests, A/B).  Decided by vfik_set_fields. */
+int vfik_one_chunk(vfik_handle* h);
 /* ABI 5.  1 when the decay repellers of the batch have integer orders that are not all the same: lean and publishing-lean
  * single-cycle launches of chains without a tool / weights then read one order byte per repeller beside the compact image and stay
  * on field path 1 / 2 (a wave whose 64 arms agree slot by slot pays scalar control flow only; a wave with an odd arm per-lane

@@ -89,6 +89,8 @@ struct vfik_handle {
     std::vector<double> arm_safe, arm_force;
     int uni_allowed = 1;                  // VFIK_UNIFORM_IMAGE=0: always the compact image (tests, A/B)
     int mixed_allowed = 1;                // VFIK_MIXED_ORDERS=0: differing integer orders take the general path, as until round 3 (tests, A/B)
+    int one_chunk_allowed = 1;            // VFIK_ONE_CHUNK=0: never the one-chunk order-5 body of the lean launches (tests, A/B)
+    int one5 = 0;                         // the uniform image holds one chunk of order-5 repellers: cycle_kernel_s's one-chunk body (vfik_set_fields decides, vfik_one_chunk reports)
     int uni_ok = 0;                       // the batch's decay repellers share one pair, now in the device constants (KConst::rep_safe, dh[0].pad)
     double uni_safe = 0.0, uni_force = 0.0;
     void* d_slots_fast = nullptr;  // compact repeller image for the straight-line path: 3 quad planes per PAIR of slots
@@ -359,6 +361,13 @@ void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts
     }
 }
 
+// Quad planes of the uniform repeller image: the empty plane 0, then one per slot -- and at least one chunk's worth of the I/O type
+// (Stage<T>::PRE), because the one-chunk body of the lean launches requests planes 1 ... PRE without looking at the slots in use.
+int uni_image_planes(const vfik_handle* h) {
+    const int pre = h->io_dtype == 32 ? vfik::Stage<float>::PRE : vfik::Stage<double>::PRE;
+    return std::max(std::max(1, h->max_slots), pre) + 1;
+}
+
 void fill_kargs(const vfik_handle* h, const vfik_io* io, vfik::KArgs& a) {
     std::memset(&a, 0, sizeof a);
     a.B = h->B;
@@ -402,6 +411,7 @@ void fill_kargs(const vfik_handle* h, const vfik_io* io, vfik::KArgs& a) {
     a.slots_used_fast = h->slots_used_fast;
     a.has_funnel = h->any_funnel;
     a.waves2 = h->waves2;
+    a.one5 = h->one5;
     a.uni = h->uni_ok && h->uni_allowed;
     a.uni_planes = 3 * ((std::max(1, h->max_slots) + 1) / 2);
     a.stamps = h->d_stamps;
@@ -517,6 +527,7 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
     if (const char* e = std::getenv("VFIK_SUB8_MAX_BATCH")) h->sub8_max_batch = h->sub8_max_batch_full = h->sub8_max_batch_ns = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("VFIK_TWO_WAVES")) h->waves2 = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_UNIFORM_IMAGE")) h->uni_allowed = std::atoi(e) != 0;
+    if (const char* e = std::getenv("VFIK_ONE_CHUNK")) h->one_chunk_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_MIXED_ORDERS")) h->mixed_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_DH_PATTERN")) h->dhp_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_ZERO_COPY_MAX")) h->zero_copy_max = (size_t)std::max(0L, std::atol(e));
@@ -535,7 +546,8 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
         const size_t sz_kc = VFIK_KCONST_SLOT(vfik::kconst_bytes(n_joints));   // (+ slack inside: the kinematics block is copied in whole 1-KiB rows)
         const size_t sz_lv = (size_t)((n_joints + 4) / 4) * h->Bpad * 4 * sizeof(float);
         const size_t sz_sf = (std::max<size_t>(1, (size_t)max_slots) + 1) / 2 * 3 * quad_plane;
-        const size_t sz_su = (std::max<size_t>(1, (size_t)max_slots) + 1) * quad_plane;   // uniform image: an EMPTY plane, then one quad plane per slot
+        // uniform image: an EMPTY plane, then one quad plane per slot -- never fewer than one chunk's (uni_image_planes: the one-chunk body reads them all)
+        const size_t sz_su = (size_t)uni_image_planes(h) * quad_plane;
         const size_t sz_sl = std::max<size_t>(1, (size_t)max_slots) * 2 * quad_plane;  // >= 1 slot: the prefetch reads slot 0
         const size_t sz_or = (std::max<size_t>(1, (size_t)max_slots) + 15) / 16 * (size_t)h->Bpad * 16;   // order planes (zeros: order 0, force 0)
         if (dev_alloc(h, &h->d_arena, sz_goal + sz_kc + sz_lv + sz_sf + sz_su + sz_sl + sz_or, true)) return bail("alloc state arena");
@@ -559,7 +571,8 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
     {   // the uniform image starts out with every slot unused (radius -inf), like the zeros (force 0) of the other two images
         std::vector<char> plane((size_t)h->Bpad * 4 * h->esz, 0);
         for (int b = 0; b < h->Bpad; ++b) put_io(h, plane, (size_t)b * 4 + 3, -std::numeric_limits<double>::infinity());
-        for (int sidx = 0; sidx < std::max(1, max_slots) + 1; ++sidx)   // (plane 0 stays like this for good: the slot every out-of-range quad reads)
+        // (plane 0 stays like this for good: the slot every out-of-range quad reads; so do the planes past max_slots, which no call writes)
+        for (int sidx = 0; sidx < uni_image_planes(h); ++sidx)
             if (hipMemcpyAsync(static_cast<char*>(h->d_slots_uni) + (size_t)sidx * plane.size(), plane.data(), plane.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess)
                 return bail("init uniform image");
         if (hipStreamSynchronize(h->stream) != hipSuccess) return bail("init uniform image");
@@ -894,6 +907,13 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
         }
     }
     h->uni_ok = uni_ok ? 1 : 0;
+    // One chunk of order-5 repellers on the uniform image (what the feeder sends: object_feeder:302,333): the lean float launches of chains
+    // of up to 7 joints take the body compiled for exactly that (cycle_kernel_s, ONE5).  It reads planes 1 ... PRE of the image whatever
+    // the slots in use: the image owns them (uni_image_planes), and every plane at or beyond an arm's count is empty -- the copy above
+    // rewrites all max_slots planes of the arms it names (pack_fields: radius -inf past the arm's last repeller), the planes beyond
+    // max_slots keep the -inf of vfik_create, and vfik_move_fields writes the rows of existing repellers alone.
+    h->one5 = (h->one_chunk_allowed && uni_ok && h->uni_allowed && h->fast_order == 5 && h->io_dtype == 32 && h->n <= 7 &&
+               h->slots_used_fast <= vfik::Stage<float>::PRE) ? 1 : 0;
     return VFIK_OK;
 }
 
@@ -2011,6 +2031,11 @@ int vfik_mixed_orders(vfik_handle* h) {
 int vfik_uniform_repellers(vfik_handle* h) {
     if (!h) return VFIK_E_ARG;
     return (h->fast_order >= 0 && h->uni_ok && h->uni_allowed) ? 1 : 0;
+}
+
+int vfik_one_chunk(vfik_handle* h) {
+    if (!h) return VFIK_E_ARG;
+    return (h->fast_order >= 0 && h->one5) ? 1 : 0;
 }
 
 int vfik_set_small_batch_kernel(vfik_handle* h, int max_batch) {

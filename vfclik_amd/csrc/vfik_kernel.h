@@ -210,6 +210,8 @@ struct KArgs {
     int uni;                     // 1: every decay repeller of the batch shares one safe distance and one force (KConst::rep_safe, dh[0].pad): lean launches read the uniform image
     int uni_planes;              // quad planes of the compact image = offset of the uniform image behind slots_fast
     int waves2;                  // 1: lean straight-line float launches of more than n_simd waves take the two-waves-per-SIMD build (VFIK_TWO_WAVES=0: never)
+    int one5;                    // 1: the uniform image holds ONE chunk of order-5 repellers and owns planes 1 ... PRE (vfik_set_fields): the lean float launches of
+                                 // chains of up to 7 joints take cycle_kernel_s's one-chunk body (in what was padding: sizeof(KArgs) is unchanged)
     // round 4: decay repellers whose INTEGER orders differ (README.old:75 documents order 20 beside the feeder's 5, object_feeder:302)
     const void* orders;          // order planes: 16 bytes per arm and plane = the decay orders of 16 slots of the compact image, one byte each
     int mixed;                   // 1: the batch's repellers do not share one order -- the straight-line path reads `orders` (MIXO kernel variants)
@@ -231,6 +233,10 @@ struct KLean {
     unsigned flags;
     int block;
 };
+// KLean::fast_order of a uniform-image launch: the decay order (< 128) in bits 0-6, the image's offset in quad planes from bit 8 on, and
+// bit 7: take the one-chunk order-5 body (cycle_kernel_s; the launcher sets it from KArgs::one5)
+constexpr int ONE5_BIT = 128;
+static_assert(sizeof(KArgs) == 352 && sizeof(KLean) == 56, "KArgs / KLean: the kernarg sizes the launch costs were measured with");
 
 // size of KConst<nj> for the host (0 if nj is not built); kconst_fill returns the largest
 // recomposition error of the DH conversion (the caller refuses a chain above 1e-9)

@@ -858,7 +858,12 @@ template <typename T, int NJ> struct ArenaLayout {
 // vector instructions (C3 -5.3 % warm / -3.7 % cold, C3N -3.1 %, C3F -2.7 %: profiles/r04_ab_dhp.txt, before the swap lost its last
 // multiplications).  Built for the lean and the publishing-lean straight-line float variants (plan_cycle); every other variant, and every
 // chain that does not match a built pattern, runs the general DH form.
-template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF, bool FUN, int WAVES, bool UNI, bool MIXO, int DHP>
+// ONE5 = the uniform-image lean launch whose batch fits ONE chunk of decay order 5 (at most PRE point obstacles of order 5: what object_feeder
+// sends, object_feeder:302,333), decided by the host (vfik_set_fields) and chosen by cycle_kernel_s behind one scalar branch: the order is the
+// constant 5, every slot quad idx < PRE comes from plane idx + 1 of the image without the in-use select (planes past the slots in use are
+// empty: radius -inf), and there is neither a next-chunk request nor a further-chunks loop.  The arithmetic is the other body's, statement
+// for statement (profiles/one_chunk_body.txt).
+template <typename T, int NJ, bool NULLSP, bool PLAIN, bool ROLL, bool FASTF, int LEAN, int CF, bool FUN, int WAVES, bool UNI, bool MIXO, int DHP, bool ONE5 = false>
 __device__ __forceinline__ void
 cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::value, KLean, KArgs>::type& a_in) {
     static_assert(DHP == 0 || (PLAIN && FASTF && (!ROLL || LEAN == 1) && LEAN != 0 && (sizeof(T) == 4 || DHP == 1)), "DHP: the lean straight-line variants (single cycle, a stepped rollout's cycle, and the lean rollout); the option bits: float32 I/O");
@@ -881,6 +886,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     static_assert(!FUN || (FASTF && PLAIN && !ROLL && (LEAN == 1 || LEAN == 3)), "FUN: the lean single-cycle straight-line variants");
     static_assert(WAVES == 1 || (WAVES == 2 && LEAN == 1 && FASTF && PLAIN && !ROLL && !FUN && sizeof(T) == 4 && NJ <= 7), "WAVES 2: lean straight-line float launches only");
     static_assert(!UNI || (FASTF && PLAIN && !ROLL && !FUN && (LEAN == 1 || LEAN == 3)), "UNI: the lean single-cycle straight-line variants");
+    static_assert(!ONE5 || (UNI && LEAN == 1 && WAVES == 1 && sizeof(T) == 4 && NJ <= 7), "ONE5: the uniform-image lean float launch at one wave per SIMD");
     KArgs a;
     if constexpr (SmallArgs<LEAN, ROLL, FASTF, MIXO>::value) {
         a = KArgs{};
@@ -1009,7 +1015,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
     // The goal and slot requests are issued later, between the joints of the kinematics: a load costs
     // the issuing wave ~50 cycles while the CU's four waves queue on the one address unit
     // (tools/ubench_loads.hip), and spreading them out lets that queue drain under arithmetic.
-    const int npre = a.slots_used < PRE ? a.slots_used : PRE;
+    const int npre = ONE5 ? PRE : (a.slots_used < PRE ? a.slots_used : PRE);
     // The straight-line path reads the COMPACT repeller image (two slots in three quads, vfik_kernel.h): a chunk of PRE
     // slots is QPC = 3 PRE / 2 quads instead of 2 PRE -- a quarter fewer bytes and requests for what is, at these
     // batches, the longest wait of the wave (the slots' data is the last to arrive).
@@ -1026,7 +1032,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         // ~60 fewer scalar instructions a wave: C3 +1.2 % warm, +0.3 % cold, C5 +-0.1 %; scalar work is not what a lone wave waits for.)
         // (UNI: plane 0 of the uniform image is an EMPTY slot for every arm -- radius -inf --, slot m sits in plane m + 1: a quad past the
         // slots in use is then harmless by itself and the chunk needs no mask)
-        const bool in = UNI ? idx < npre : (FASTF ? 2 * (idx / 3) < npre : (idx >> 1) < npre);
+        const bool in = ONE5 ? true : UNI ? idx < npre : (FASTF ? 2 * (idx / 3) < npre : (idx >> 1) < npre);
         stage_quad<T>(slots0 + (in ? (long)(UNI ? idx + 1 : idx) * planeB : 0), (unsigned)arm * (unsigned)QB, dreg, Stage<T>::slot_off(idx, NJ));
     };
     constexpr int N_SLOT = QPC * Q16;                       // requests issued after the goal
@@ -1576,7 +1582,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             // used slot of every arm is a decay repeller with the same integer decay order -- what
             // object_feeder produces for point obstacles (object_feeder:317-334).  Empty slots carry
             // force 0.  Straight-line code per chunk of PRE slots: the slots interleave in the schedule.
-            const int n0 = a.fast_order;
+            const int n0 = ONE5 ? 5 : a.fast_order;
             // One chunk = PRE slots: read them out of LDS, then -- before the arithmetic -- request the
             // next chunk into the same rows, so that its latency hides behind this chunk's math.
             // One chunk = PRE slots: read them out of LDS, then -- before the arithmetic -- request the
@@ -1626,7 +1632,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
                         fk[m] = m < ncur ? v[6 * hf + 5] : 0.0;
                     }
                 }
-                if (c0 + PRE < a.slots_used) {  // wave-uniform
+                if (!ONE5 && c0 + PRE < a.slots_used) {  // wave-uniform
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the rows have returned
 #pragma unroll
                     for (int idx = 0; idx < QPC; ++idx) {
@@ -1779,6 +1785,7 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             chunk(0);
             // further chunks: kept out of line of the first so that the common (<= PRE slots) case is
             // straight-line code with no loop-carried register shuffling
+            if constexpr (!ONE5)
             for (int c0 = PRE; c0 < a.slots_used; c0 += PRE) {
                 VFIK_WAIT_VM(0);
                 chunk(c0);
@@ -2326,6 +2333,10 @@ cycle_kernel_s(const void* base, const void* q, void* qdot_out, int* status, int
     KLean k;
     k.base = base; k.q = q; k.qdot_out = qdot_out; k.status = status;
     k.B = B; k.Bpad = Bpad; k.slots_used = slots_used; k.fast_order = fast_order; k.flags = flags; k.block = block;
+    // (the one-chunk order-5 body: bit 7 of fast_order's low byte, set by launch_plan for these instantiations alone -- orders are < 128)
+    if constexpr (UNI && LEAN == 1 && WAVES == 1 && !ROLL && !FUN && sizeof(T) == 4 && NJ <= 7) {
+        if (fast_order & ONE5_BIT) { cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, FUN, WAVES, UNI, false, DHP, true>(k); return; }
+    }
     cycle_body<T, NJ, NULLSP, PLAIN, ROLL, FASTF, LEAN, CF, FUN, WAVES, UNI, false, DHP>(k);
 }
 // The members of the handle's state arena and the launch's first arguments, from scalars (the arena's layout: vfik_kernel.h)
@@ -3466,6 +3477,10 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
     // UNI variants read the uniform repeller image, a.uni_planes quad planes behind the compact one: the offset rides in the upper bits of
     // fast_order (KLean's fourteen dwords are all taken)
     a.fast_order = p.uni ? (p.fast_order & 255) | (a.uni_planes << 8) : p.fast_order;
+    // ... and bit 7 of its low byte asks cycle_kernel_s for the one-chunk order-5 body (KArgs::one5: the host's decision, vfik_set_fields)
+    // (the body reads planes 1 ... PRE of the image and nothing of slots_used or the order: never without what the decision rests on)
+    const bool one5 = a.one5 && p.family == CycleFamily::Lean && p.lean == 1 && p.uni && !p.fun && p.waves == 1 && sizeof(T) == 4 && NJ <= 7 &&
+                      p.fast_order == 5 && p.slots_used <= Stage<T>::PRE;
     a.slots_used = p.slots_used;
     a.block = p.block;
     const dim3 grid(p.grid), blk(p.block);
@@ -3474,7 +3489,7 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
     auto lean_s = [&](auto CF, auto FUN, auto WAVES, auto UNI, auto D) {
         if constexpr (SmallArgs<1, false, true>::value)
             hipLaunchKernelGGL((cycle_kernel_s<T, NJ, NS, true, false, true, 1, VFIK_V(CF), false, VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>), grid, blk, p.lds,
-                               stream, a.arena, a.q, a.qdot_out, a.status, a.B, a.Bpad, a.slots_used, a.fast_order, a.flags, a.block);
+                               stream, a.arena, a.q, a.qdot_out, a.status, a.B, a.Bpad, a.slots_used, one5 ? a.fast_order | ONE5_BIT : a.fast_order, a.flags, a.block);
         else
             launch_x<T, NJ, NS, true, false, true, 1, VFIK_V(CF), false, VFIK_V(FUN), VFIK_V(WAVES), VFIK_V(UNI), VFIK_V(D)>(a, p, stream);
         launched = true;

@@ -104,6 +104,7 @@ def load_library(path=None):
         "vfik_slots_in_use": (C.c_int, [H]),
         "vfik_field_path": (C.c_int, [H]),
         "vfik_uniform_repellers": (C.c_int, [H]),
+        "vfik_one_chunk": (C.c_int, [H]),
         "vfik_mixed_orders": (C.c_int, [H]),
         "vfik_launch_epoch": (C.c_long, [H]),
         "vfik_dh_pattern": (C.c_int, [H]),
@@ -410,6 +411,11 @@ class Engine:
     def uniform_repellers(self):
         """True when every decay repeller of the batch shares one safe distance and one force (the uniform repeller image is read)."""
         return bool(self.lib.vfik_uniform_repellers(self.h))
+
+    @property
+    def one_chunk(self):
+        """True when the lean float32 launches take the kernel's one-chunk order-5 body (include/vfik.h: vfik_one_chunk)."""
+        return bool(self.lib.vfik_one_chunk(self.h))
 
     @property
     def dh_pattern(self):
