@@ -16,6 +16,7 @@
 #include "../../include/vfik.h"
 #include "vfik_io_layout.h"
 #include "vfik_kernel.h"
+#include "vfik_scene.h"
 
 namespace {
 
@@ -36,18 +37,6 @@ int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess) return fail(VFIK_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-
-// number of device slots a field of this type occupies (goal block excluded)
-int slots_of(int type) {
-    switch (type) {
-        case VFIK_FIELD_NULL: return 0;
-        case VFIK_FIELD_REPELLER: return 1;
-        case VFIK_FIELD_HEMISPHERE: return 2;
-        case VFIK_FIELD_FUNNEL: return 2;
-        case VFIK_FIELD_ATTRACTOR: return 3;
-        default: return -1;
-    }
-}
 
 }  // namespace
 
@@ -85,17 +74,13 @@ struct vfik_handle {
     void* d_funnel = nullptr;  // aux block, 6 quad planes: the arm's funnel attractor (3) and hemisphere repeller (3) on the straight-line path (vfik_kernel.h)
     void* d_slots = nullptr;   // 2*S quad planes
     void* d_slots_uni = nullptr;   // uniform repeller image: ONE quad plane per slot (x y z radius); read when every decay repeller of the batch shares safe distance and force
-    std::vector<char> arm_pair_state;     // per arm: 0 no decay repeller, 1 all of them share one (safe, force), 2 mixed
-    std::vector<double> arm_safe, arm_force;
-    int uni_allowed = 1;                  // VFIK_UNIFORM_IMAGE=0: always the compact image (tests, A/B)
-    int mixed_allowed = 1;                // VFIK_MIXED_ORDERS=0: differing integer orders take the general path, as until round 3 (tests, A/B)
-    int one_chunk_allowed = 1;            // VFIK_ONE_CHUNK=0: never the one-chunk order-5 body of the lean launches (tests, A/B)
-    int one5 = 0;                         // the uniform image holds one chunk of order-5 repellers: cycle_kernel_s's one-chunk body (vfik_set_fields decides, vfik_one_chunk reports)
-    int uni_ok = 0;                       // the batch's decay repellers share one pair, now in the device constants (KConst::rep_safe, dh[0].pad)
-    double uni_safe = 0.0, uni_force = 0.0;
+    // the field sets as vfik_set_fields left them (vfik_scene.h): every arm's summary, and what the batch's launches take for it
+    std::vector<vfik::ArmScene> arms;
+    vfik::ScenePlan scene;
+    vfik::SceneKnobs knobs;
+    double uni_safe = 0.0, uni_force = 0.0;   // the uniform repeller pair as the device constants hold it (KConst::rep_safe, dh[0].pad)
     void* d_slots_fast = nullptr;  // compact repeller image for the straight-line path: 3 quad planes per PAIR of slots
-    void* d_orders = nullptr;      // order planes: 16 bytes per arm and plane, one byte per compact-image slot (vfik_kernel.h); read when `mixed`
-    int mixed = 0;                 // the batch's decay repellers have integer orders that differ (between slots or between arms)
+    void* d_orders = nullptr;      // order planes: 16 bytes per arm and plane, one byte per compact-image slot (vfik_kernel.h); read when the scene is `mixed`
     unsigned short* d_repmap = nullptr;   // vfik_move_fields: general slot of the arm's k-th decay repeller, 8 entries (16 bytes) per arm and plane (vfik_kernel.h: MoveArgs)
     unsigned short* d_scenemap = nullptr; // vfik_move_scene: the same for its k-th funnel, hemisphere and attractor behind the goal block, three maps in a row (vfik_kernel.h: SceneMoveArgs)
     bool fields_set = false;       // some vfik_set_fields call succeeded: there are images to move
@@ -145,14 +130,6 @@ struct vfik_handle {
     size_t dev_bytes = 0;
     // host bookkeeping
     std::vector<double> bridge_host;  // [B][8] mirror of d_mixw_arm: mixer weights 0..5, max_vel 6
-    std::vector<int> slots_per_arm;
-    std::vector<int> fast_slots_per_arm;  // slots of the compact repeller image per arm (the funnel is not one)
-    std::vector<char> arm_has_funnel;
-    int slots_used_fast = 0;
-    int any_funnel = 0;
-    std::vector<int> arm_order;  // per arm: -1 no repellers, n >= 0 all slots are repellers of integer order n, -2 general
-    int slots_used = 0;
-    int fast_order = 0;
     int plain = 0;  // the chain allows the PLAIN kernel variants: 1 + (shared tool ? 1 : 0) + (shared IK weights other than one ? 2 : 0); 0: the general variants
     int dhp = 0;    // ... and the chain matches a DH pattern the lean kernels are built for (vfik_kernel.h: DhPattern)
     int dhp_allowed = 1;   // VFIK_DH_PATTERN=0: always the general DH form (tests, A/B)
@@ -238,142 +215,17 @@ bool gpu_visible(const void* p) {
     return at.type == hipMemoryTypeHost || at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
-template <typename T>
-void put(std::vector<char>& buf, size_t idx, double v) {
-    reinterpret_cast<T*>(buf.data())[idx] = static_cast<T>(v);
-}
-
 // ... rounded to the handle's I/O type
 void put_io(const vfik_handle* h, std::vector<char>& buf, size_t idx, double v) {
-    if (h->io_dtype == 32) put<float>(buf, idx, v); else put<double>(buf, idx, v);
-}
-
-// Pack the field sets of n_arms arms into quad-plane staging images (plane P, arm j, component c ->
-// (P * n_arms + j) * 4 + c): goal = 4 planes, slots = 2*S planes (vfik_kernel.h).
-template <typename T>
-void pack_fields(const vfik_field* fields, int max_fields, const int32_t* counts, int n_arms, int S,
-                 std::vector<char>& goal, std::vector<char>& slots, std::vector<char>& fast, std::vector<int>& used,
-                 std::vector<char>& funnel, std::vector<int>& used_fast, std::vector<char>& has_funnel,
-                 std::vector<char>& uni, std::vector<char>& pair_state, std::vector<double>& pair_safe, std::vector<double>& pair_force,
-                 std::vector<unsigned char>& ord, std::vector<unsigned short>& rmap, std::vector<unsigned short>& smap) {
-    funnel.assign((size_t)6 * n_arms * 4 * sizeof(T), 0);  // aux block: funnel planes 0..2, hemisphere planes 3..5
-    goal.assign((size_t)4 * n_arms * 4 * sizeof(T), 0);
-    slots.assign((size_t)std::max(1, 2 * S) * n_arms * 4 * sizeof(T), 0);
-    // compact image: a decay repeller needs 6 of its slot's 8 scalars (x y z radius safe | force; the decay order is
-    // one number for the batch on the straight-line path and the type is known), so two slots share three quads:
-    // (x0 y0 z0 r0 | s0 f0 x1 y1 | z1 r1 s1 f1).  Slots of another type leave zeros (force 0): they force the general path.
-    fast.assign((size_t)3 * ((std::max(1, S) + 1) / 2) * n_arms * 4 * sizeof(T), 0);
-    // uniform image: when every decay repeller of the BATCH has the same safe distance and force (what the object feeder sends:
-    // 0.001 and -10, object_feeder:301-302,323,331) a slot is one quad (x y z radius) and the pair lives in the constants
-    uni.assign((size_t)std::max(1, S) * n_arms * 4 * sizeof(T), 0);
-    // (the force being the batch's, a slot an arm does not use cannot carry force 0 as in the other images: its radius is -inf)
-    for (size_t q4 = 0; q4 < (size_t)std::max(1, S) * n_arms; ++q4) put<T>(uni, q4 * 4 + 3, -std::numeric_limits<double>::infinity());
-    // order planes: byte (m % 16) of plane (m / 16) = the integer decay order of compact-image slot m; slots an arm does not use
-    // repeat the order of its last repeller (5 -- what the feeder sends, object_feeder:302,333 -- for an arm without any)
-    ord.assign((size_t)((std::max(1, S) + 15) / 16) * n_arms * 16, 5);
-    // vfik_move_fields' map: entry (m % 8) of plane (m / 8) = the general slot of compact-image slot m, MOVE_NONE behind the arm's last repeller
-    rmap.assign((size_t)((std::max(1, S) + 7) / 8) * n_arms * 8, vfik::MOVE_NONE);
-    // vfik_move_scene's maps, three of that layout in a row: entry k of class c (funnel, hemisphere, attractor behind the goal block) = the
-    // general slot of the arm's k-th primitive of that class, MOVE_NONE from the arm's count on
-    const size_t map_planes = (size_t)(std::max(1, S) + 7) / 8;
-    smap.assign(3 * map_planes * n_arms * 8, vfik::MOVE_NONE);
-    auto sm = [&](int cls, int j, int k) -> unsigned short& { return smap[((cls * map_planes + (size_t)(k >> 3)) * n_arms + j) * 8 + (k & 7)]; };
-    std::vector<int> order;
-    for (int j = 0; j < n_arms; ++j) {
-        const vfik_field* f = fields + (size_t)j * max_fields;
-        order.resize(counts[j]);
-        for (int k = 0; k < counts[j]; ++k) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return f[a].id < f[b].id; });
-        bool have_goal = false, have_funnel = false, have_hemi = false;
-        pair_state[j] = 0; pair_safe[j] = 0.0; pair_force[j] = 0.0;
-        int m = 0, mr = 0;  // general slots used; compact-image slots used (repellers only, packed densely)
-        int n_fun = 0, n_hem = 0, n_att = 0;   // funnels, hemispheres, attractors behind the goal block seen so far
-        auto gq = [&](int e) { return ((size_t)(e >> 2) * n_arms + j) * 4 + (e & 3); };
-        for (int k : order) {
-            const vfik_field& fd = f[k];
-            if (fd.type == VFIK_FIELD_NULL) continue;
-            if (fd.type == VFIK_FIELD_ATTRACTOR && !have_goal) {
-                have_goal = true;
-                for (int e = 0; e < 12; ++e) put<T>(goal, gq(e), fd.p[e]);
-                put<T>(goal, gq(12), 1.0);  // "goal present"
-                put<T>(goal, gq(13), fd.p[16]);
-                put<T>(goal, gq(14), fd.force);
-                continue;
-            }
-            const int ns = slots_of(fd.type);
-            auto at = [&](int slot, int e) { return ((size_t)(2 * (m + slot) + (e >> 2)) * n_arms + j) * 4 + (e & 3); };
-            for (int e = 0; e < 6; ++e) put<T>(slots, at(0, e), fd.p[e]);
-            put<T>(slots, at(0, 6), fd.force);
-            put<T>(slots, at(0, 7), (double)fd.type);
-            if (fd.type == VFIK_FIELD_FUNNEL) sm(vfik::SCENE_FUN, j, n_fun++) = (unsigned short)m;
-            if (fd.type == VFIK_FIELD_HEMISPHERE) sm(vfik::SCENE_HEM, j, n_hem++) = (unsigned short)m;
-            if (fd.type == VFIK_FIELD_ATTRACTOR) sm(vfik::SCENE_ATT, j, n_att++) = (unsigned short)m;
-            if (fd.type == VFIK_FIELD_FUNNEL && !have_funnel) {
-                // the straight-line path's funnel block (used only when this funnel is the arm's one non-repeller entry)
-                have_funnel = true;
-                const double blk[12] = {fd.p[0], fd.p[1], fd.p[2], fd.p[3], fd.p[4], fd.p[5], fd.p[6], fd.p[7], fd.p[8], fd.p[9], fd.force, 1.0};
-                for (int e = 0; e < 12; ++e) put<T>(funnel, ((size_t)(e >> 2) * n_arms + j) * 4 + (e & 3), blk[e]);
-            }
-            if (fd.type == VFIK_FIELD_HEMISPHERE && !have_hemi) {
-                // ... and the hemisphere block (object_feeder:344-353, ObstacleH: a surface with its normal): x y z nx | ny nz safe order | force present
-                have_hemi = true;
-                const double blk[12] = {fd.p[0], fd.p[1], fd.p[2], fd.p[3], fd.p[4], fd.p[5], fd.p[6], fd.p[7], fd.force, 1.0, 0.0, 0.0};
-                for (int e = 0; e < 12; ++e) put<T>(funnel, ((size_t)(3 + (e >> 2)) * n_arms + j) * 4 + (e & 3), blk[e]);
-            }
-            if (fd.type == VFIK_FIELD_REPELLER) {
-                for (int e = 0; e < 4; ++e) put<T>(uni, ((size_t)mr * n_arms + j) * 4 + e, fd.p[e]);
-                // (compared as the device will see them: rounded to the I/O type)
-                const double sv = (double)static_cast<T>(fd.p[4]), fv = (double)static_cast<T>(fd.force);
-                if (pair_state[j] == 0) { pair_state[j] = 1; pair_safe[j] = sv; pair_force[j] = fv; }
-                else if (pair_safe[j] != sv || pair_force[j] != fv) pair_state[j] = 2;
-                // (the uniform image's kernel clamps radius + safe at 0 -- how it disarms unused slots: a repeller with a NEGATIVE sum
-                // keeps the arm, hence the batch, on the compact image)
-                if ((double)static_cast<T>(fd.p[3]) + sv < 0.0) pair_state[j] = 2;
-                {   // (non-integer or large orders send the batch to the general path: the byte is not read then)
-                    const double o = fd.p[5];
-                    ord[((size_t)(mr >> 4) * n_arms + j) * 16 + (mr & 15)] = (o >= 0.0 && o < 128.0 && (double)(int)o == o) ? (unsigned char)(int)o : 0;
-                }
-                rmap[((size_t)(mr >> 3) * n_arms + j) * 8 + (mr & 7)] = (unsigned short)m;
-                const int pair = mr >> 1, half = mr & 1;
-                ++mr;
-                for (int i = 0; i < 6; ++i) {
-                    const int e = 6 * half + i;  // position in the pair's 12 scalars
-                    put<T>(fast, ((size_t)(3 * pair + (e >> 2)) * n_arms + j) * 4 + (e & 3), i < 5 ? fd.p[i] : fd.force);
-                }
-            }
-            for (int c = 1; c < ns; ++c) {
-                for (int e = 0; e < 6; ++e) {
-                    const int pi = 6 * c + e;
-                    put<T>(slots, at(c, e), pi < VFIK_MAX_PARAMS ? fd.p[pi] : 0.0);
-                }
-                put<T>(slots, at(c, 7), -1.0);
-            }
-            m += ns;
-        }
-        if (mr > 0) {   // the slots behind the last repeller repeat ITS order: a partly filled chunk adds no distinct order of its own
-            const size_t np = ord.size() / ((size_t)n_arms * 16);
-            const unsigned char last = ord[((size_t)((mr - 1) >> 4) * n_arms + j) * 16 + ((mr - 1) & 15)];
-            for (size_t ms = mr; ms < np * 16; ++ms) ord[((ms >> 4) * n_arms + j) * 16 + (ms & 15)] = last;
-        }
-        used[j] = m;
-        used_fast[j] = mr;
-        has_funnel[j] = (have_funnel || have_hemi) ? 1 : 0;
-    }
-}
-
-// Quad planes of the uniform repeller image: the empty plane 0, then one per slot -- and at least one chunk's worth of the I/O type
-// (Stage<T>::PRE), because the one-chunk body of the lean launches requests planes 1 ... PRE without looking at the slots in use.
-int uni_image_planes(const vfik_handle* h) {
-    const int pre = h->io_dtype == 32 ? vfik::Stage<float>::PRE : vfik::Stage<double>::PRE;
-    return std::max(std::max(1, h->max_slots), pre) + 1;
+    if (h->io_dtype == 32) vfik::put<float>(buf, idx, v); else vfik::put<double>(buf, idx, v);
 }
 
 void fill_kargs(const vfik_handle* h, const vfik_io* io, vfik::KArgs& a) {
     std::memset(&a, 0, sizeof a);
     a.B = h->B;
     a.Bpad = h->Bpad;
-    a.slots_used = h->slots_used;
-    a.fast_order = h->fast_order;
+    a.slots_used = h->scene.slots_used;
+    a.fast_order = h->scene.fast_order;
     a.flags = h->params.flags;
     a.tool_stride = h->tool_per_arm ? h->Bpad : 0;
     a.plain = (h->plain && !h->tool_per_arm && !h->d_wts) ? h->plain : 0;   // (1 ... 4: the PLAIN kernels, with the batch's shared tool / shared IK weights as vfik_kernel.h says)
@@ -408,16 +260,16 @@ void fill_kargs(const vfik_handle* h, const vfik_io* io, vfik::KArgs& a) {
     a.n_simd = h->n_simd;
     a.arena = h->d_arena;
     a.funnel = h->d_funnel;
-    a.slots_used_fast = h->slots_used_fast;
-    a.has_funnel = h->any_funnel;
+    a.slots_used_fast = h->scene.slots_used_fast;
+    a.has_funnel = h->scene.any_funnel;
     a.waves2 = h->waves2;
-    a.one5 = h->one5;
-    a.uni = h->uni_ok && h->uni_allowed;
-    a.uni_planes = 3 * ((std::max(1, h->max_slots) + 1) / 2);
+    a.one5 = h->scene.one_chunk();
+    a.uni = h->scene.uniform(h->knobs);
+    a.uni_planes = vfik::image_shape(vfik::IMG_COMPACT, h->max_slots, h->io_dtype).planes;
     a.stamps = h->d_stamps;
     a.kc = h->d_kconst;
     a.orders = h->d_orders;
-    a.mixed = h->mixed;
+    a.mixed = h->scene.mixed_orders();
     a.dhp = a.plain ? h->dhp : 0;
 }
 
@@ -445,39 +297,6 @@ int upload_kconst(vfik_handle* h) {
     h->plain = plain;
     h->dhp = h->dhp_allowed ? dhp : 0;
     return VFIK_OK;
-}
-
-// which arms qualify for the kernel's straight-line repeller path
-// (-1: no repeller; n >= 0: every repeller has integer order n; -3: integer orders that differ; -2: the general path)
-int classify_arm(const vfik_field* f, int count) {
-    int order = -1;
-    bool goal = false, funnel = false, hemi = false, mixed = false;
-    for (int k = 0; k < count; ++k) {
-        const vfik_field& fd = f[k];
-        if (fd.type == VFIK_FIELD_NULL) continue;
-        if (fd.type == VFIK_FIELD_ATTRACTOR && !goal) { goal = true; continue; }
-        if (fd.type == VFIK_FIELD_FUNNEL && !funnel) {
-            // one funnel attractor with small integer decay orders (object_feeder:277,279 sends 10 and 2): the straight-line
-            // path evaluates it from its own block
-            funnel = true;
-            const double oa = fd.p[7], od = fd.p[9];
-            if (!((double)(int)oa == oa) || oa < 0 || oa >= 128 || !((double)(int)od == od) || od < 0 || od >= 128) return -2;
-            continue;
-        }
-        if (fd.type == VFIK_FIELD_HEMISPHERE && !hemi) {  // one hemisphere repeller with a small integer decay order (object_feeder:353 sends 5)
-            hemi = true;
-            const double oh = fd.p[7];
-            if (!((double)(int)oh == oh) || oh < 0 || oh >= 128) return -2;
-            continue;
-        }
-        if (fd.type != VFIK_FIELD_REPELLER) return -2;
-        const double o = fd.p[5];
-        const int n = (int)o;
-        if (!((double)n == o) || n < 0 || n >= 128) return -2;
-        if (order >= 0 && n != order) mixed = true;
-        order = n;
-    }
-    return mixed ? -3 : order;
 }
 
 int check_handle(const vfik_handle* h) {
@@ -526,9 +345,10 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
     }
     if (const char* e = std::getenv("VFIK_SUB8_MAX_BATCH")) h->sub8_max_batch = h->sub8_max_batch_full = h->sub8_max_batch_ns = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("VFIK_TWO_WAVES")) h->waves2 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("VFIK_UNIFORM_IMAGE")) h->uni_allowed = std::atoi(e) != 0;
-    if (const char* e = std::getenv("VFIK_ONE_CHUNK")) h->one_chunk_allowed = std::atoi(e) != 0;
-    if (const char* e = std::getenv("VFIK_MIXED_ORDERS")) h->mixed_allowed = std::atoi(e) != 0;
+    h->knobs.io_dtype = io_dtype; h->knobs.n = n_joints;
+    if (const char* e = std::getenv("VFIK_UNIFORM_IMAGE")) h->knobs.uni_allowed = std::atoi(e) != 0;
+    if (const char* e = std::getenv("VFIK_ONE_CHUNK")) h->knobs.one_chunk_allowed = std::atoi(e) != 0;
+    if (const char* e = std::getenv("VFIK_MIXED_ORDERS")) h->knobs.mixed_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_DH_PATTERN")) h->dhp_allowed = std::atoi(e) != 0;
     if (const char* e = std::getenv("VFIK_ZERO_COPY_MAX")) h->zero_copy_max = (size_t)std::max(0L, std::atol(e));
     auto bail = [&](const char* what) { if (g_err.empty()) fail(VFIK_E_HIP, "%s failed", what); vfik_destroy(h); return (vfik_handle*)nullptr; };
@@ -540,20 +360,20 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
     }
     const size_t B = batch;
     h->Bpad = (batch + 63) / 64 * 64;
-    const size_t quad_plane = (size_t)h->Bpad * 4 * h->esz;
+    // (the images' sizes: vfik_scene.h, image_shape)
+    auto image_sz = [&](vfik::Image img) { return vfik::image_bytes(img, max_slots, io_dtype, (size_t)h->Bpad); };
     {   // the state a lean launch reads, in one allocation whose layout the kernel can derive (vfik_kernel.h: arena layout)
-        const size_t sz_goal = (4 + 6) * quad_plane;   // goal block + aux block (funnel, hemisphere)
+        const size_t sz_goal = image_sz(vfik::IMG_GOAL) + image_sz(vfik::IMG_AUX);   // goal block + aux block (funnel, hemisphere)
         const size_t sz_kc = VFIK_KCONST_SLOT(vfik::kconst_bytes(n_joints));   // (+ slack inside: the kinematics block is copied in whole 1-KiB rows)
         const size_t sz_lv = (size_t)((n_joints + 4) / 4) * h->Bpad * 4 * sizeof(float);
-        const size_t sz_sf = (std::max<size_t>(1, (size_t)max_slots) + 1) / 2 * 3 * quad_plane;
-        // uniform image: an EMPTY plane, then one quad plane per slot -- never fewer than one chunk's (uni_image_planes: the one-chunk body reads them all)
-        const size_t sz_su = (size_t)uni_image_planes(h) * quad_plane;
-        const size_t sz_sl = std::max<size_t>(1, (size_t)max_slots) * 2 * quad_plane;  // >= 1 slot: the prefetch reads slot 0
-        const size_t sz_or = (std::max<size_t>(1, (size_t)max_slots) + 15) / 16 * (size_t)h->Bpad * 16;   // order planes (zeros: order 0, force 0)
+        const size_t sz_sf = image_sz(vfik::IMG_COMPACT);
+        const size_t sz_su = image_sz(vfik::IMG_UNI);   // (never fewer planes than one chunk's: the one-chunk body reads them all)
+        const size_t sz_sl = image_sz(vfik::IMG_SLOTS);
+        const size_t sz_or = image_sz(vfik::IMG_ORDERS);   // (zeros: order 0, force 0)
         if (dev_alloc(h, &h->d_arena, sz_goal + sz_kc + sz_lv + sz_sf + sz_su + sz_sl + sz_or, true)) return bail("alloc state arena");
         char* a0 = static_cast<char*>(h->d_arena);
         h->d_goal = a0;
-        h->d_funnel = a0 + 4 * quad_plane;
+        h->d_funnel = a0 + image_sz(vfik::IMG_GOAL);
         h->d_kconst = a0 + sz_goal;
         h->d_lastvec = reinterpret_cast<float*>(a0 + sz_goal + sz_kc);
         h->d_slots_fast = a0 + sz_goal + sz_kc + sz_lv;
@@ -562,29 +382,23 @@ vfik_handle* vfik_create(int device, int io_dtype, int n_joints, int max_slots, 
         h->d_orders = a0 + sz_goal + sz_kc + sz_lv + sz_sf + sz_su + sz_sl;
     }
     {   // vfik_move_fields' map, every entry MOVE_NONE until field sets arrive
-        const size_t sz_map = (std::max<size_t>(1, (size_t)max_slots) + 7) / 8 * (size_t)h->Bpad * 16;
+        const size_t sz_map = image_sz(vfik::IMG_REPMAP), sz_smap = image_sz(vfik::IMG_SCENEMAPS);
         if (dev_alloc(h, (void**)&h->d_repmap, sz_map, false)) return bail("alloc repeller map");
         if (hipMemsetAsync(h->d_repmap, 0xFF, sz_map, h->stream) != hipSuccess) return bail("init repeller map");
-        if (dev_alloc(h, (void**)&h->d_scenemap, 3 * sz_map, false)) return bail("alloc scene maps");
-        if (hipMemsetAsync(h->d_scenemap, 0xFF, 3 * sz_map, h->stream) != hipSuccess) return bail("init scene maps");
+        if (dev_alloc(h, (void**)&h->d_scenemap, sz_smap, false)) return bail("alloc scene maps");
+        if (hipMemsetAsync(h->d_scenemap, 0xFF, sz_smap, h->stream) != hipSuccess) return bail("init scene maps");
     }
     {   // the uniform image starts out with every slot unused (radius -inf), like the zeros (force 0) of the other two images
         std::vector<char> plane((size_t)h->Bpad * 4 * h->esz, 0);
         for (int b = 0; b < h->Bpad; ++b) put_io(h, plane, (size_t)b * 4 + 3, -std::numeric_limits<double>::infinity());
         // (plane 0 stays like this for good: the slot every out-of-range quad reads; so do the planes past max_slots, which no call writes)
-        for (int sidx = 0; sidx < uni_image_planes(h); ++sidx)
+        for (int sidx = 0; sidx < vfik::image_shape(vfik::IMG_UNI, max_slots, io_dtype).planes; ++sidx)
             if (hipMemcpyAsync(static_cast<char*>(h->d_slots_uni) + (size_t)sidx * plane.size(), plane.data(), plane.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess)
                 return bail("init uniform image");
         if (hipStreamSynchronize(h->stream) != hipSuccess) return bail("init uniform image");
     }
     if (dev_alloc(h, (void**)&h->d_mixw, 16 * sizeof(double), true)) return bail("alloc mixw");
-    h->slots_per_arm.assign(B, 0);
-    h->fast_slots_per_arm.assign(B, 0);
-    h->arm_has_funnel.assign(B, 0);
-    h->arm_pair_state.assign(B, 0);
-    h->arm_safe.assign(B, 0.0);
-    h->arm_force.assign(B, 0.0);
-    h->arm_order.assign(B, -1);
+    h->arms.assign(B, vfik::ArmScene{});
 #ifdef VFIK_STAMPS
     if (dev_alloc(h, (void**)&h->d_stamps, ((B + 63) / 64) * 10 * sizeof(unsigned long long), true)) return bail("alloc stamps");
 #endif
@@ -817,88 +631,50 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
     // validate everything before touching device state
     for (int j = 0; j < n_arms; ++j) {
         if (counts[j] < 0 || counts[j] > max_fields) return fail(VFIK_E_ARG, "arm %d: count %d outside [0, %d]", first_arm + j, counts[j], max_fields);
-        int need = 0;
-        bool goal = false;
-        for (int k = 0; k < counts[j]; ++k) {
-            const vfik_field& fd = fields[(size_t)j * max_fields + k];
-            const int ns = slots_of(fd.type);
-            if (ns < 0) return fail(VFIK_E_ARG, "arm %d field %d: unknown type %d", first_arm + j, fd.id, fd.type);
-            if (fd.type == VFIK_FIELD_ATTRACTOR && !goal) { goal = true; continue; }
-            need += ns;
-        }
+        const vfik_field* f = fields + (size_t)j * max_fields;
+        int bad = 0;
+        const int need = vfik::slots_needed(f, counts[j], &bad);
+        if (need < 0) return fail(VFIK_E_ARG, "arm %d field %d: unknown type %d", first_arm + j, f[bad].id, f[bad].type);
         if (need > h->max_slots) return fail(VFIK_E_ARG, "arm %d needs %d slots, handle capacity is %d", first_arm + j, need, h->max_slots);
     }
     HIP_TRY(hipSetDevice(h->device));
-    std::vector<char> goal, slots, fast, funnel, hasf(n_arms), uni, pstate(n_arms);
-    std::vector<double> psafe(n_arms), pforce(n_arms);
-    std::vector<int> used(n_arms), used_fast(n_arms);
-    std::vector<unsigned char> ord;
-    std::vector<unsigned short> rmap, smap;
+    // pack (vfik_scene.h): the staging images of the call's arms and what each arm's set holds
+    vfik::FieldImages im;
+    std::vector<vfik::ArmScene> packed(n_arms);
     const int S = h->max_slots;
-    if (h->io_dtype == 32) pack_fields<float>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap, smap);
-    else pack_fields<double>(fields, max_fields, counts, n_arms, S, goal, slots, fast, used, funnel, used_fast, hasf, uni, pstate, psafe, pforce, ord, rmap, smap);
+    if (h->io_dtype == 32) vfik::pack_fields<float>(fields, max_fields, counts, n_arms, S, im, packed.data());
+    else vfik::pack_fields<double>(fields, max_fields, counts, n_arms, S, im, packed.data());
+    auto planes = [&](vfik::Image img) { return (size_t)vfik::staged_planes(img, S, h->io_dtype); };
     const size_t qb = 4 * h->esz, w = (size_t)n_arms * qb, pitch = (size_t)h->Bpad * qb;
+    const size_t gp = planes(vfik::IMG_GOAL) - 1;   // the goal block's last plane is copied apart
     char* dg = static_cast<char*>(h->d_goal) + (size_t)first_arm * qb;
-    HIP_TRY(hipMemcpy2DAsync(dg, pitch, goal.data(), w, w, 3, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(dg, pitch, im.goal.data(), w, w, gp, hipMemcpyHostToDevice, h->stream));
     // plane 3 = (present, slow-down, force, speedScale): the 4th component belongs to vfik_set_speed_scale
-    HIP_TRY(hipMemcpy2DAsync(dg + 3 * pitch, qb, goal.data() + 3 * w, qb, 3 * h->esz, n_arms, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpy2DAsync(static_cast<char*>(h->d_funnel) + (size_t)first_arm * qb, pitch, funnel.data(), w, w, 6, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(dg + gp * pitch, qb, im.goal.data() + gp * w, qb, 3 * h->esz, n_arms, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(static_cast<char*>(h->d_funnel) + (size_t)first_arm * qb, pitch, im.aux.data(), w, w, planes(vfik::IMG_AUX), hipMemcpyHostToDevice, h->stream));
     if (S > 0) {
+        const size_t w16 = (size_t)n_arms * 16, pitch16 = (size_t)h->Bpad * 16;   // order planes and maps: 16 bytes per arm and plane
         char* ds = static_cast<char*>(h->d_slots) + (size_t)first_arm * qb;
-        HIP_TRY(hipMemcpy2DAsync(ds, pitch, slots.data(), w, w, (size_t)S * 2, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(ds, pitch, im.slots.data(), w, w, planes(vfik::IMG_SLOTS), hipMemcpyHostToDevice, h->stream));
         char* df = static_cast<char*>(h->d_slots_fast) + (size_t)first_arm * qb;
-        HIP_TRY(hipMemcpy2DAsync(df, pitch, fast.data(), w, w, (size_t)((S + 1) / 2) * 3, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(df, pitch, im.compact.data(), w, w, planes(vfik::IMG_COMPACT), hipMemcpyHostToDevice, h->stream));
         char* du = static_cast<char*>(h->d_slots_uni) + pitch + (size_t)first_arm * qb;   // (slot m in plane m + 1)
-        HIP_TRY(hipMemcpy2DAsync(du, pitch, uni.data(), w, w, (size_t)S, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(du, pitch, im.uni.data(), w, w, planes(vfik::IMG_UNI), hipMemcpyHostToDevice, h->stream));
         char* dor = static_cast<char*>(h->d_orders) + (size_t)first_arm * 16;
-        HIP_TRY(hipMemcpy2DAsync(dor, (size_t)h->Bpad * 16, ord.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 15) / 16, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(dor, pitch16, im.orders.data(), w16, w16, planes(vfik::IMG_ORDERS), hipMemcpyHostToDevice, h->stream));
         char* dm = reinterpret_cast<char*>(h->d_repmap) + (size_t)first_arm * 16;
-        HIP_TRY(hipMemcpy2DAsync(dm, (size_t)h->Bpad * 16, rmap.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, (size_t)(S + 7) / 8, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(dm, pitch16, im.repmap.data(), w16, w16, planes(vfik::IMG_REPMAP), hipMemcpyHostToDevice, h->stream));
         char* dsm = reinterpret_cast<char*>(h->d_scenemap) + (size_t)first_arm * 16;   // (the three maps' planes follow each other on both sides)
-        HIP_TRY(hipMemcpy2DAsync(dsm, (size_t)h->Bpad * 16, smap.data(), (size_t)n_arms * 16, (size_t)n_arms * 16, 3 * ((size_t)(S + 7) / 8), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(dsm, pitch16, im.scenemaps.data(), w16, w16, planes(vfik::IMG_SCENEMAPS), hipMemcpyHostToDevice, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->fields_set = true;
-    for (int j = 0; j < n_arms; ++j) {
-        h->slots_per_arm[first_arm + j] = used[j];
-        h->fast_slots_per_arm[first_arm + j] = used_fast[j];
-        h->arm_has_funnel[first_arm + j] = hasf[j];
-        h->arm_order[first_arm + j] = classify_arm(fields + (size_t)j * max_fields, counts[j]);
-        h->arm_pair_state[first_arm + j] = pstate[j];
-        h->arm_safe[first_arm + j] = psafe[j];
-        h->arm_force[first_arm + j] = pforce[j];
-    }
-    h->slots_used = *std::max_element(h->slots_per_arm.begin(), h->slots_per_arm.end());
-    h->slots_used_fast = *std::max_element(h->fast_slots_per_arm.begin(), h->fast_slots_per_arm.end());
-    h->any_funnel = 0;
-    for (char f : h->arm_has_funnel) h->any_funnel |= f;
-    // One integer order for every decay repeller of the batch: the straight-line path with that order as a launch constant.  Integer
-    // orders that differ -- within an arm (-3) or between arms: the straight-line path still, reading the order planes (`mixed`).
-    int fo = -1;
-    bool general = false, mixed = false;
-    for (int o : h->arm_order) {
-        if (o == -2) { general = true; break; }
-        if (o == -3 || (o >= 0 && fo >= 0 && o != fo)) mixed = true;
-        if (o >= 0) fo = o;
-    }
-    if (!h->mixed_allowed && mixed) general = true;
-    h->mixed = (!general && mixed) ? 1 : 0;
-    h->fast_order = general ? -1 : (fo < 0 ? 5 : fo);   // (no repeller anywhere: any order >= 1 will do -- see the uniform image below)
-    // one (safe distance, force) for every decay repeller of the batch?  Then the pair goes into the device constants and the lean
-    // launches read the uniform image.
-    // (not with decay order 0: the uniform image disarms an unused slot through its magnitude, ((radius + safe) / D)^order = 0^order,
-    // which is 1 for order 0)
-    bool uni_ok = !general && h->fast_order != 0, have = false;
-    double us = 0.0, uf = 0.0;
-    for (int b = 0; b < h->B && uni_ok; ++b) {
-        const char st = h->arm_pair_state[b];
-        if (st == 0) continue;
-        if (st == 2) { uni_ok = false; break; }
-        if (!have) { have = true; us = h->arm_safe[b]; uf = h->arm_force[b]; }
-        else if (h->arm_safe[b] != us || h->arm_force[b] != uf) uni_ok = false;
-    }
-    if (uni_ok && have && (us != h->uni_safe || uf != h->uni_force)) {
-        h->uni_safe = us; h->uni_force = uf;
+    std::copy(packed.begin(), packed.end(), h->arms.begin() + first_arm);
+    // what the batch's launches take from now on: decided over ALL arms (vfik_scene.h: plan_scene)
+    h->scene = vfik::plan_scene(h->arms.data(), h->B, h->knobs);
+    // a uniform pair other than the one in the device constants: there it goes
+    if (h->scene.uni_ok && h->scene.have_pair && (h->scene.safe != h->uni_safe || h->scene.force != h->uni_force)) {
+        h->uni_safe = h->scene.safe; h->uni_force = h->scene.force;
         if (h->chain_set) {  // (a chain set later writes the pair with the rest of the constants: upload_kconst)
             char* kc = static_cast<char*>(h->d_kconst);
             HIP_TRY(hipMemcpyAsync(kc + VFIK_KCONST_REP_SAFE_OFF(h->n), &h->uni_safe, sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -906,14 +682,6 @@ int vfik_set_fields(vfik_handle* h, int first_arm, int n_arms, const vfik_field*
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
     }
-    h->uni_ok = uni_ok ? 1 : 0;
-    // One chunk of order-5 repellers on the uniform image (what the feeder sends: object_feeder:302,333): the lean float launches of chains
-    // of up to 7 joints take the body compiled for exactly that (cycle_kernel_s, ONE5).  It reads planes 1 ... PRE of the image whatever
-    // the slots in use: the image owns them (uni_image_planes), and every plane at or beyond an arm's count is empty -- the copy above
-    // rewrites all max_slots planes of the arms it names (pack_fields: radius -inf past the arm's last repeller), the planes beyond
-    // max_slots keep the -inf of vfik_create, and vfik_move_fields writes the rows of existing repellers alone.
-    h->one5 = (h->one_chunk_allowed && uni_ok && h->uni_allowed && h->fast_order == 5 && h->io_dtype == 32 && h->n <= 7 &&
-               h->slots_used_fast <= vfik::Stage<float>::PRE) ? 1 : 0;
     return VFIK_OK;
 }
 
@@ -1013,7 +781,7 @@ static int scene_launch(vfik_handle* h, int first_arm, int n_arms, const vfik_sc
     s.n_fun = s.fun6 ? mv.n_fun : 0;
     s.n_hem = s.hem6 ? mv.n_hem : 0;
     s.n_att = s.att16 ? mv.n_att : 0;
-    s.map_planes = (std::max(1, h->max_slots) + 7) / 8;
+    s.map_planes = vfik::image_shape(vfik::IMG_REPMAP, h->max_slots, h->io_dtype).planes;
     hipError_t e = vfik::launch_move_scene(h->io_dtype, s, h->stream);
     if (e != hipSuccess) return fail(VFIK_E_HIP, "scene move launch: %s", hipGetErrorString(e));
     return VFIK_OK;
@@ -1895,7 +1663,7 @@ int vfik_probe_field(vfik_handle* h, const void* pose, void* v6) {
     HIP_TRY(hipSetDevice(h->device));
     const double rs = h->params.rot_slowdown;
     const double cos_slow = rs > 0.0 && rs < 3.14159265358979323846 ? std::cos(rs) : -2.0;  // as kconst_fill
-    hipError_t e = vfik::launch_probe(h->io_dtype, pose, h->d_goal, h->d_slots, h->B, h->Bpad, h->slots_used, rs, cos_slow, v6, h->stream);
+    hipError_t e = vfik::launch_probe(h->io_dtype, pose, h->d_goal, h->d_slots, h->B, h->Bpad, h->scene.slots_used, rs, cos_slow, v6, h->stream);
     if (e != hipSuccess) return fail(VFIK_E_HIP, "probe launch: %s", hipGetErrorString(e));
     return VFIK_OK;
 }
@@ -2011,32 +1779,19 @@ int vfik_debug_read_stamps(vfik_handle* h, unsigned long long* dst) {
 }
 #endif
 
-int vfik_slots_in_use(vfik_handle* h) { return h ? h->slots_used : VFIK_E_ARG; }
+int vfik_slots_in_use(vfik_handle* h) { return h ? h->scene.slots_used : VFIK_E_ARG; }
 
-int vfik_field_path(vfik_handle* h) {
-    if (!h) return VFIK_E_ARG;
-    if (h->fast_order < 0) return 0;
-    return h->any_funnel ? 2 : 1;
-}
+int vfik_field_path(vfik_handle* h) { return h ? h->scene.field_path() : VFIK_E_ARG; }
 
 long vfik_launch_epoch(vfik_handle* h) { return h ? h->epoch : (long)VFIK_E_ARG; }
 
 int vfik_dh_pattern(vfik_handle* h) { return h ? ((h->plain && !h->tool_per_arm && !h->d_wts) ? h->dhp : 0) : VFIK_E_ARG; }
 
-int vfik_mixed_orders(vfik_handle* h) {
-    if (!h) return VFIK_E_ARG;
-    return (h->fast_order >= 0 && h->mixed) ? 1 : 0;
-}
+int vfik_mixed_orders(vfik_handle* h) { return h ? h->scene.mixed_orders() : VFIK_E_ARG; }
 
-int vfik_uniform_repellers(vfik_handle* h) {
-    if (!h) return VFIK_E_ARG;
-    return (h->fast_order >= 0 && h->uni_ok && h->uni_allowed) ? 1 : 0;
-}
+int vfik_uniform_repellers(vfik_handle* h) { return h ? h->scene.uniform(h->knobs) : VFIK_E_ARG; }
 
-int vfik_one_chunk(vfik_handle* h) {
-    if (!h) return VFIK_E_ARG;
-    return (h->fast_order >= 0 && h->one5) ? 1 : 0;
-}
+int vfik_one_chunk(vfik_handle* h) { return h ? h->scene.one_chunk() : VFIK_E_ARG; }
 
 int vfik_set_small_batch_kernel(vfik_handle* h, int max_batch) {
     if (check_handle(h)) return VFIK_E_ARG;

@@ -59,7 +59,7 @@ struct KConst {
     // (That rot_slow lies in (0, pi/8) -- the short arctangent of rot_axis_angle -- the kernels read off cos_slow > cos(pi/8).)
     double tail_c, tail_s, tail_e;  // trailing z-screw of the last fixed transform
     // safe distance of every decay repeller of the batch when they all share one (and one force, dh[0].pad): the uniform repeller
-    // image of the straight-line path then carries (x y z radius) per slot only (vfik_abi.cpp: pack_fields, vfik_set_fields)
+    // image of the straight-line path then carries (x y z radius) per slot only (vfik_scene.h: pack_fields, plan_scene)
     double rep_safe;
     // ---- everything else: read through the scalar cache.  Ordered by use on the lean paths: the first members share the 1-KiB
     // rows that every wave copies to LDS for the kinematics block, so the L2 has them by the time the scalar loads ask -- with
@@ -167,7 +167,7 @@ struct KArgs {
     const void* q;
     const void* goal;
     const void* slots;
-    const void* slots_fast;  // compact repeller image of the straight-line path: 3 quad planes per pair of slots (vfik_abi.cpp, pack_fields)
+    const void* slots_fast;  // compact repeller image of the straight-line path: 3 quad planes per pair of slots (vfik_scene.h, pack_fields)
     const void* tool;
     const void* null_control;
     const void* ext;
