@@ -517,6 +517,47 @@ int vfik_script(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o);
 /* The same with HOST pointers (io and o alike), poll_checks and *checks_run as vfik_follow_host. */
 int vfik_script_host(vfik_handle* h, const vfik_io* io, const vfik_script_opts* o, int poll_checks, int* checks_run);
 
+/* Stalled arms.  The reference has two outcomes for a timed move: the arm arrived, or it is still under way when the time is up (gotoFrame,
+ * set_ref_js: handlers.py:346-387, 544-576).  For a batch that keeps ONE arm that will never arrive -- a goal out of reach, a posture beyond a
+ * limit, no goal block -- in pending[k] until the time-out, and the early exit of the host forms never fires.  The stall rule is a third outcome,
+ * decided on the device inside the checks of all five timed moves.  It is state of the HANDLE, off by default; with the rule off nothing changes:
+ * the same check kernels, the same results.
+ *   measure      in double on the io-typed values, like the arrival rules.  Cartesian rule (vfik_goto, vfik_follow, a script's frame steps):
+ *                d = the distance, a = the angle in radians exactly as the arrival rule forms it, (double)deg * M_PI / 180.0; both NaN for
+ *                an arm without a goal block.  Joint rule (vfik_goto_js, vfik_follow_js, a script's posture steps): e = max_i |(double)ref_i -
+ *                (double)q_i| over the joints whose precision in force (prec or via_prec) is finite, 0 without such a joint, NaN if any
+ *                of them is NaN; ref is the value the caller sent, as in the arrival rule.
+ *   state        per arm best[2] (double) and count (int32), the handle's.  The pass in front of block 0 sets best = +inf, count = 0 and
+ *                stalled[b] = -1 for EVERY arm; the check that advances an arm to its next list item or script step resets best and count.
+ *   after block k    for every arm that ran the block, is under way and did not arrive at this check: progress means
+ *                d < best_d - eps_pos || a < best_a - eps_rot     (joint rule: e < best_e - eps_js),
+ *                all compares strict, so NaN is never progress.  On progress best becomes the componentwise minimum and count = 0; else
+ *                count += 1, and when count == patience the arm is stalled: stalled[b] = (k + 1) * stride - 1.  Arrival goes first: an arm that
+ *                arrives at the check where count would reach patience arrives.  An arm without a goal block, or with a NaN reference
+ *                row, stalls at check patience - 1.
+ *   a stalled arm  has left the state machine: no rule of any kind is applied to it again, arrived, reached and next keep their values, it
+ *                is not counted in pending[k], and with stop = 1 the gate of the next block is 0 for it -- its q, its output rows and its
+ *                nullspace memory stay and its trace rows repeat, exactly as for an arm held at arrival.  With stop = 0 it keeps taking
+ *                cycles unchecked (diff and way_traj are still written for it).  The gate: in && !(hold && next == L) && !(stop && stalled).
+ *   stalled      NULL: an array of the handle, read with vfik_stalled_host; else a DEVICE pointer to int32 [B] that every later timed move
+ *                writes.  Either way it holds the outcome of the LAST timed move.
+ * vfik_set_stall_rule(h, NULL) switches the rule off.  The call allocates the handle's state (never under capture: VFIK_E_STATE), synchronises
+ * the handle's stream, moves no launch decision and leaves vfik_launch_epoch alone; a timed move's blocks run the cycle kernels they ran
+ * without a rule (with stop = 1 always under the handle's gate, as with hold).  VFIK_E_ARG: patience < 1, stop other than 0 / 1, an eps negative, NaN or infinite,
+ * a `stalled` that is no int32-aligned device pointer; the rule in force stays.
+ * vfik_stalled_host copies stalled[B] of the last timed move to the host and synchronises; VFIK_E_STATE without a rule, and while the
+ * handle's stream is being captured (nothing is enqueued, the capture goes on). */
+typedef struct vfik_stall_rule {
+    int32_t patience;         /* >= 1: consecutive checks without progress */
+    int32_t stop;             /* 1: a stalled arm takes no further cycle */
+    double  eps_pos, eps_rot; /* metres, radians; finite, >= 0 */
+    double  eps_js;           /* radians (metres: prismatic); finite, >= 0 */
+    int32_t* stalled;         /* out [B] DEVICE pointer, or NULL: the handle's own array */
+} vfik_stall_rule;
+size_t vfik_stall_rule_size(void);
+int vfik_set_stall_rule(vfik_handle* h, const vfik_stall_rule* r);   /* NULL: off (the default) */
+int vfik_stalled_host(vfik_handle* h, int32_t* out /* host [B] */);  /* synchronises; the last timed move's */
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

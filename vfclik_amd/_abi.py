@@ -94,6 +94,12 @@ class ScriptOpts(C.Structure):
                 ("diff", C.c_void_p), ("way_traj", C.c_void_p)]
 
 
+class StallRule(C.Structure):
+    """``struct vfik_stall_rule`` (include/vfik.h: vfik_set_stall_rule)."""
+    _fields_ = [("patience", C.c_int32), ("stop", C.c_int32), ("eps_pos", C.c_double), ("eps_rot", C.c_double), ("eps_js", C.c_double),
+                ("stalled", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

@@ -105,6 +105,13 @@ struct vfik_handle {
     int* d_follow_len = nullptr;   // vfik_follow (which runs on vfik_goto's buffers): every arm's path length
     void* d_js_ref = nullptr;      // vfik_follow_js, vfik_script: the reference row [B][n] their blocks read as io->q_ref (nobody else reads it)
     void* d_script_mixw = nullptr; // vfik_script: the 2 quad planes its blocks read as the per-arm mixer weights (d_mixw_arm's layout; nobody else reads them)
+    // vfik_set_stall_rule: the rule the checks of every timed move evaluate (stall_on), its per-arm state best[B][2] and count[B], and
+    // stalled[B] where the caller names no array of its own
+    bool stall_on = false;
+    vfik_stall_rule stall{};
+    double* d_stall_best = nullptr;
+    int* d_stall_count = nullptr;
+    int* d_stall_own = nullptr;
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -426,7 +433,7 @@ void vfik_destroy(vfik_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw};
+                    h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw, h->d_stall_best, h->d_stall_count, h->d_stall_own};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -1214,7 +1221,7 @@ int timed_check(vfik_handle* h, TimedMove& m) {
     if (!io->q_lo != !io->q_hi) return fail(VFIK_E_ARG, "io->q_lo and io->q_hi come together (both or neither)");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
     m.n_checks = m.n_cycles / m.stride;
-    m.gated = m.hold || io->active || m.list;
+    m.gated = m.hold || io->active || m.list || (h->stall_on && h->stall.stop);   // (a stalled arm that stops is gated like a held one)
     return VFIK_OK;
 }
 
@@ -1368,6 +1375,16 @@ int timed_launch_check(vfik_handle* h, const TimedMove& m, int k, const vfik::Bl
     g.diff = m.x[vfik::X_DIFF];
     std::memcpy(g.prec, m.prec, sizeof g.prec);   // (all of both: the Cartesian pair sits in [0], [1] whatever n is)
     std::memcpy(g.via_prec, m.via_prec, sizeof g.via_prec);
+    // the handle's stall rule: the STALL builds of the same checks, the rule and its state as their second argument
+    vfik::StallArgs sa{};
+    const vfik::StallArgs* st = nullptr;
+    if (h->stall_on) {
+        sa.best = h->d_stall_best; sa.count = h->d_stall_count;
+        sa.stalled = h->stall.stalled ? h->stall.stalled : h->d_stall_own;
+        sa.patience = h->stall.patience; sa.stop = h->stall.stop;
+        sa.eps_pos = h->stall.eps_pos; sa.eps_rot = h->stall.eps_rot; sa.eps_js = h->stall.eps_js;
+        st = &sa;
+    }
     if (m.script) {
         vfik::ScriptArgs s{};
         s.c = g;
@@ -1379,10 +1396,10 @@ int timed_launch_check(vfik_handle* h, const TimedMove& m, int k, const vfik::Bl
         std::memcpy(s.mix, m.mix, sizeof s.mix);
         std::memcpy(s.js_prec, m.js_prec, sizeof s.js_prec);
         std::memcpy(s.js_via_prec, m.js_via_prec, sizeof s.js_via_prec);
-        const hipError_t es = vfik::launch_script(h->io_dtype, s, h->stream);
+        const hipError_t es = vfik::launch_script(h->io_dtype, s, h->stream, st);
         return es != hipSuccess ? fail(VFIK_E_HIP, "script launch: %s", hipGetErrorString(es)) : (int)VFIK_OK;
     }
-    hipError_t e = vfik::launch_check(h->io_dtype, m.joint, m.list, g, h->stream);
+    hipError_t e = vfik::launch_check(h->io_dtype, m.joint, m.list, g, h->stream, st);
     if (e != hipSuccess) {
         static const char* const name[2][2] = {{"arrive", "follow"}, {"arrive_js", "follow_js"}};
         return fail(VFIK_E_HIP, "%s launch: %s", name[m.joint][m.list], hipGetErrorString(e));
@@ -1544,6 +1561,45 @@ int vfik_script_host(vfik_handle* h, const vfik_io* io, const vfik_script_opts* 
     TimedMove m;
     const int rc = script_check(h, io, o, m);
     return rc != VFIK_OK ? rc : timed_run_host(h, m, poll_checks, checks_run);
+}
+
+// ---- the stall rule of the timed moves: state of the handle that their checks alone read (timed_launch_check) ----
+size_t vfik_stall_rule_size(void) { return sizeof(vfik_stall_rule); }
+
+int vfik_set_stall_rule(vfik_handle* h, const vfik_stall_rule* r) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!r) { h->stall_on = false; return VFIK_OK; }
+    if (r->patience < 1) return fail(VFIK_E_ARG, "stall rule: patience %d, at least one check without progress", r->patience);
+    if (r->stop != 0 && r->stop != 1) return fail(VFIK_E_ARG, "stall rule: stop %d is neither 0 nor 1", r->stop);
+    if (!std::isfinite(r->eps_pos) || !std::isfinite(r->eps_rot) || !std::isfinite(r->eps_js) || r->eps_pos < 0.0 || r->eps_rot < 0.0 || r->eps_js < 0.0)
+        return fail(VFIK_E_ARG, "stall rule: eps (%g m, %g rad, joints %g) must be finite and not negative", r->eps_pos, r->eps_rot, r->eps_js);
+    if (r->stalled && (!gpu_visible(r->stalled) || reinterpret_cast<uintptr_t>(r->stalled) % sizeof(int32_t)))
+        return fail(VFIK_E_ARG, "stall rule: stalled must be an int32-aligned DEVICE pointer (NULL: the handle's own array)");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_set_stall_rule allocates the handle's stall state: call it before capturing the stream")) return VFIK_E_STATE;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const size_t B = (size_t)h->B;
+    if (!h->d_stall_best && dev_alloc(h, (void**)&h->d_stall_best, B * 2 * sizeof(double), true)) return VFIK_E_HIP;
+    if (!h->d_stall_count && dev_alloc(h, (void**)&h->d_stall_count, B * sizeof(int32_t), true)) return VFIK_E_HIP;
+    if (!h->d_stall_own) {   // (-1 in every byte: no arm stalled before the first timed move)
+        if (dev_alloc(h, (void**)&h->d_stall_own, B * sizeof(int32_t), false)) return VFIK_E_HIP;
+        HIP_TRY(hipMemsetAsync(h->d_stall_own, 0xFF, B * sizeof(int32_t), h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->stall = *r;
+    h->stall_on = true;
+    return VFIK_OK;
+}
+
+int vfik_stalled_host(vfik_handle* h, int32_t* out) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!out) return fail(VFIK_E_ARG, "vfik_stalled_host: out[B] is required");
+    if (!h->stall_on) return fail(VFIK_E_STATE, "vfik_stalled_host: the handle has no stall rule (vfik_set_stall_rule)");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_stalled_host copies to the host and synchronises: not while the stream is being captured")) return VFIK_E_STATE;
+    HIP_TRY(hipMemcpyAsync(out, h->stall.stalled ? h->stall.stalled : h->d_stall_own, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return VFIK_OK;
 }
 
 // ---- pipelined host path -------------------------------------------------------------------------

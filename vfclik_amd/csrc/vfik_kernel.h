@@ -584,7 +584,23 @@ struct CheckArgs {
     const int* way_prev;        // [B] row k - 1 of way_traj, or NULL (no trace, or k = 0)
     double via_prec[VFIK_MAX_JOINTS];   // a list: at every item before an arm's last
 };
-hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream);
+// The stall rule of a handle (vfik_set_stall_rule), evaluated inside the check by the STALL builds (check_stall_kernel, script_stall_kernel) for
+// every arm that ran its block, is under way and did not arrive at this check.  The measure, in double on the io-typed values: the Cartesian
+// rule's (d, a) as the arrival rule forms them (NaN for an arm without a goal block), or the joint rule's e = max |ref - q| over the joints whose
+// precision in force is finite (best[b][0] alone).  Progress: d < best_d - eps_pos || a < best_a - eps_rot, or e < best_e - eps_js, all strict;
+// then best = the componentwise minimum and count = 0, else ++count, and count == patience writes stalled[b] = (k + 1) * stride - 1.  A stalled
+// arm meets no rule again, is not counted in pending[k] and, with `stop`, has gate 0.  k < 0: best = +inf, count = 0, stalled = -1; the check
+// that advances an arm resets its best and count.  A second kernel argument, so that CheckArgs and ScriptArgs -- and with them the device
+// code of the builds without the rule -- keep their layout.  The arm's own lane reads and writes its state; no LDS, no scratch, no atomic.
+struct StallArgs {
+    double* best;               // [B][2]
+    int* count;                 // [B]
+    int* stalled;               // [B] cycle index of the check that declared the arm stalled, -1 = not stalled
+    int patience, stop;
+    double eps_pos, eps_rot, eps_js;
+};
+// st == NULL: the builds without the rule
+hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream, const StallArgs* st = nullptr);
 // The check of a motion script (vfik_script; script_kernel<T>, vfik_kernel.hip): vfik_follow's state machine over a list whose items are goal
 // frames or postures, kind[b][w] telling which.  `c` is read as a Cartesian list's check reads it -- way = way16, prec / via_prec = the distance
 // pair, ref = the handle's reference row, diff -- and the rest is the script's own: what the joint rule and the switch of controller need.
@@ -601,7 +617,7 @@ struct ScriptArgs {
     double mix[2][4];           // w0..w3 under way to a frame [0], to a posture [1]
     double js_prec[VFIK_MAX_JOINTS], js_via_prec[VFIK_MAX_JOINTS];   // the joint rule's band: at an arm's last step, at those before it
 };
-hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream);
+hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream, const StallArgs* st = nullptr);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

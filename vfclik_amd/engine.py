@@ -93,6 +93,9 @@ def load_library(path=None):
         "vfik_script_opts_size": (C.c_size_t, []),
         "vfik_script": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.ScriptOpts)]),
         "vfik_script_host": (C.c_int, [H, C.POINTER(IO), C.POINTER(_abi.ScriptOpts), C.c_int, C.POINTER(C.c_int)]),
+        "vfik_stall_rule_size": (C.c_size_t, []),
+        "vfik_set_stall_rule": (C.c_int, [H, C.POINTER(_abi.StallRule)]),
+        "vfik_stalled_host": (C.c_int, [H, C.c_void_p]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -144,7 +147,8 @@ def load_library(path=None):
                         % (lib.vfik_follow_opts_size(), C.sizeof(_abi.FollowOpts)))
     for name, size, mirror in (("vfik_goto_js_opts", lib.vfik_goto_js_opts_size(), _abi.GotoJsOpts),
                                ("vfik_follow_js_opts", lib.vfik_follow_js_opts_size(), _abi.FollowJsOpts),
-                               ("vfik_script_opts", lib.vfik_script_opts_size(), _abi.ScriptOpts)):
+                               ("vfik_script_opts", lib.vfik_script_opts_size(), _abi.ScriptOpts),
+                               ("vfik_stall_rule", lib.vfik_stall_rule_size(), _abi.StallRule)):
         if size != C.sizeof(mirror):
             raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
@@ -186,6 +190,7 @@ class Engine:
         self._chk(self.lib.vfik_set_params(self.h, C.byref(self.params)))
         self._torch_out = {}
         self.n_objects = 0  # object frames of the distance monitor held by the handle (set_objects)
+        self._stall_rule = None  # the stall rule of the timed moves (set_stall_rule), with the caller's stalled array kept alive
         self._make_specs()
 
     # -- plumbing -------------------------------------------------------------------------------
@@ -614,8 +619,38 @@ class Engine:
         ran = C.c_int(0)
         self._chk(fn(self.h, C.byref(io), C.byref(o), int(poll), C.byref(ran)))
         out["checks_run"] = int(ran.value)
+        if self._stall_rule is not None:
+            out["stalled"] = self.stalled()
         for k in ("pending",) + traces:
             out[k] = out[k][:out["checks_run"]]
+        return out
+
+    def set_stall_rule(self, patience, eps=(0.0, 0.0), eps_js=0.0, stop=True, stalled=None):
+        """Declare arms that make no progress stalled, on the device, in every timed move from now on (include/vfik.h:
+        vfik_set_stall_rule); ``patience=None`` switches the rule off again, the default.  An arm under way whose measure -- distance and
+        angle to its goal, or the largest joint error -- has not improved on its best by more than ``eps`` = (metres, radians) or
+        ``eps_js`` for ``patience`` checks in a row is stalled: no rule is applied to it again, it leaves ``pending`` (so ``poll`` ends a
+        host form without it) and, with ``stop``, it takes no further cycle.  ``stalled``: an int32 (batch,) torch tensor on this device
+        or a raw device address that receives every arm's stall cycle (-1: not stalled), else the engine keeps its own (:meth:`stalled`).
+        While a rule is set every ``*_host`` form returns a ``"stalled"`` key."""
+        if patience is None:
+            self._chk(self.lib.vfik_set_stall_rule(self.h, None))
+            self._stall_rule = None
+            return
+        self._check_dev((("stalled", stalled, (self.batch,), "int32"),))
+        r = _abi.StallRule()
+        r.patience, r.stop = int(patience), (1 if stop else 0)
+        r.eps_pos, r.eps_rot = map(float, eps)
+        r.eps_js = float(eps_js)
+        r.stalled = _ptr(stalled)
+        self._chk(self.lib.vfik_set_stall_rule(self.h, C.byref(r)))
+        self._stall_rule = (r, stalled)
+
+    def stalled(self):
+        """int32 (batch,): the cycle index of the check that declared each arm stalled in the last timed move, -1 for an arm that
+        did not stall (vfik_stalled_host; synchronises).  Needs a stall rule."""
+        out = np.empty(self.batch, dtype=np.int32)
+        self._chk(self.lib.vfik_stalled_host(self.h, C.c_void_p(out.ctypes.data)))
         return out
 
     def _js_precision(self, precision, name="precision"):

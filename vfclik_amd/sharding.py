@@ -263,6 +263,17 @@ class ShardedEngine:
         return self._checked_host(lambda e, i, a: e.script_host(qs_of[i], kinds[i], ways[i], wayqs[i], n_cycles, dt, precision, js_precision, **a),
                                   global_rows, kw)
 
+    def set_stall_rule(self, patience, eps=(0.0, 0.0), eps_js=0.0, stop=True):
+        """Engine.set_stall_rule on every engine of this rank (``patience=None``: off); each engine keeps its own ``stalled`` array.  While
+        the rule is set the host forms return ``stalled`` in arm order beside their other per-arm rows."""
+        for e in self.engines:
+            e.set_stall_rule(patience, eps=eps, eps_js=eps_js, stop=stop)
+
+    def stalled(self):
+        """Engine.stalled of this rank's arms, in arm order."""
+        import numpy as np
+        return np.concatenate([e.stalled() for e in self.engines], axis=0)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
