@@ -1,5 +1,5 @@
 """CPU-side checks of the waypoint lists (include/vfik.h: vfik_follow): the options struct and its ctypes mirror, the ABI version, the
-exported symbols, and the oracle restatement (tests/follow_reference.py) on a hand-made case of three arms."""
+exported symbols, and the oracle restatement (tests/timed_reference.py: follow) on a hand-made case of three arms."""
 import ctypes
 import os
 import re
@@ -59,31 +59,25 @@ def three_arms(lib):
     """lwr, nullspace + joint-limit task, three waypoints 0.1 rad apart in joint space: arm 0 starts 0.03 rad from its first waypoint's
     configuration, arm 1 is gated off by the caller, arm 2 has a one-row path (rows 1 and 2 start with NaN).  160 cycles of 10 ms,
     checks every 4, precision (0.01 m, 0.05 rad) at every waypoint, hold on."""
-    import follow_reference as fr
+    import timed_reference as tr
     from oracle import oracle_c
-    from vfclik_amd import _abi, robots, synth
-    chain = robots.lwr()
-    w = synth.make_workload(chain, 3, 2, seed=53, io_dtype=np.float64)
-    qg0 = np.array([[0.3, 0.5, -0.2, 1.0, 0.1, -0.6, 0.2]] * 3) * np.array([[1.0], [0.8], [-0.9]])
-    step = 0.1 * np.array([1, -1, 1, 1, -1, 1, -1.0])
-    way = np.stack([chain.fk(qg0 + i * step).reshape(3, 16) for i in range(3)], axis=1)
+    from vfclik_amd import _abi
+    chain, w, qg, way, q0, params = tr.three_lwr_arms(_abi.F_NULLSPACE | _abi.F_JOINT_LIMIT_TASK)
     way[2, 1:] = np.nan
-    q0 = qg0 + 0.03 * np.array([1, -1, 1, -1, 1, -1, 1.0])
-    params = _abi.default_params(flags=_abi.F_NULLSPACE | _abi.F_JOINT_LIMIT_TASK, max_vel=0.7)
     start = np.array(w["fields"], copy=True)
-    ref = fr.follow_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], way, N_CYCLES, STRIDE, 0.01, PREC, hold=True,
-                              clamp=True, active=[1, 0, 1], want=("qdot_out", "pose"))
+    ref = tr.follow(oracle_c, chain, params, q0, w["fields"], w["nfields"], way, N_CYCLES, STRIDE, 0.01, PREC, hold=True, clamp=True,
+                    active=[1, 0, 1], want=("qdot_out", "pose"))
     assert np.array_equal(start["p"], w["fields"]["p"])   # the caller's field array is not the mutable one
     return q0, way, ref, w
 
 
 def test_reference_path_lengths():
-    import follow_reference as fr
+    import timed_reference as tr
     way = np.zeros((5, 3, 16))
     way[1, 2, 0] = way[2, 1, 0] = way[3, 0, 0] = np.nan
     way[4, 1, 0] = way[4, 2, 5] = np.nan    # a NaN elsewhere in a row does not end a path; rows behind the first NaN row do not count
     way[3, 2, 0] = 1.0
-    assert list(fr.path_lengths(way)) == [3, 2, 1, 0, 1]
+    assert list(tr.list_lengths(way)) == [3, 2, 1, 0, 1]
 
 
 def test_reference_rule_on_three_arms(three_arms):

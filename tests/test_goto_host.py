@@ -1,5 +1,5 @@
 """CPU-side checks of the batched goto (include/vfik.h: vfik_goto): the options struct and its ctypes mirror, the ABI version, the
-exported symbols, and the oracle restatement (tests/goto_reference.py) on a hand-made case of three arms."""
+exported symbols, and the oracle restatement (tests/timed_reference.py: goto) on a hand-made case of three arms."""
 import ctypes
 import os
 import re
@@ -52,23 +52,20 @@ def test_goto_symbols_are_declared_and_exported(lib):
 def three_arms(lib):
     """lwr, nullspace + joint-limit task: arm 0 starts 0.03 rad from its goal configuration, arm 1 is gated off by the caller, arm 2
     starts 0.2 rad away.  40 cycles of 10 ms, checks every 4, precision (0.01 m, 0.05 rad), once with hold and once without."""
-    import goto_reference as gr
+    import timed_reference as tr
     from oracle import oracle_c
-    from vfclik_amd import _abi, robots, synth
-    chain = robots.lwr()
-    w = synth.make_workload(chain, 3, 2, seed=53, io_dtype=np.float64)
-    qg = np.array([[0.3, 0.5, -0.2, 1.0, 0.1, -0.6, 0.2]] * 3) * np.array([[1.0], [0.8], [-0.9]])
-    w["fields"]["p"][:, 0, :16] = chain.fk(qg).reshape(3, 16)
-    q0 = qg + np.array([[0.03], [0.03], [0.2]]) * np.array([1, -1, 1, -1, 1, -1, 1.0])
-    params = _abi.default_params(flags=_abi.F_NULLSPACE | _abi.F_JOINT_LIMIT_TASK, max_vel=0.7)
+    from vfclik_amd import _abi
+    chain, w, qg, way, q0, params = tr.three_lwr_arms(_abi.F_NULLSPACE | _abi.F_JOINT_LIMIT_TASK)
+    w["fields"]["p"][:, 0, :16] = way[:, 0]
+    q0[2] = qg[2, 0] + 0.2 * np.array([1, -1, 1, -1, 1, -1, 1.0])
     kw = dict(n_cycles=40, stride=4, dt=0.01, precision=(0.01, 0.05), clamp=True, active=[1, 0, 1], want=("qdot_out", "pose"))
-    held = gr.goto_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], hold=True, **kw)
-    free = gr.goto_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], hold=False, **kw)
+    held = tr.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], hold=True, **kw)
+    free = tr.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], hold=False, **kw)
     return q0, held, free, chain, w, params
 
 
 def test_reference_arrival_rule_on_three_arms(three_arms):
-    import goto_reference as gr
+    import timed_reference as tr
     q0, held, free, chain, w, params = three_arms
     for r in (held, free):
         a = r["arrived"]
@@ -79,7 +76,7 @@ def test_reference_arrival_rule_on_three_arms(three_arms):
         assert np.all(r["dist_traj"][k0, 0] < thr)                        # under both thresholds at its check ...
         assert k0 == 0 or not np.all(r["dist_traj"][k0 - 1, 0] < thr)     # ... and at none before
         # the distances are those of the pose of the block's last cycle against the goal frame
-        goal = gr.goal_frames(w["fields"], w["nfields"])
+        goal = tr.goal_frames(w["fields"], w["nfields"])
         assert np.allclose(goal, w["fields"]["p"][:, 0, :16])
         # pending: the arms the caller lets run that have not arrived yet
         for k in range(10):
@@ -101,6 +98,6 @@ def test_reference_hold_freezes_an_arrived_arm(three_arms):
     assert np.any(free["q_traj"][k0 + 1:, 0] != free["q_traj"][k0, 0])    # without it the arm keeps tracking
     assert np.array_equal(held["q_traj"][: k0 + 1], free["q_traj"][: k0 + 1])
     # the held arm's output rows are those of its last evaluated cycle: the pose whose distance passed the check
-    import goto_reference as gr
-    d = gr.goal_distance(held["pose"][:1], w["fields"]["p"][:1, 0, :16])
+    import timed_reference as tr
+    d = tr.goal_distance(held["pose"][:1], w["fields"]["p"][:1, 0, :16])
     assert np.array_equal(d[0], held["dist_traj"][k0, 0])

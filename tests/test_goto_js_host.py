@@ -1,5 +1,5 @@
 """CPU-side checks of the joint-space goto and the posture lists (include/vfik.h: vfik_goto_js / vfik_follow_js): the option structs and
-their ctypes mirrors, the ABI version, the exported symbols, and the oracle restatement (tests/goto_js_reference.py) against the closed
+their ctypes mirrors, the ABI version, the exported symbols, and the oracle restatement (tests/timed_reference.py: goto_js, follow_js) against the closed
 form of a pure P controller."""
 import ctypes
 import os
@@ -71,26 +71,26 @@ def test_engine_and_sharded_engine_have_the_methods(lib):
 def test_rule_edges_are_computed_as_written():
     """The two edges are fl(ref - prec) and fl(ref + prec): a q equal to an edge passes, its neighbour outside does not, whatever
     |ref - q| <= prec says."""
-    import goto_js_reference as jr
+    import timed_reference as tr
     rng = np.random.default_rng(3)
     ref = rng.uniform(-2, 2, (4000, 1))
     prec = rng.uniform(0.001, 0.3, (4000, 1))
     lo, hi = ref - prec, ref + prec
-    assert jr.rule(ref, lo, prec).all() and jr.rule(ref, hi, prec).all()
-    assert not jr.rule(ref, np.nextafter(lo, -np.inf), prec).any() and not jr.rule(ref, np.nextafter(hi, np.inf), prec).any()
-    assert not jr.rule(ref, np.full_like(ref, np.nan), prec).any() and not jr.rule(np.full_like(ref, np.nan), lo, prec).any()
-    assert jr.rule(ref, ref + 1e9, np.full_like(prec, np.inf)).all()    # +inf: the joint never decides
+    assert tr.rule(ref, lo, prec).all() and tr.rule(ref, hi, prec).all()
+    assert not tr.rule(ref, np.nextafter(lo, -np.inf), prec).any() and not tr.rule(ref, np.nextafter(hi, np.inf), prec).any()
+    assert not tr.rule(ref, np.full_like(ref, np.nan), prec).any() and not tr.rule(np.full_like(ref, np.nan), lo, prec).any()
+    assert tr.rule(ref, ref + 1e9, np.full_like(prec, np.inf)).all()    # +inf: the joint never decides
     fabs = np.abs(ref - lo) <= prec
     assert np.count_nonzero(~fabs) > 100                                # ... and |ref - q| <= prec is another function
 
 
 def test_list_lengths():
-    import goto_js_reference as jr
+    import timed_reference as tr
     way = np.zeros((5, 3, 7))
     way[1, 2, 0] = way[2, 1, 0] = way[3, 0, 0] = np.nan
     way[4, 1, 0] = way[4, 2, 5] = np.nan    # a NaN elsewhere in a row does not end a list; rows behind the first NaN row do not count
     way[3, 2, 0] = 1.0
-    assert list(jr.list_lengths(way)) == [3, 2, 1, 0, 1]
+    assert list(tr.list_lengths(way)) == [3, 2, 1, 0, 1]
 
 
 KP, DT, STRIDE, N_CYCLES = 8.0, 0.01, 4, 80
@@ -114,7 +114,7 @@ def pure_p(lib):
     """lwr under pure joint control (mixer [0, 0, 1, 0, 0, 0], F_MIXER; the rollout's clamp off, nothing near a limit for arms 0-2):
     arm 0 starts 0.02 rad from its reference, arm 1 0.25 rad, arm 2 is gated off by the caller; arm 3's reference lies 0.1 rad BEYOND the
     upper limit of joint 0 with precision 0.01: the controller keeps the clamped value, the rule reads what the caller sent."""
-    import goto_js_reference as jr
+    import timed_reference as tr
     from oracle import oracle_c
     from vfclik_amd import _abi, robots, synth
     chain = robots.lwr()
@@ -125,7 +125,7 @@ def pure_p(lib):
     ref[3, 0] = chain.q_hi[0] + 0.1
     q0[3, 0] = chain.q_hi[0] - 0.05
     params = _abi.default_params(flags=_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=KP)
-    out = jr.goto_js_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], ref, N_CYCLES, STRIDE, DT, PREC, hold=True,
+    out = tr.goto_js(oracle_c, chain, params, q0, w["fields"], w["nfields"], ref, N_CYCLES, STRIDE, DT, PREC, hold=True,
                                clamp=False, active=[1, 1, 0, 1])
     return chain, q0, ref, out
 
@@ -158,7 +158,7 @@ def test_reference_against_the_closed_form(pure_p):
 def test_reference_posture_list(pure_p):
     """Three postures 0.1 rad apart, via precision 3 x: one advance per check at most, the last posture under the tight precision; a
     one-row list; an arm without a list is kept out.  W = 1 is the goto."""
-    import goto_js_reference as jr
+    import timed_reference as tr
     from oracle import oracle_c
     from vfclik_amd import _abi, robots, synth
     chain, q0, ref, out = pure_p
@@ -168,7 +168,7 @@ def test_reference_posture_list(pure_p):
     wayq[1, 1:] = np.nan
     wayq[2] = np.nan
     params = _abi.default_params(flags=_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=KP)
-    f = jr.follow_js_reference(oracle_c, chain, params, q0[:3], w["fields"], w["nfields"], wayq, 160, STRIDE, DT, PREC, via_prec=3 * PREC,
+    f = tr.follow_js(oracle_c, chain, params, q0[:3], w["fields"], w["nfields"], wayq, 160, STRIDE, DT, PREC, via_prec=3 * PREC,
                                hold=True)
     assert list(f["length"]) == [3, 1, 0] and list(f["next"]) == [3, 1, 0]
     r = f["reached"][0]
@@ -178,11 +178,11 @@ def test_reference_posture_list(pure_p):
     for wi, cyc in enumerate(r):
         k = (cyc + 1) // STRIDE - 1
         assert f["way_traj"][k, 0] == wi
-        assert jr.rule(wayq[:1, wi], f["q_traj"][k, :1], PREC if wi == 2 else 3 * PREC).all()
+        assert tr.rule(wayq[:1, wi], f["q_traj"][k, :1], PREC if wi == 2 else 3 * PREC).all()
     assert f["reached"][1, 0] == out["arrived"][1] and np.all(f["reached"][1, 1:] == -1)
     assert np.all(f["reached"][2] == -1) and np.all(f["q_traj"][:, 2] == q0[2]) and np.all(f["way_traj"][:, 2] == -1)
     assert f["pending"][0] == 2 and f["pending"][-1] == 0
-    g = jr.goto_js_reference(oracle_c, chain, params, q0[:2], w["fields"][:2], w["nfields"][:2], ref[:2], N_CYCLES, STRIDE, DT, PREC, hold=True)
-    f1 = jr.follow_js_reference(oracle_c, chain, params, q0[:2], w["fields"][:2], w["nfields"][:2], ref[:2, None, :], N_CYCLES, STRIDE, DT,
+    g = tr.goto_js(oracle_c, chain, params, q0[:2], w["fields"][:2], w["nfields"][:2], ref[:2], N_CYCLES, STRIDE, DT, PREC, hold=True)
+    f1 = tr.follow_js(oracle_c, chain, params, q0[:2], w["fields"][:2], w["nfields"][:2], ref[:2, None, :], N_CYCLES, STRIDE, DT,
                                 PREC, hold=True)
     assert np.array_equal(g["arrived"], f1["reached"][:, 0]) and np.array_equal(g["q_traj"], f1["q_traj"]) and np.array_equal(g["diff"], f1["diff"])

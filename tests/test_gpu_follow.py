@@ -1,5 +1,5 @@
 """Waypoint lists (include/vfik.h: vfik_follow / vfik_follow_host) on the GPU against their restatement with the oracle
-(tests/follow_reference.py): which arm reaches which waypoint at which check, the joint path, the distance trace and the waypoint it
+(tests/timed_reference.py: follow): which arm reaches which waypoint at which check, the joint path, the distance trace and the waypoint it
 was measured against, the count of arms still under way, the hold, ragged paths, the caller's gate, the goal block afterwards, the
 early exit of the host form, its argument errors, the kernels it launches and the sharded form.
 
@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import follow_reference as fr  # noqa: E402
+import timed_reference as fr  # noqa: E402
 import kernel_variants as kv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -78,8 +78,8 @@ def _reference(env, robot, B, flags, stride, hold=True, io_dtype=np.float64, gat
         chain, w, q0, way, active = _case(env, robot, B, io_dtype, gate, no_goal, ragged)
         way = np.ascontiguousarray(way[:, :n_way])
         params = env.abi.default_params(flags=flags, max_vel=0.7)
-        ref = fr.follow_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], way, N_CYCLES, stride, DT, PREC, via_precision=via,
-                                  hold=hold, clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",))
+        ref = fr.follow(env.oc, chain, params, q0, w["fields"], w["nfields"], way, N_CYCLES, stride, DT, PREC, via_precision=via, hold=hold,
+                        clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",))
         for v in ref.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)
@@ -272,8 +272,7 @@ def test_ragged_paths(env):
     nxt = env.oc.cycle_batch(chain, params, ref["q"], ref["fields"], w["nfields"], states=ref["states"], want=("qdot_out", "pose"))
     out = eng.step_host(np.array(ref["q"]), want=("qdot_out", "goal_dist"))
     err = np.abs(out["qdot_out"][inc] - nxt["qdot_out"][inc]).max()
-    import goto_reference as gr
-    ed = np.abs(out["goal_dist"][inc] - gr.goal_distance(nxt["pose"], gr.goal_frames(ref["fields"], w["nfields"]))[inc]).max(axis=0)
+    ed = np.abs(out["goal_dist"][inc] - fr.goal_distance(nxt["pose"], fr.goal_frames(ref["fields"], w["nfields"]))[inc]).max(axis=0)
     print("following cycle: qdot_out max error %.3e, goal_dist %.3e m %.3e deg" % (err, ed[0], ed[1]))
     assert err < 1e-6 and ed[0] < 1e-8 and ed[1] < 1e-6
     eng.close()

@@ -1,5 +1,5 @@
 """Posture lists (include/vfik.h: vfik_follow_js / vfik_follow_js_host: a script of set_ref_js calls, handlers.py:544-576, for the batch)
-on the GPU against their restatement with the oracle (tests/goto_js_reference.py): which arm reaches which posture at which check, the
+on the GPU against their restatement with the oracle (tests/timed_reference.py: follow_js): which arm reaches which posture at which check, the
 posture index every check was made against, the joint path, `diff`, the count of arms under way, lists of different lengths, an arm
 without a list, and what the call leaves of the handle.
 
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import goto_js_reference as jr  # noqa: E402
+import timed_reference as jr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -80,8 +80,8 @@ def _reference(env, robot, B, stride, hold, io_dtype=np.float64, active=None):
         chain, w, q0, wayq = _case(env, robot, B, io_dtype)
         params = _params(env)
         p = _prec(chain.n)
-        out = jr.follow_js_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], wayq, N_CYCLES, stride, DT, p, via_prec=3 * p,
-                                     hold=hold, clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7)
+        out = jr.follow_js(env.oc, chain, params, q0, w["fields"], w["nfields"], wayq, N_CYCLES, stride, DT, p, via_prec=3 * p, hold=hold,
+                           clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7)
         for v in out.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)
@@ -106,26 +106,14 @@ def _follow(eng, q0, wayq, stride, hold, **kw):
 
 
 def _replay(wayq, L, q_traj, stride, hold, prec, via, ua=None):
-    """The state machine of the header on given q rows, with the helper's rule: (reached, next, way_traj, last check every arm ran).
-    ua: the caller's gate as booleans (None: every arm)."""
+    """The helper's state machine on given q rows: (reached, next, way_traj, last check every arm ran).  ua: the caller's gate as
+    booleans (None: every arm)."""
     n_checks, B, n = q_traj.shape
-    arms = np.arange(B)
-    part = (L > 0) if ua is None else (L > 0) & ua
-    nxt = np.zeros(B, dtype=np.int32)
-    reached = np.full((B, wayq.shape[1]), -1, dtype=np.int32)
-    way_traj = np.full((n_checks, B), -1, dtype=np.int32)
-    last_ran = np.full(B, -1)
-    gate = part.copy()
-    for k in range(n_checks):
-        idx = np.minimum(nxt, np.maximum(L - 1, 0))
-        way_traj[k] = np.where(gate, idx, way_traj[k - 1] if k else -1)
-        last_ran = np.where(gate, k, last_ran)
-        p = np.where((nxt >= L - 1)[:, None], prec[None, :], via[None, :])
-        ok = gate & (nxt < L) & jr.rule(wayq[arms, idx], q_traj[k].astype(np.float64), p)
-        reached[arms[ok], nxt[ok]] = (k + 1) * stride - 1
-        nxt = nxt + ok.astype(np.int32)
-        gate = part & ~(bool(hold) & (nxt == L))
-    return reached, nxt, way_traj, last_ran
+    kind = jr.list_kind(wayq, jr.POSTURE)
+    assert np.array_equal(jr.lengths(kind), L)
+    m = jr.replay(kind, wayq, np.ones(B, dtype=bool), q_traj, None, n_checks * stride, stride, (0.0, 0.0), prec, js_via_precision=via,
+                  hold=hold, active=ua)
+    return m.reached, m.next, m.way_traj, m.last_ran
 
 
 def _check(got, ref, q0, wayq, stride, hold, io_dtype, active=None, n_checks=None):

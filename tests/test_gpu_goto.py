@@ -1,5 +1,5 @@
 """The batched goto (include/vfik.h: vfik_goto / vfik_goto_host; handlers.py:346-440 for the batch) on the GPU against its
-restatement with the oracle (tests/goto_reference.py): which arm arrives at which check, the joint path, the distance trace, the count
+restatement with the oracle (tests/timed_reference.py: goto): which arm arrives at which check, the joint path, the distance trace, the count
 of arms still under way, the hold, the caller's gate, the early exit of the host form, its argument errors, the kernels it launches
 and the sharded form.
 
@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import goto_reference as gr  # noqa: E402
+import timed_reference as gr  # noqa: E402
 import kernel_variants as kv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -68,8 +68,8 @@ def _reference(env, robot, B, flags, stride, hold, io_dtype=np.float64, gate=Fal
     if key not in env.cache:
         chain, w, q0, active = _case(env, robot, B, io_dtype, gate, no_goal)
         params = env.abi.default_params(flags=flags, max_vel=0.7)
-        ref = gr.goto_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, stride, DT, PREC, hold=hold, clamp=True,
-                                active=active, io_dtype=io_dtype, want=("qdot_out",))
+        ref = gr.goto(env.oc, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, stride, DT, PREC, hold=hold, clamp=True, active=active,
+                      io_dtype=io_dtype, want=("qdot_out",))
         for v in ref.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)

@@ -1,5 +1,5 @@
 """The joint-space goto (include/vfik.h: vfik_goto_js / vfik_goto_js_host; set_ref_js, handlers.py:544-576, for the batch) on the GPU
-against its restatement with the oracle (tests/goto_js_reference.py): which arm arrives at which check, the joint path, `diff`, the count
+against its restatement with the oracle (tests/timed_reference.py: goto_js): which arm arrives at which check, the joint path, `diff`, the count
 of arms still under way, the hold, the caller's gate, arms without a controller, the decision edges, the early exit of the host form, its
 argument errors, the kernels it launches, the device form and the sharded form.
 
@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import goto_js_reference as jr  # noqa: E402
+import timed_reference as jr  # noqa: E402
 import kernel_variants as kv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -81,8 +81,8 @@ def _reference(env, robot, B, stride, hold, io_dtype=np.float64, mixed=False):
             ref[1::2, 0] = np.nan
             active = np.ones(B, dtype=np.int32)
             active[::3] = 0
-        out = jr.goto_js_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], ref, N_CYCLES, stride, DT, _prec(chain.n), hold=hold,
-                                   clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7, mix_w_arm=mixw)
+        out = jr.goto_js(env.oc, chain, params, q0, w["fields"], w["nfields"], ref, N_CYCLES, stride, DT, _prec(chain.n), hold=hold, clamp=True,
+                         active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7, mix_w_arm=mixw)
         for v in out.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)

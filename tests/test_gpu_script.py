@@ -1,6 +1,6 @@
 """Motion scripts (include/vfik.h: vfik_script / vfik_script_host: set_ref_js, a list of gotoFrame calls, set_ref_js, with the bridge's
 controller switched around each change of kind, handlers.py:189-211, 346-387, 481-497, 544-576) on the GPU against their restatement with
-the oracle (tests/script_reference.py): which arm reaches which step at which check, the step every check was made against, the joint
+the oracle (tests/timed_reference.py: script): which arm reaches which step at which check, the step every check was made against, the joint
 path, the distance trace, `diff`, the count of arms under way, scripts of different lengths and shapes, the caller's gate, an arm
 without a goal block, the hold, the early exit, the two pure forms against vfik_follow and vfik_follow_js, what the call leaves of
 the handle, the kernels it launches, its argument errors, the device form and the sharded form.
@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import script_reference as sr  # noqa: E402
+import timed_reference as sr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -101,9 +101,8 @@ def _reference(env, robot, B, stride, hold, io_dtype=np.float64, gate=False, no_
             active = np.ones(B, dtype=np.int32)
             active[::3] = 0
         p = _prec(chain.n)
-        ref = sr.script_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, n_cycles, stride, DT, PREC, p,
-                                  js_via_precision=3 * p, hold=hold, clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",),
-                                  stepped=chain.n > 7)
+        ref = sr.script(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, n_cycles, stride, DT, PREC, p,
+                        js_via_precision=3 * p, hold=hold, clamp=True, active=active, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7)
         for v in ref.values():
             if isinstance(v, np.ndarray):
                 v.setflags(write=False)
@@ -147,7 +146,7 @@ def _check(got, ref, q0, kind, wayq, stride, hold, io_dtype, active=None, n_chec
     B, n = q0.shape
     p = _prec(n)
     n_checks = n_cycles // stride if n_checks is None else n_checks
-    L = sr.script_lengths(kind)
+    L = sr.lengths(kind)
     assert np.array_equal(L, ref["length"]) and set(L) == {0, 1, 3, 4}
     ua = np.ones(B, dtype=bool) if active is None else active != 0
     part = ua & (L > 0)
@@ -288,8 +287,8 @@ def test_early_exit(env):
 def _goal_left(w, kind, way, got):
     """The field array with every arm's goal as the script left it: the last frame it was sent (rows 0..2), for arms with a goal block"""
     fields = np.array(w["fields"], copy=True)
-    L = sr.script_lengths(kind)
-    slot = sr.fr._goal_slot(fields, w["nfields"])
+    L = sr.lengths(kind)
+    slot = sr.goal_slot(fields, w["nfields"])
     for b in range(kind.shape[0]):
         sent = [i for i in range(min(got["next"][b], L[b] - 1) + 1) if kind[b, i] == F] if L[b] > 0 else []
         if sent and slot[b] >= 0:
@@ -339,9 +338,8 @@ def test_the_handle_is_left_as_it_was(env, per_arm):
     assert np.array_equal(after_ref["q_ref_out"], first_ref["q_ref_out"])
     if per_arm:
         p = _prec(7)
-        ref = sr.script_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, N_CYCLES, 1, DT, PREC, p,
-                                  js_via_precision=3 * p, hold=False, clamp=True, want=("qdot_out",),
-                                  bridge_arm=np.column_stack([mixw[:, 4], mixw[:, 5], max_vel]))
+        ref = sr.script(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, N_CYCLES, 1, DT, PREC, p, js_via_precision=3 * p,
+                        hold=False, clamp=True, want=("qdot_out",), bridge_arm=np.column_stack([mixw[:, 4], mixw[:, 5], max_vel]))
         part = ref["length"] > 0
         out, _ = _left_out(ref, part, np.float64)
         inc = ~out

@@ -1,5 +1,5 @@
 """The stall rule of the timed moves (include/vfik.h: vfik_set_stall_rule) on the GPU against its restatement with the oracle
-(tests/stall_reference.py): which arm stalls at which check, beside which arm arrives, in vfik_goto (float64 and float32), vfik_goto_js and
+(tests/timed_reference.py): which arm stalls at which check, beside which arm arrives, in vfik_goto (float64 and float32), vfik_goto_js and
 vfik_script; the state machine replayed on the GPU's own rows; arms without a goal block and the two values of `stop`; the early exit of
 the host form; the rule switched off again; the errors, the device-pointer form and the sharded form.
 
@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import stall_reference as st  # noqa: E402
+import timed_reference as st  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -314,10 +314,9 @@ def test_script_stalls(env, robot, B):
     chain, w, q0, kind, way, wayq, params = _script_case(env, robot, B, io_dtype)
     p = _prec(chain.n)
     rule = st.Rule(**c["rule"])
-    ref = _frozen(st.stall_reference(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, SCRIPT_CYCLES, stride, DT, PREC, p,
-                                     js_via_precision=3 * p, hold=True, clamp=True, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7,
-                                     rule=rule))
-    L = st.sr.script_lengths(kind)
+    ref = _frozen(st.script(env.oc, chain, params, q0, w["fields"], w["nfields"], kind, way, wayq, SCRIPT_CYCLES, stride, DT, PREC, p,
+                            js_via_precision=3 * p, hold=True, clamp=True, io_dtype=io_dtype, want=("qdot_out",), stepped=chain.n > 7, rule=rule))
+    L = st.lengths(kind)
     part = L > 0
     out = _left_out(ref, part, io_dtype)
     done = part & (ref["next"] == L)
@@ -377,7 +376,7 @@ def test_pure_scripts_equal_follow_and_follow_js_with_the_rule(env):
         b = eng.script_host(q0, kind, way, wayq, SCRIPT_CYCLES, DT, PREC, p, js_via_precision=3 * p, **kw)
         eng.close()
         far = np.arange(B) % 5 == 0
-        far &= st.sr.script_lengths(kind) > 2
+        far &= st.lengths(kind) > 2
         print("kind %d: %d arms stall, %d finish" % (kinds, np.count_nonzero(a["stalled"] >= 0), np.count_nonzero(a["next"] == 4)))
         assert np.all(a["stalled"][far] >= 0) and np.all(a["next"][far] == 2) and np.count_nonzero(a["next"] == 4) >= 40
         assert a["checks_run"] == b["checks_run"]

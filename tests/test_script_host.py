@@ -1,7 +1,6 @@
 """CPU-side checks of the motion scripts (include/vfik.h: vfik_script): the options struct and its ctypes mirror, the ABI version, the
-exported symbols, and the oracle restatement (tests/script_reference.py) against the two restatements it is built from -- a script of
-frames only is tests/follow_reference.py's run, one of postures only tests/goto_js_reference.py's, bit for bit -- and on a hand-made
-case of two steps."""
+exported symbols, and the oracle restatement (tests/timed_reference.py: script) against the list forms' entry points -- a script of
+frames only is `follow`'s run, one of postures only `follow_js`'s, bit for bit -- and on a hand-made case of two steps."""
 import ctypes
 import os
 import re
@@ -62,25 +61,13 @@ def test_engine_and_sharded_engine_have_the_methods(lib):
 
 
 def test_script_lengths():
-    import script_reference as sr
+    import timed_reference as tr
     kind = np.array([[1, 2, 1, 2], [2, 2, 0, 1], [0, 1, 1, 1], [1, 3, 1, 1], [2, -1, 2, 2], [0, 0, 0, 0]], dtype=np.int32)
-    assert list(sr.script_lengths(kind)) == [4, 2, 0, 1, 1, 0]
+    assert list(tr.lengths(kind)) == [4, 2, 0, 1, 1, 0]
 
 
 STRIDE, N_CYCLES, DT, PREC = 4, 160, 0.01, (0.01, 0.05)
 JS_PREC = 0.01 * np.ones(7)
-
-
-def _three(flags, **params):
-    from vfclik_amd import _abi, robots, synth
-    chain = robots.lwr()
-    w = synth.make_workload(chain, 3, 2, seed=53, io_dtype=np.float64)
-    qg0 = np.array([[0.3, 0.5, -0.2, 1.0, 0.1, -0.6, 0.2]] * 3) * np.array([[1.0], [0.8], [-0.9]])
-    step = 0.1 * np.array([1, -1, 1, 1, -1, 1, -1.0])
-    qg = np.stack([qg0 + i * step for i in range(3)], axis=1)
-    way = chain.fk(qg.reshape(9, 7)).reshape(3, 3, 16)
-    q0 = qg0 + 0.03 * np.array([1, -1, 1, -1, 1, -1, 1.0])
-    return chain, w, qg, way, q0, _abi.default_params(flags=flags, max_vel=0.7, **params)
 
 
 def _same(a, b, keys):
@@ -89,22 +76,20 @@ def _same(a, b, keys):
 
 
 def test_frames_only_is_follow_reference(lib):
-    """kind all FRAME (arm 2: one step, then none), mix_frame = params.mix_w[:4]: follow_reference's run with NaN rows ending the
-    paths, bit for bit -- the caller gates arm 1."""
-    import follow_reference as fr
-    import script_reference as sr
+    """kind all FRAME (arm 2: one step, then none), mix_frame = params.mix_w[:4]: `follow`'s run with NaN rows ending the paths, bit
+    for bit -- the caller gates arm 1.  The two entry points differ in who owns the mixer and in where the lengths come from."""
+    import timed_reference as tr
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_NULLSPACE | _abi.F_MIXER | _abi.F_LIMITER)
+    chain, w, qg, way, q0, params = tr.three_lwr_arms(_abi.F_NULLSPACE | _abi.F_MIXER | _abi.F_LIMITER)
     kind = np.full((3, 3), _abi.STEP_FRAME, dtype=np.int32)
     kind[2, 1:] = 0
     way_nan = way.copy()
     way_nan[2, 1:] = np.nan
     kw = dict(hold=True, clamp=True, active=[1, 0, 1], want=("qdot_out", "pose"))
-    a = fr.follow_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], way_nan, N_CYCLES, STRIDE, DT, PREC,
-                            via_precision=(0.03, 0.1), **kw)
-    b = sr.script_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, N_CYCLES, STRIDE, DT, PREC, JS_PREC,
-                            via_precision=(0.03, 0.1), mix_frame=list(params.mix_w)[:4], **kw)
+    a = tr.follow(oracle_c, chain, params, q0, w["fields"], w["nfields"], way_nan, N_CYCLES, STRIDE, DT, PREC, via_precision=(0.03, 0.1), **kw)
+    b = tr.script(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, N_CYCLES, STRIDE, DT, PREC, JS_PREC,
+                  via_precision=(0.03, 0.1), mix_frame=list(params.mix_w)[:4], **kw)
     assert list(a["next"]) == [3, 0, 1]
     _same(a, b, ("reached", "next", "length", "pending", "q_traj", "dist_traj", "way_traj", "q", "qdot_out", "pose", "status"))
     assert np.array_equal(a["fields"]["p"], b["fields"]["p"]) and np.array_equal(a["closest"], b["closest_c"])
@@ -112,21 +97,19 @@ def test_frames_only_is_follow_reference(lib):
 
 
 def test_postures_only_is_follow_js_reference(lib):
-    """kind all POSTURE, mix_posture = params.mix_w[:4]: follow_js_reference's run, bit for bit; without hold."""
-    import goto_js_reference as jr
-    import script_reference as sr
+    """kind all POSTURE, mix_posture = params.mix_w[:4]: `follow_js`'s run, bit for bit; without hold."""
+    import timed_reference as tr
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=8.0)
+    chain, w, qg, way, q0, params = tr.three_lwr_arms(_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=8.0)
     kind = np.full((3, 3), _abi.STEP_POSTURE, dtype=np.int32)
     kind[2, 1:] = 7
     wayq_nan = qg.copy()
     wayq_nan[2, 1:] = np.nan
     kw = dict(hold=False, clamp=True, active=[1, 0, 1], want=("qdot_out",))
-    a = jr.follow_js_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], wayq_nan, N_CYCLES, STRIDE, DT, JS_PREC,
-                               via_prec=3 * JS_PREC, **kw)
-    b = sr.script_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, N_CYCLES, STRIDE, DT, PREC, JS_PREC,
-                            js_via_precision=3 * JS_PREC, mix_posture=list(params.mix_w)[:4], **kw)
+    a = tr.follow_js(oracle_c, chain, params, q0, w["fields"], w["nfields"], wayq_nan, N_CYCLES, STRIDE, DT, JS_PREC, via_prec=3 * JS_PREC, **kw)
+    b = tr.script(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, N_CYCLES, STRIDE, DT, PREC, JS_PREC,
+                  js_via_precision=3 * JS_PREC, mix_posture=list(params.mix_w)[:4], **kw)
     assert list(a["next"]) == [3, 0, 1]
     _same(a, b, ("reached", "next", "length", "pending", "q_traj", "way_traj", "q", "diff", "qdot_out", "status"))
     assert np.array_equal(a["closest"], b["closest_j"]) and np.all(np.isinf(b["closest_c"]))
@@ -138,17 +121,17 @@ def test_two_steps_by_hand(lib):
     posture.  Arm 2: no script (kind zeroed).  Posture steps are a pure P controller under [0, 0, 1, 0] -- the field takes no part --,
     so arm 0 reaches P0 when e0 (1 - kp dt)^c <= prec: cycle 11; the frame step then runs under [1, 1, 0, 0], where the reference row
     takes no part."""
-    import script_reference as sr
+    import timed_reference as tr
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_MIXER, jp_kp=8.0)
+    chain, w, qg, way, q0, params = tr.three_lwr_arms(_abi.F_MIXER, jp_kp=8.0)
     F, P = _abi.STEP_FRAME, _abi.STEP_POSTURE
     kind = np.array([[P, F, 0], [F, P, 0], [0, F, P]], dtype=np.int32)
     sign = np.array([1, -1, 1, -1, 1, -1, 1.0])
     q0 = np.array([qg[0, 0] + 0.02 * sign, qg[1, 0] + 0.03 * sign, qg[2, 0]])
     n_cycles = 240
-    r = sr.script_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, n_cycles, STRIDE, DT, PREC, JS_PREC,
-                            hold=True, clamp=True, want=("qdot_out",))
+    r = tr.script(oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, n_cycles, STRIDE, DT, PREC, JS_PREC, hold=True,
+                  clamp=True, want=("qdot_out",))
     assert list(r["length"]) == [2, 2, 0] and list(r["next"]) == [2, 2, 0]
     thr = np.array([PREC[0], PREC[1] * 180.0 / np.pi])
     # arm 0: the closed form of its posture step, then the frame
@@ -164,7 +147,7 @@ def test_two_steps_by_hand(lib):
     # arm 1: no controller until its posture; the goal stays the frame it was sent first
     j0, j1 = [(c + 1) // STRIDE - 1 for c in r["reached"][1, :2]]
     assert 0 <= j0 < j1 and np.all(r["dist_traj"][j0, 1] < thr)
-    assert sr.gjr.rule(qg[1:2, 1], r["q_traj"][j1, 1:2], JS_PREC).all() and not sr.gjr.rule(qg[1:2, 1], r["q_traj"][j1 - 1, 1:2], JS_PREC).any()
+    assert tr.rule(qg[1:2, 1], r["q_traj"][j1, 1:2], JS_PREC).all() and not tr.rule(qg[1:2, 1], r["q_traj"][j1 - 1, 1:2], JS_PREC).any()
     assert np.array_equal(r["diff"][1], qg[1, 1] - r["q_traj"][j1, 1]) and np.array_equal(r["fields"]["p"][1, 0, :12], way[1, 0, :12])
     assert np.all(r["q_traj"][j1:, 1] == r["q_traj"][j1, 1])                                      # hold
     # between j0 and j1 arm 1 is a pure P controller towards its posture
@@ -177,6 +160,6 @@ def test_two_steps_by_hand(lib):
         cyc = (k + 1) * STRIDE - 1
         assert r["pending"][k] == sum(1 for b in (0, 1) if r["reached"][b, 1] > cyc)
     # the replay of the state machine on the run's own rows gives the run's decisions
-    m = sr.replay(kind, qg, r["present"], r["q_traj"], r["dist_traj"], n_cycles, STRIDE, PREC, JS_PREC, hold=True)
+    m = tr.replay(kind, qg, r["present"], r["q_traj"], r["dist_traj"], n_cycles, STRIDE, PREC, JS_PREC, hold=True)
     assert np.array_equal(m.reached, r["reached"]) and np.array_equal(m.next, r["next"]) and np.array_equal(m.way_traj, r["way_traj"])
     assert np.array_equal(m.pending, r["pending"]) and np.array_equal(m.diff, r["diff"])

@@ -1,7 +1,7 @@
 """CPU-side checks of the stall rule of the timed moves (include/vfik.h: vfik_set_stall_rule): the rule struct and its ctypes mirror, the
-exported symbols, the Python methods, and the host restatement (tests/stall_reference.py) -- the rule on hand-made traces, and its
-oracle-stepped loop against goto_reference, goto_js_reference and script_reference, which it must reproduce bit for bit while the
-patience is larger than the number of checks."""
+exported symbols, the Python methods, and the host restatement (tests/timed_reference.py) -- the rule on hand-made traces, and the
+oracle-stepped loop with a rule against the same move without one, which it must reproduce bit for bit while the patience is larger
+than the number of checks; a goto against a script of one frame step, a joint-space goto against one of one posture step."""
 import ctypes
 import os
 import re
@@ -48,7 +48,7 @@ def test_engine_and_sharded_engine_have_the_methods(lib):
 
 # ---- the rule on hand-made traces.  eps = (1/8, 1/4) and measures that are sums of powers of two: best - eps is exact ----
 def _state(B, patience):
-    import stall_reference as st
+    import timed_reference as st
     return st.StallState(B, st.Rule(patience, eps=(0.125, 0.25), eps_js=0.125))
 
 
@@ -81,7 +81,7 @@ def test_equality_is_not_progress_and_the_stall_lands_at_the_patience_th_miss():
 
 
 def test_nan_is_never_progress_and_the_joint_measure():
-    import stall_reference as st
+    import timed_reference as st
     s = _state(2, 2)
     sel = np.array([True, True])
     nan = np.nan
@@ -101,7 +101,7 @@ STRIDE = 4
 
 def _frames_machine(dist, patience, n_way=2, present=None, stop=True, hold=True):
     """replay of a frames-only script on hand-made distance rows dist (checks, B) in metres, angle 0 (NaN beside a NaN distance)"""
-    import stall_reference as st
+    import timed_reference as st
     n_checks, B = dist.shape
     kind = np.full((B, n_way), st.FRAME, dtype=np.int32)
     d2 = np.stack([dist, np.where(np.isnan(dist), np.nan, 0.0)], axis=2)
@@ -145,7 +145,7 @@ def test_machine_stop_off_keeps_the_arm_running_unchecked():
 def test_machine_posture_steps():
     """The joint rule.  Arm 0's reference starts with NaN; arm 1 creeps by 1/16 per check under eps_js = 1/8; arm 2's first joint is
     far off and never moves, its second gains 1/2 per check."""
-    import stall_reference as st
+    import timed_reference as st
     nan, inf = np.nan, np.inf
     n_checks = 8
     wayq = np.array([[[nan, 0.0]], [[0.0, 0.0]], [[0.0, 0.0]]])
@@ -170,22 +170,9 @@ def test_machine_posture_steps():
     assert list(m.stalled) == [3 * STRIDE - 1, -1, 4 * STRIDE - 1]
 
 
-# ---- the oracle-stepped loop: with a patience above n_checks it is the three restatements it stands beside, bit for bit ----
+# ---- the oracle-stepped loop: with a patience above n_checks it is the move without a rule, bit for bit ----
 N_CYCLES, DT, PREC = 160, 0.01, (0.01, 0.05)
 JS_PREC = 0.01 * np.ones(7)
-
-
-def _three(flags, **params):
-    """tests/test_script_host.py's three lwr arms"""
-    from vfclik_amd import _abi, robots, synth
-    chain = robots.lwr()
-    w = synth.make_workload(chain, 3, 2, seed=53, io_dtype=np.float64)
-    qg0 = np.array([[0.3, 0.5, -0.2, 1.0, 0.1, -0.6, 0.2]] * 3) * np.array([[1.0], [0.8], [-0.9]])
-    step = 0.1 * np.array([1, -1, 1, 1, -1, 1, -1.0])
-    qg = np.stack([qg0 + i * step for i in range(3)], axis=1)
-    way = chain.fk(qg.reshape(9, 7)).reshape(3, 3, 16)
-    q0 = qg0 + 0.03 * np.array([1, -1, 1, -1, 1, -1, 1.0])
-    return chain, w, qg, way, q0, _abi.default_params(flags=flags, max_vel=0.7, **params)
 
 
 def _same(a, b, keys):
@@ -194,25 +181,29 @@ def _same(a, b, keys):
 
 
 def _never():
-    import stall_reference as st
+    import timed_reference as st
     return st.Rule(N_CYCLES // STRIDE + 1, eps=(1e-3, 1e-2), eps_js=1e-3)
 
 
 def test_patient_rule_is_goto_reference(lib):
-    import goto_reference as gr
-    import stall_reference as st
+    """goto with a patient rule = goto without one = a script of one frame step -- the arm's own goal, sent, under the handle's weights
+    as the call's quad"""
+    import timed_reference as st
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_NULLSPACE | _abi.F_MIXER | _abi.F_LIMITER)
+    chain, w, qg, way, q0, params = st.three_lwr_arms(_abi.F_NULLSPACE | _abi.F_MIXER | _abi.F_LIMITER)
     w["fields"]["p"][:, 0, :16] = way[:, 1]          # the goal: one step of 0.1 rad per joint away
     w["nfields"][2] = 0                              # arm 2: no goal block
     kw = dict(hold=True, clamp=True, active=[1, 1, 1], want=("qdot_out",))
-    a = gr.goto_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, STRIDE, DT, PREC, **kw)
+    a = st.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, STRIDE, DT, PREC, **kw)
     b = st.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, STRIDE, DT, PREC, rule=_never(), **kw)
     assert np.all(a["arrived"][:2] >= 0) and a["arrived"][2] == -1
     _same(a, b, ("arrived", "pending", "q_traj", "dist_traj", "q", "qdot_out", "status"))
     assert np.array_equal(a["closest"], b["closest_c"]) and np.all(b["stalled"] == -1)
-    c = st.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, STRIDE, DT, PREC, rule=None, **kw)
+    goal = np.where((w["nfields"] > 0)[:, None], w["fields"]["p"][:, 0, :16], 0.0)
+    c = st.script(oracle_c, chain, params, q0, w["fields"], w["nfields"], np.full((3, 1), st.FRAME, dtype=np.int32), goal[:, None, :],
+                  np.zeros((3, 1, 7)), N_CYCLES, STRIDE, DT, PREC, np.zeros(7), mix_frame=list(params.mix_w)[:4], **kw)
+    c["arrived"] = c["reached"][:, 0]
     _same(b, c, ("arrived", "pending", "q_traj", "dist_traj", "q", "qdot_out", "status"))
     # and with patience 3 the arm without a goal block stalls at check 2, stops there, and the others are untouched
     d = st.goto(oracle_c, chain, params, q0, w["fields"], w["nfields"], N_CYCLES, STRIDE, DT, PREC, rule=st.Rule(3, eps=(1e-3, 1e-2)), **kw)
@@ -222,43 +213,45 @@ def test_patient_rule_is_goto_reference(lib):
 
 
 def test_patient_rule_is_goto_js_reference(lib):
-    import goto_js_reference as jr
-    import stall_reference as st
+    """goto_js with a patient rule = goto_js without one = a script of one posture step under the handle's weights as the call's quad"""
+    import timed_reference as st
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=8.0)
+    chain, w, qg, way, q0, params = st.three_lwr_arms(_abi.F_MIXER, mix_w=[0, 0, 1, 0, 0, 0], jp_kp=8.0)
     q_ref = qg[:, 0].copy()
     q_ref[2, 0] = np.nan                             # arm 2: no controller
     kw = dict(hold=True, clamp=True, want=("qdot_out",))
-    a = jr.goto_js_reference(oracle_c, chain, params, q0, w["fields"], w["nfields"], q_ref, N_CYCLES, STRIDE, DT, JS_PREC, **kw)
+    a = st.goto_js(oracle_c, chain, params, q0, w["fields"], w["nfields"], q_ref, N_CYCLES, STRIDE, DT, JS_PREC, **kw)
     b = st.goto_js(oracle_c, chain, params, q0, w["fields"], w["nfields"], q_ref, N_CYCLES, STRIDE, DT, JS_PREC, rule=_never(), **kw)
     assert np.all(a["arrived"][:2] >= 0) and a["arrived"][2] == -1
     _same(a, b, ("arrived", "pending", "q_traj", "q", "diff", "qdot_out", "status"))
     assert np.array_equal(a["closest"], b["closest_j"]) and np.all(b["stalled"] == -1)
+    c = st.script(oracle_c, chain, params, q0, w["fields"], w["nfields"], np.full((3, 1), st.POSTURE, dtype=np.int32), np.zeros((3, 1, 16)),
+                  q_ref[:, None, :], N_CYCLES, STRIDE, DT, (0.0, 0.0), JS_PREC, mix_posture=list(params.mix_w)[:4], **kw)
+    _same(b, c, ("reached", "pending", "q_traj", "q", "diff", "qdot_out", "status", "closest_j"))
     d = st.goto_js(oracle_c, chain, params, q0, w["fields"], w["nfields"], q_ref, N_CYCLES, STRIDE, DT, JS_PREC, rule=st.Rule(2, eps_js=1e-3), **kw)
     assert list(d["stalled"]) == [-1, -1, 2 * STRIDE - 1] and np.array_equal(d["arrived"], a["arrived"])
 
 
 def test_patient_rule_is_script_reference(lib):
-    import script_reference as sr
-    import stall_reference as st
+    import timed_reference as st
     from oracle import oracle_c
     from vfclik_amd import _abi
-    chain, w, qg, way, q0, params = _three(_abi.F_MIXER, jp_kp=8.0)
+    chain, w, qg, way, q0, params = st.three_lwr_arms(_abi.F_MIXER, jp_kp=8.0)
     F, P = _abi.STEP_FRAME, _abi.STEP_POSTURE
     kind = np.array([[P, F, 0], [F, P, 0], [0, F, P]], dtype=np.int32)
     sign = np.array([1, -1, 1, -1, 1, -1, 1.0])
     q0 = np.array([qg[0, 0] + 0.02 * sign, qg[1, 0] + 0.03 * sign, qg[2, 0]])
     args = (oracle_c, chain, params, q0, w["fields"], w["nfields"], kind, way, qg, 240, STRIDE, DT, PREC, JS_PREC)
     kw = dict(hold=True, clamp=True, want=("qdot_out",))
-    a = sr.script_reference(*args, **kw)
-    b = st.stall_reference(*args, rule=st.Rule(61, eps=(1e-3, 1e-2), eps_js=1e-3), **kw)
+    a = st.script(*args, **kw)
+    b = st.script(*args, rule=st.Rule(61, eps=(1e-3, 1e-2), eps_js=1e-3), **kw)
     assert list(a["next"]) == [2, 2, 0]
     _same(a, b, ("reached", "next", "length", "pending", "q_traj", "dist_traj", "way_traj", "q", "diff", "qdot_out", "status", "q_ref",
                  "closest_c", "closest_j"))
     assert np.array_equal(a["fields"]["p"], b["fields"]["p"]) and np.all(b["stalled"] == -1)
     # both arms took more checks in total than a patience of 8, yet finish: the advance resets the state
-    c = st.stall_reference(*args, rule=st.Rule(8, eps=(1e-4, 1e-3), eps_js=1e-4), **kw)
+    c = st.script(*args, rule=st.Rule(8, eps=(1e-4, 1e-3), eps_js=1e-4), **kw)
     checks = (a["reached"][:2, 1] + 1) // STRIDE
     assert np.all(checks > 8) and np.all(c["stalled"] == -1)
     _same(a, c, ("reached", "next", "q_traj"))
