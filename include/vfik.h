@@ -179,8 +179,9 @@ int vfik_set_arm_weights(vfik_handle* h, int first_arm, int n_arms, const double
 int vfik_set_mixer_weights(vfik_handle* h, int first_arm, int n_arms, const double* w);
 
 /* Per-arm limiter speed: what each arm's bridge keeps after a /bridge/max_vel message (bridge:612-623; the
- * reference accepts 0 <= v <= config.max_vel, the caller applies that rule).  Used with VFIK_F_LIMITER.  A
- * vfik_set_params that CHANGES vfik_params.max_vel writes the new value to every arm. */
+ * reference accepts 0 <= v <= config.max_vel, the caller applies that rule).  Used with VFIK_F_LIMITER.  Any
+ * v >= 0, +inf included (no limit: the decision is lead > max_vel), as for vfik_params.max_vel; negative values
+ * and NaN are refused.  A vfik_set_params that CHANGES vfik_params.max_vel writes the new value to every arm. */
 int vfik_set_max_vel(vfik_handle* h, int first_arm, int n_arms, const double* values);
 
 /* Last command of mixer channel 2..5 (jointcmd, mechanismcmd, xtra1cmd, xtra2cmd; bridge:593-596)

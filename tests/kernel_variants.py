@@ -33,6 +33,16 @@ HEAVY = " [heavy]"
 Variant = collections.namedtuple("Variant", "name kernel args heavy")
 
 
+def chain10(robots, Chain):
+    """The 10-joint chain of the suite: the LWR's DH table and three more links, off every DH pattern (none is built for 10 joints)."""
+    import math
+
+    import numpy as np
+    dh = list(robots._LWR_DH) + [(0.05, math.pi / 2, 0.1, 0.0), (0.0, -math.pi / 2, 0.12, 0.3), (0.08, 0.4, 0.0, 0.0)]
+    lim = np.concatenate([robots._LWR_LIM, np.array([150, 120, 150]) * math.pi / 180])
+    return Chain.from_dh(dh, -lim, lim, name="rand10")
+
+
 def parse(name):
     """cycle_kernel_name's string -> Variant(name, kernel, args, heavy); args maps the template parameter names to int / bool / 'float' | 'double'."""
     heavy = name.endswith(HEAVY)

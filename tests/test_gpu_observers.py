@@ -6,6 +6,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
+def _hp_observers():
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import hp_observers
+    return hp_observers
+
+
 def test_goal_distance_and_tracking_error():
     import __graft_entry__ as g
     g.build()
@@ -85,6 +93,11 @@ def test_object_distances_match_the_monitor(dt, tol):
             assert oid == k
             assert abs(got[b, k, 0] - dxyz) < (1e-12 if dt == np.float64 else 1e-6)
             assert abs(got[b, k, 1] - dang) < tol, (b, k, got[b, k, 1], dang)
+    # (that restatement floors the angle and words the relative rotation as G R^T: its bar cannot go below what the two forms differ by for
+    # frames rounded to float32.)  The monitor's own form is held to its 50-digit reference by the derived units of tests/hp_observers.py:
+    ho = _hp_observers()
+    rD, rA = ho.ratios(got, ho.reference(("test_object_distances", dt), pose.astype(np.float64), frames.astype(np.float64)), dt)
+    assert rD.max() < 1.0 and rA.max() < 1.0, (rD.max(), rA.max())
     assert np.abs(got[:, 0]).max() < (1e-6 if dt == np.float64 else 0.1)
     assert np.abs(got[:, 1, 0] - 0.25).max() < 1e-6 and np.abs(got[:, 1, 1] - 180.0).max() < (1e-5 if dt == np.float64 else 0.1)
     with pytest.raises(engine.VfikError):
@@ -158,6 +171,7 @@ def test_observers_fused_into_the_cycle_call(dt, tol):
     q = w["q"].copy()
     outs = prev = None
     seen = 0
+    hist = {"pose": [], "v6": [], "act": [], "out": []}
     for t in range(K):
         active = rng.uniform(size=B) > 0.2 if t % 3 == 1 else None
         ask_pose = t % 2 == 0                          # with and without the caller asking for pose / v6 itself
@@ -190,8 +204,31 @@ def test_observers_fused_into_the_cycle_call(dt, tol):
                     assert abs(out["obj_dist"][b, k, 1] - dang) < (1e-6 if dt == np.float64 else 5e-2)
                 # object 0 is the goal: the monitor's entry equals the cycle kernel's own goal distance
                 assert abs(out["obj_dist"][b, 0, 0] - out["goal_dist"][b, 0]) < (1e-9 if dt == np.float64 else 1e-5)
+        # (the rows the fused estimator read: this call's own where it published them, the same cycle's of the second call otherwise)
+        hist["pose"].append((out if ask_pose else ref_full)["pose"].astype(np.float64))
+        hist["v6"].append((out if ask_pose else ref_full)["v6"].astype(np.float64))
+        hist["act"].append(act.astype(np.int32))
+        hist["out"].append(out["track_error"].astype(np.float64))
+        if ask_pose:
+            # the monitor's own form against its 50-digit reference on the pose this very call published, by the units of tests/hp_observers.py
+            ho = _hp_observers()
+            sel = np.nonzero(act & (np.arange(B) % 13 == 0))[0]
+            href = ho.reference(("fused", dt, t), out["pose"][sel].astype(np.float64), frames[sel].astype(dt).astype(np.float64))
+            rD, rA = ho.ratios(out["obj_dist"][sel], href, dt)
+            assert rD.max() < 1.0 and rA.max() < 1.0, (t, rD.max(), rA.max())
         q = q + step * np.where(act[:, None], out["qdot_out"].astype(np.float64), 0.0)
     assert seen > B * (K - 6) * 0.7
+    # (a sample, for run time: every 13th arm's monitor entries on the cycles that publish the pose, above, and every third arm's estimator here;
+    # the whole batch at the edges is tests/test_gpu_observer_edges.py, object 0 against goal_dist with its angle included)
+    # the estimator over every third arm's whole history against the 50-digit reference, by the units of tests/hp_observers.py: the bars that
+    # supersede 1e-7 / 5e-6 above, and the decision, exact outside its band
+    ho = _hp_observers()
+    sel = np.arange(0, B, 3)
+    P, V, A = (np.stack(hist[k])[:, sel] for k in ("pose", "v6", "act"))
+    tref = ho.track_reference(("fused", dt), P, V, A)
+    ratio, wrong, amb = ho.track_ratios(np.stack(hist["out"])[:, sel], tref, dt, A)
+    assert ratio.max() < 1.0 and not wrong.any(), (ratio.max(axis=(0, 1)), np.argwhere(wrong)[:5])
+    assert amb.any(axis=0).sum() <= ho.AMBIGUOUS_CAP * len(sel)
     # observers belong to single cycles
     with pytest.raises(engine.VfikError):
         eng.rollout_host(q, 3, 1e-3, want=("qdot_out", "track_error"))

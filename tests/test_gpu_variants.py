@@ -65,9 +65,7 @@ def _chain(env, nj, pattern):
         lim = np.array([170, 120, 150, 170, 120, 170], dtype=float) * math.pi / 180
         return Chain.from_dh(dh, -lim, lim, name="powercube6_off")
     assert nj == 10 and not pattern   # (no pattern is built for 10 joints)
-    dh = lwr_dh + [(0.05, math.pi / 2, 0.1, 0.0), (0.0, -math.pi / 2, 0.12, 0.3), (0.08, 0.4, 0.0, 0.0)]
-    lim = np.concatenate([lwr_lim, np.array([150, 120, 150]) * math.pi / 180])
-    return Chain.from_dh(dh, -lim, lim, name="rand10")
+    return kv.chain10(R, Chain)
 
 
 def _tool(i=0):

@@ -919,7 +919,7 @@ int vfik_set_max_vel(vfik_handle* h, int first_arm, int n_arms, const double* va
     if (!values) return fail(VFIK_E_ARG, "null values");
     if (check_arms(h, first_arm, n_arms)) return VFIK_E_ARG;
     for (int j = 0; j < n_arms; ++j)
-        if (!(values[j] >= 0.0) || !std::isfinite(values[j])) return fail(VFIK_E_ARG, "arm %d: max_vel %g must be finite and >= 0", first_arm + j, values[j]);
+        if (!(values[j] >= 0.0)) return fail(VFIK_E_ARG, "arm %d: max_vel %g must be >= 0", first_arm + j, values[j]);   // (+inf: no limit, as vfik_params.max_vel)
     HIP_TRY(hipSetDevice(h->device));
     if (ensure_bridge_state(h) != VFIK_OK) return VFIK_E_HIP;
     for (int j = 0; j < n_arms; ++j) h->bridge_host[(size_t)(first_arm + j) * 8 + 6] = values[j];

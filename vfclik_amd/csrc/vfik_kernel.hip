@@ -2138,7 +2138,8 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
 #pragma unroll
         for (int i = 0; i < NJ; ++i) lead = fmax(lead, fabs(qo[i]));
         if (lead > mw[6]) {
-            const double ratio = mw[6] * rcp_nr(lead);
+            // (an infinite lead is outside rcp_nr's range: bridge:192's max_vel / inf is 0, the finite joints stop and the infinite one is NaN)
+            const double ratio = mw[6] * (lead < __builtin_inf() ? rcp_nr(lead) : 0.0);
 #pragma unroll
             for (int i = 0; i < NJ; ++i) qo[i] *= ratio;
             status |= VFIK_ST_LIMITED;
@@ -3141,7 +3142,7 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) lead = fmax(lead, fabs(qo[i]));
         if (lead > kc->max_vel) {
-            const double ratio = kc->max_vel * rcp_nr(lead);
+            const double ratio = kc->max_vel * (lead < __builtin_inf() ? rcp_nr(lead) : 0.0);   // (as in cycle_kernel's limiter)
 #pragma unroll
             for (int i = 0; i < NJ; ++i) qo[i] *= ratio;
             status |= VFIK_ST_LIMITED;
