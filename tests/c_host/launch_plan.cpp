@@ -1,6 +1,7 @@
 // Prints the kernel each launch description takes under the launch plan (vfik_kernel.h: plan_cycle), with its grid, block and LDS bytes:
 // one line of `key=value` pairs per launch on stdin (KArgs members; pointers: 1 = given), one line per launch on stdout.  Host code only, no GPU:
 // built and run by tests/test_launch_plan.py.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -8,8 +9,25 @@
 #include <map>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "../../vfclik_amd/csrc/vfik_kernel.h"
+
+// The KUKA LWR 4+ in z-normal form (vfclik_amd/robots.py: (a, alpha, d) = (0, +-pi/2 | 0, d) per link): B[0] the identity, B[i] = Tz(d_i) Rx(alpha_i)
+static vfik_chain lwr_chain() {
+    static const double quarter[7] = {1, -1, -1, 1, 1, -1, 0}, d[7] = {0.310, 0.0, 0.400, 0.0, 0.390, 0.0, 0.078};
+    vfik_chain c;
+    std::memset(&c, 0, sizeof c);
+    c.n = 7;
+    c.B[0][0] = c.B[0][5] = c.B[0][10] = 1.0;
+    for (int i = 0; i < 7; ++i) {
+        const double al = quarter[i] * 1.57079632679489661923, ca = std::cos(al), sa = std::sin(al);
+        const double B[12] = {1, 0, 0, 0, 0, ca, -sa, 0, 0, sa, ca, d[i]};
+        std::memcpy(c.B[i + 1], B, sizeof B);
+        c.q_lo[i] = -2.0; c.q_hi[i] = 2.0;
+    }
+    return c;
+}
 
 int main() {
     std::string line;
@@ -37,13 +55,20 @@ int main() {
         a.plain = (int)get("plain", 1);
         a.dhp = (int)get("dhp", 0);
         // The rule for a shared tool's 3 x 3 block (include/vfik.h, vfik_set_tool): tool_shear_e6 = s gives the identity with entry (0, 1) =
-        // s / 1e6, a block whose max |R R^T - I| is that entry; tool_flat = 1 zeroes the block's last column (no inverse).  A block the rule
-        // refuses is not a plain + tool handle: kconst_fill reports plain = 0 and no pattern for it, restated here.
+        // s / 1e6, a block whose max |R R^T - I| is that entry; tool_flat = 1 zeroes the block's last column (no inverse).  `plain` and `dhp` are
+        // then what kconst_fill answers for the LWR with that tool, as a handle takes them: 2 and 1, or 0 and 0 for a block the rule refuses.
         if (kv.count("tool_shear_e6") || kv.count("tool_flat")) {
-            double tool12[12] = {1, 0, 0, 0.02, 0, 1, 0, -0.01, 0, 0, 1, 0.2}, c3[3];
+            double tool12[12] = {1, 0, 0, 0.02, 0, 1, 0, -0.01, 0, 0, 1, 0.2};
             tool12[1] = (double)get("tool_shear_e6", 0) / 1e6;
             if (get("tool_flat", 0)) tool12[2] = tool12[6] = tool12[10] = 0.0;
-            if (!vfik::tool_block_serves_plain(tool12, c3)) a.plain = a.dhp = 0;
+            const vfik_chain lwr = lwr_chain();
+            vfik_params par;
+            std::memset(&par, 0, sizeof par);
+            par.speed_scale = 1.0; par.lambda = 0.1;
+            for (double& w : par.wy) w = 1.0;
+            for (double& w : par.wq) w = 1.0;
+            std::vector<char> image(vfik::kconst_bytes(lwr.n));
+            vfik::kconst_fill(lwr.n, image.data(), lwr, par, tool12, &a.plain, &a.dhp);
         }
         a.mixw = ptr("mixw");
         a.wts = static_cast<const double*>(ptr("wts"));

@@ -66,7 +66,7 @@ ROUTES = [
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, true, 5> grid=256 block=256 lds=80896'),
     ('nj=7 io=32 B=65536 dhp=1 plain=4',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 7> grid=256 block=256 lds=80896'),
-    # the rule for a shared tool's 3 x 3 block (include/vfik.h, vfik_set_tool; the driver restates kconst_fill's use of it): a block off a rotation
+    # the rule for a shared tool's 3 x 3 block (include/vfik.h, vfik_set_tool; the driver takes plain and dhp from kconst_fill on the LWR with that tool): a block off a rotation
     # by 1e-4 (typed with four decimals), and one at 0.062 -- below VFIK_TOOL_MAX_DEFECT = 1/16 -- stay plain + tool handles ...
     ('nj=7 io=32 B=65536 dhp=1 plain=2 tool_shear_e6=100',
      'cycle_kernel_s<float, 7, false, true, false, true, 1, -1, false, false, 1, false, 3> grid=256 block=256 lds=80896'),

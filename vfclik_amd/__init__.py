@@ -1,6 +1,6 @@
 """vfclik_amd -- MI355X-native batched replacement for vfclik's per-cycle control loop.
 
-Hot path (HIP, gfx950): ``vfclik_amd/csrc/vfik_kernel.hip`` (kernels) + ``vfik_abi.cpp`` (host side) behind the C-ABI of ``include/vfik.h``.
+Hot path (HIP, gfx950): ``vfclik_amd/csrc/vfik_kernel.hip`` + ``vfik_aux.hip`` (kernels) + ``vfik_abi.cpp`` (host side) behind the C-ABI of ``include/vfik.h``.
 Host side (this package) mirrors the reference's port / handler interface:
 
     engine          ctypes binding of the C-ABI (fails loudly without the HIP library)

@@ -1,5 +1,6 @@
 // vfik_abi.cpp -- host side of the C-ABI declared in include/vfik.h: handle, device state, field
-// packing, launches.  Compiled by hipcc into libvfik_hip.so together with vfik_kernel.hip.
+// packing, launches.  Compiled by hipcc into libvfik_hip.so together with vfik_kernel.hip (the cycle kernels) and
+// vfik_aux.hip (the auxiliary kernels, the launchers); the chain's constants come from vfik_kconst.h.
 // There is no CPU execution path in this file: every compute entry point launches a HIP kernel.
 #include <hip/hip_runtime.h>
 
@@ -138,7 +139,7 @@ struct vfik_handle {
     // host bookkeeping
     std::vector<double> bridge_host;  // [B][8] mirror of d_mixw_arm: mixer weights 0..5, max_vel 6
     int plain = 0;  // the chain allows the PLAIN kernel variants: 1 + (shared tool ? 1 : 0) + (shared IK weights other than one ? 2 : 0); 0: the general variants
-    int dhp = 0;    // ... and the chain matches a DH pattern the lean kernels are built for (vfik_kernel.h: DhPattern)
+    int dhp = 0;    // ... and the chain matches a DH pattern the lean kernels are built for (vfik_kconst.h: DhPattern)
     int dhp_allowed = 1;   // VFIK_DH_PATTERN=0: always the general DH form (tests, A/B)
     bool speed_set = false;
     // vfik_step_host / vfik_rollout_host: one device arena + one pinned host arena for every member of the call
@@ -1718,8 +1719,7 @@ int vfik_probe_field(vfik_handle* h, const void* pose, void* v6) {
     if (!pose || !v6) return fail(VFIK_E_ARG, "vfik_probe_field: pose and v6 are required");
     HIP_TRY(hipSetDevice(h->device));
     const double rs = h->params.rot_slowdown;
-    const double cos_slow = rs > 0.0 && rs < 3.14159265358979323846 ? std::cos(rs) : -2.0;  // as kconst_fill
-    hipError_t e = vfik::launch_probe(h->io_dtype, pose, h->d_goal, h->d_slots, h->B, h->Bpad, h->scene.slots_used, rs, cos_slow, v6, h->stream);
+    hipError_t e = vfik::launch_probe(h->io_dtype, pose, h->d_goal, h->d_slots, h->B, h->Bpad, h->scene.slots_used, rs, vfik::cos_slow_of(rs), v6, h->stream);
     if (e != hipSuccess) return fail(VFIK_E_HIP, "probe launch: %s", hipGetErrorString(e));
     return VFIK_OK;
 }

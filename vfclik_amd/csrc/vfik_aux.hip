@@ -1,0 +1,601 @@
+// vfik_aux.hip -- the library's small kernels beside the control cycle, and every type-erased launcher vfik_abi.cpp calls:
+//   mix_kernel, track_kernel, monitor_kernel, probe_kernel      the mixer's sum alone, the tracking estimator, the distance monitor, the field probe
+//   move_kernel, move_scene_kernel                              goals, obstacles, funnels, hemispheres and attractors that move
+//   check_kernel, script_kernel (+ the _stall_ builds)          the check after each block of a timed move (vfik_check_body.inc, twice)
+//   launch_cycle                                                a launch's plan (vfik_kernel.h: plan_cycle) -> the entry point of the object that holds
+//                                                               its kernel (vfik_kernel.hip, compiled per joint count, I/O type, nullspace module)
+// Compiled once (csrc/Makefile: vfik_dispatch.o).  The float64 building blocks are vfik_device.h, shared with the cycle kernels.
+#include "vfik_kernel.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+
+namespace vfik {
+// the per-part entry points of vfik_kernel.hip
+#define X(n)                                                                                                      \
+    hipError_t launch_cycle_nj##n##_t32_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t32_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t64_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
+    hipError_t launch_cycle_nj##n##_t64_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);
+VFIK_NJ_LIST
+#undef X
+
+namespace {
+#include "vfik_device.h"
+
+// CommandMixer.read's weighted sum alone (command_mixer.py:78-82): out = sum_k cmd[k] * w[k], left to
+// right from 0.0, multiply and add rounded separately (what CPython does).
+template <typename T>
+__global__ void __launch_bounds__(256) mix_kernel(const T* cmds, const double* w, int K, long count, long chan_stride, T* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) acc = mac_unfused(acc, (double)cmds[k * chan_stride + i], w[k]);
+    out[i] = (T)acc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tracking-error estimator of scripts/vf (vf:349-428), batched, as its own small kernel (a diagnostic:
+// it never feeds qdot).  Per arm it keeps the previous tool frame, the last 4 commanded twists and a
+// frame counter; from the 6th frame on (frame_list longer than 5, vf:354) it compares the twist
+// MEASURED between the two latest frames, scaled by the assumed 150 Hz robot loop (vf:408-411), with
+// the twist COMMANDED check_delay = 4 cycles earlier (vf:363): direction angles, corrected magnitudes,
+// |difference| and arm_tracking = difference < 0.10.  state: [38][B] doubles (12 frame, 24 commands,
+// count, -).  out: [B][8] = vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr,
+// cmd_vel_mag_corr, cmd_rot_mag_corr, ext_int_diff, arm_tracking (vf:418-427); zeros until the 6th frame.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) track_kernel(const T* pose, const T* v6, double* st, T* out, const int* active, int B) {
+    const int arm = blockIdx.x * blockDim.x + threadIdx.x;
+    if (arm >= B) return;
+    if (active && !active[arm]) return;  // inside vf's `if qInBottle` (vf:312-313,349): no fresh q, no new frame
+    const long Bs = B;
+    double F[12], P[12], cmd[4][6];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { F[k] = (double)pose[(long)arm * 16 + k]; P[k] = st[k * Bs + arm]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cmd[j][k] = st[(12 + 6 * j + k) * Bs + arm];
+    const double cnt = st[36 * Bs + arm];  // frames seen before this one
+    // cmd_buffer.append(...); keep the last 4 (vf:350-352): after the shift cmd[0] is the oldest
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cmd[j][k] = cmd[j + 1][k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cmd[3][k] = (double)v6[(long)arm * 6 + k];
+    double res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (cnt >= 5.0) {  // len(frame_list) > frame_list_size (vf:354)
+        // ext_diff = PyKDL.diff(previous frame, this frame): vel = dp, rot = log(R_b R_a^T) in the base frame
+        double ev[3] = {F[3] - P[3], F[7] - P[7], F[11] - P[11]};
+        double Ra[9], Rb[9], ax[3], th;
+        bool has_axis;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { Ra[3 * r + c] = P[4 * r + c]; Rb[3 * r + c] = F[4 * r + c]; }
+        rot_axis_angle<false>(Ra, Rb, -2.0, ax, th, has_axis);
+        const double ext_vel_mag = sqrt(ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2]);
+        const double ext_rot_mag = has_axis ? th : 0.0;
+        // the command issued check_delay = 4 cycles ago is the oldest entry of the full buffer (vf:363)
+        const double* c = cmd[0];
+        const double cmd_vel_mag = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+        const double cmd_rot_mag = sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]);
+        double eu[3] = {1, 0, 0}, cu[3] = {1, 0, 0}, er[3] = {1, 0, 0}, cr[3] = {1, 0, 0};  // vf:365-374,390-399
+        if (ext_vel_mag > 0.0) for (int k = 0; k < 3; ++k) eu[k] = ev[k] / ext_vel_mag;
+        if (cmd_vel_mag > 0.0) for (int k = 0; k < 3; ++k) cu[k] = c[k] / cmd_vel_mag;
+        if (ext_rot_mag > 0.0) for (int k = 0; k < 3; ++k) er[k] = ax[k];
+        if (cmd_rot_mag > 0.0) for (int k = 0; k < 3; ++k) cr[k] = c[3 + k] / cmd_rot_mag;
+        const double vd = fmin(1.0, fmax(-1.0, cu[0] * eu[0] + cu[1] * eu[1] + cu[2] * eu[2]));
+        const double rd = fmin(1.0, fmax(-1.0, cr[0] * er[0] + cr[1] * er[1] + cr[2] * er[2]));
+        res[0] = fabs(acos(vd));
+        res[1] = fabs(acos(rd));
+        res[2] = ext_vel_mag * 150.0;   // loop_freq (vf:408)
+        res[3] = ext_rot_mag * 150.0;
+        res[4] = cmd_vel_mag;
+        res[5] = cmd_rot_mag / 5.0;     // vf:412
+        res[6] = fabs((res[4] + res[5]) - (res[2] + res[3]));
+        res[7] = res[6] < 0.10 ? 1.0 : 0.0;  // tracking_th (vf:409,416)
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out[(long)arm * 8 + k] = (T)res[k];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) st[k * Bs + arm] = F[k];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) st[(12 + 6 * j + k) * Bs + arm] = cmd[j][k];
+    st[36 * Bs + arm] = cnt + 1.0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Distance monitor of scripts/monitor_distance (monitor_distance:76-84,148-167), batched: for every arm
+// and every object frame it was told about (/dmonitor/objectsIn: the goal is object 0, obstacles
+// follow), the xyz distance between the tool pose and the object and the rotation angle between their
+// orientations, in DEGREES (orientLength = |diff(current, final).rot| * 180/pi).  One thread per
+// (arm, object); pose [B][16], frames [B][O][16], out [B][O][2].  A diagnostic: it never feeds qdot.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) monitor_kernel(const T* pose, const T* frames, int O, long count, T* out, const int* active) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const long arm = t / O;
+    if (active && !active[arm]) return;  // no fresh q, no new pose (monitor_distance:138-147 acts on a pose that ARRIVED): the rows stay
+    double P[12], F[12];
+    const T* pp = pose + arm * 16;
+    const T* fp = frames + t * 16;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { P[k] = (double)pp[k]; F[k] = (double)fp[k]; }
+    const double dx = P[3] - F[3], dy = P[7] - F[7], dz = P[11] - F[11];
+    // relative rotation E = R_cur^T R_obj; its angle is what |diff().rot| measures
+    double E[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) E[3 * i + j] = P[i] * F[j] + P[4 + i] * F[4 + j] + P[8 + i] * F[8 + j];
+    const double a0 = 0.5 * (E[7] - E[5]), a1 = 0.5 * (E[2] - E[6]), a2 = 0.5 * (E[3] - E[1]);
+    const double c = 0.5 * (E[0] + E[4] + E[8] - 1.0);
+    const double sn = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+    out[2 * t] = (T)sqrt(dx * dx + dy * dy + dz * dz);
+    out[2 * t + 1] = (T)(atan2_pos(sn, c) * 57.295779513082320877);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Field probe of scripts/vf (vf:469-503, "for visualizing"): the arm's total field evaluated at a pose that
+// is handed in (/pose_in) instead of the forward kinematics: v6 = speedScale * scalars * normCart(sum)
+// (vf:491-494 = vf:344-347 at another frame).  One thread per arm; goal block and slots are read straight
+// from the quad planes through the general per-slot path.  pose [B][16], out [B][6].
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) probe_kernel(const T* pose, const T* goal, const T* slots, int B, long Bp, int slots_used,
+                                                    double rot_slow, double cos_slow, T* out) {
+    const int arm = blockIdx.x * blockDim.x + threadIdx.x;
+    if (arm >= B) return;
+    double Rt[9], pt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Rt[3 * r + c] = (double)pose[(long)arm * 16 + 4 * r + c];
+        pt[r] = (double)pose[(long)arm * 16 + 4 * r + 3];
+    }
+    const long Qp = Bp * 4;
+    double gq[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) gq[k] = (double)goal[(long)(k >> 2) * Qp + (long)arm * 4 + (k & 3)];
+    double tot[6] = {0, 0, 0, 0, 0, 0}, sc[2] = {1.0, 1.0};
+    double GR[9], Gp[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) GR[3 * r + c] = gq[4 * r + c];
+        Gp[r] = gq[4 * r + 3];
+    }
+    attractor<false>(Rt, pt, GR, Gp, gq[13], gq[14], rot_slow, cos_slow, gq[12] != 0.0, tot, sc, nullptr);
+    const T* sq = slots + (long)arm * 4;
+    const SlotGlobal<T> rg{sq, Qp};
+    for (int m = 0; m < slots_used; ++m) eval_slot(rg, m, Rt, pt, rot_slow, cos_slow, tot, sc);
+    double nt, nti, nr, nri;
+    sqrt_rsqrt(tot[0] * tot[0] + tot[1] * tot[1] + tot[2] * tot[2], nt, nti);
+    sqrt_rsqrt(tot[3] * tot[3] + tot[4] * tot[4] + tot[5] * tot[5], nr, nri);
+    const double speed = gq[15];
+    const double kt = nt > EPS_LEN ? speed * sc[0] * nti : 0.0;
+    const double kr = nr > EPS_LEN ? speed * sc[1] * nri : 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        out[(long)arm * 6 + k] = (T)(tot[k] * kt);
+        out[(long)arm * 6 + 3 + k] = (T)(tot[3 + k] * kr);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// vfik_move_fields (ABI 6): goals and obstacles that move (object_feeder:214-354 re-sends an object's primitives with new coordinates
+// whenever its pose changes: the goal frame, object_feeder:229-241; x y z radius of the point obstacles and the near-goal repeller,
+// object_feeder:317-334).  One thread per (arm, primitive): lanes run over arms -- aligned to the planes' 64-quad rows, so that every
+// plane write of a wave is one contiguous 1 KiB (2 KiB at float64 I/O) -- and blockIdx.y over the primitives: the goal frame when
+// one is given, then decay repeller k of the caller's rows.  Every image a later launch may read gets the new numbers:
+//   goal block   rows 0..2 of the frame (plane 3 -- present, slow-down, force, speedScale -- stays),
+//   uniform      plane k + 1: the whole quad (x y z radius),
+//   compact      (x0 y0 z0 r0 | s0 f0 x1 y1 | z1 r1 s1 f1): the even slot's first quad; the odd slot's two half quads (s f stay),
+//   general      first plane of the slot repmap names (p0..p3 = x y z radius; p4 p5 force type stay).
+// Rows from the arm's repeller count on find MOVE_NONE in the map and write nothing: an unused slot keeps its -inf radius / zero force.
+// Plain vector stores, no LDS, no loop, no register array.  VEC: the caller's arrays are 16-byte aligned (whole-quad loads).
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct alignas(16) MoveQuad { T v[4]; };
+template <typename T> struct alignas(2 * sizeof(T)) MovePair { T v[2]; };
+
+template <typename T, bool VEC>
+__device__ __forceinline__ MoveQuad<T> move_load(const T* src) {
+    if (VEC) return *reinterpret_cast<const MoveQuad<T>*>(src);
+    MoveQuad<T> r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r.v[e] = src[e];
+    return r;
+}
+
+// the goal frame of one arm: rows 0..2 into the goal block's first three planes
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_goal_row(const MoveArgs& m, int arm, long j) {
+    const long Qp = m.Bpad;  // quads per plane
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(m.goal) + arm;
+    if (g[3 * Qp].v[0] == (T)0) return;   // no goal block: the row is ignored
+    const T* src = static_cast<const T*>(m.goal16) + j * 16;
+    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
+    if (r0.v[0] != r0.v[0]) return;       // NaN: this goal stays
+    g[0] = r0;
+    g[Qp] = r1;
+    g[2 * Qp] = r2;
+}
+
+// decay repeller k of one arm: x y z radius into the uniform, the compact and the general image
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_rep_row(const MoveArgs& m, int arm, long j, int k) {
+    const long Qp = m.Bpad;
+    if (k >= m.n_rep || k >= m.S) return;
+    const unsigned gs = m.repmap[((long)(k >> 3) * m.Bpad + arm) * 8 + (k & 7)];
+    if (gs >= (unsigned)m.S) return;              // MOVE_NONE: the arm has no k-th decay repeller
+    const MoveQuad<T> r = move_load<T, VEC>(static_cast<const T*>(m.rep4) + (j * m.n_rep + k) * 4);
+    if (r.v[0] != r.v[0]) return;                 // NaN: this repeller stays
+    static_cast<MoveQuad<T>*>(m.slots_uni)[(long)(k + 1) * Qp + arm] = r;
+    static_cast<MoveQuad<T>*>(m.slots)[(long)(2 * gs) * Qp + arm] = r;
+    MoveQuad<T>* const f = static_cast<MoveQuad<T>*>(m.slots_fast) + (long)(3 * (k >> 1)) * Qp + arm;
+    if (!(k & 1)) {
+        f[0] = r;
+    } else {
+        MovePair<T> lo, hi;
+        lo.v[0] = r.v[0]; lo.v[1] = r.v[1]; hi.v[0] = r.v[2]; hi.v[1] = r.v[3];
+        reinterpret_cast<MovePair<T>*>(f + Qp)[1] = lo;
+        reinterpret_cast<MovePair<T>*>(f + 2 * Qp)[0] = hi;
+    }
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
+    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
+    const long j = arm - m.first_arm;
+    if (m.active && !m.active[j]) return;
+    int k = (int)blockIdx.y;
+    if (m.goal16) {
+        if (k == 0) {
+            move_goal_row<T, VEC>(m, arm, j);
+            return;
+        }
+        --k;
+    }
+    move_rep_row<T, VEC>(m, arm, j, k);
+}
+
+// ------------------------------------------------------------------------------------------------
+// vfik_move_scene: the rest of what the object feeder re-sends for an object that moves -- the approach funnel of `set goalAndNormal`
+// (object_feeder:248-303), the surface of `set ObstacleH` (object_feeder:335-354) -- and attractors behind the goal block.  The same
+// thread mapping as move_kernel; blockIdx.y runs over the goal frame, the caller's repeller rows, then its funnel, hemisphere and attractor
+// rows (the class of a block is uniform: scalar branches).  Goal and repellers: move_kernel's stores.  The new classes live in the general
+// image (and the aux block), whose slots keep p0..p5 | force type in two planes:
+//   funnel / hemisphere k, general slot gs   plane 2 gs <- the quad x y z ax; plane 2 gs + 1 <- its FIRST pair ay az (force, type stay);
+//                                            k = 0 also aux planes 0, 1 (funnel) or 3, 4 (hemisphere), laid out alike (cutAngle
+//                                            angleOrder / safe order in the second pair stay);
+//   attractor k, general slot gs             planes 2 gs, 2 gs + 1 (pair), 2 gs + 2, 2 gs + 3 (pair) <- p0..p11; slot gs + 2 (frame row 3,
+//                                            slow-down distance) stays.
+// A wave's pair stores cover the first 8 of every 16 bytes of one contiguous 1-KiB row (2 KiB at float64 I/O): every 128-byte line of the row
+// is touched by ONE instruction -- byte-masked in L2, no line split between instructions -- as move_kernel's odd compact-image slots already are.
+// Rows of six are 8-byte aligned at float32: pair loads (VEC: the caller's 6-rows are pair aligned, its 4- and 16-rows quad aligned).
+// ------------------------------------------------------------------------------------------------
+template <typename T, bool VEC>
+__device__ __forceinline__ MovePair<T> move_load_pair(const T* src) {
+    if (VEC) return *reinterpret_cast<const MovePair<T>*>(src);
+    MovePair<T> r;
+    r.v[0] = src[0]; r.v[1] = src[1];
+    return r;
+}
+
+__device__ __forceinline__ unsigned scene_slot(const SceneMoveArgs& s, int cls, int arm, int k) {
+    return s.scenemap[((long)(cls * s.map_planes + (k >> 3)) * s.m.Bpad + arm) * 8 + (k & 7)];
+}
+
+// funnel / hemisphere k of one arm: six scalars into the slot's first quad and the first pair of its second
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_six_row(const SceneMoveArgs& s, int arm, int cls, const T* src, int k, int aux_plane) {
+    const long Qp = s.m.Bpad;
+    if (k >= s.m.S) return;
+    const unsigned gs = scene_slot(s, cls, arm, k);
+    if (gs + 1 >= (unsigned)s.m.S) return;        // MOVE_NONE: the arm has no k-th primitive of this class (a real one owns slots gs, gs + 1)
+    const MovePair<T> a = move_load_pair<T, VEC>(src), b = move_load_pair<T, VEC>(src + 2), c = move_load_pair<T, VEC>(src + 4);
+    if (a.v[0] != a.v[0]) return;                 // NaN: this primitive stays
+    MoveQuad<T> q;
+    q.v[0] = a.v[0]; q.v[1] = a.v[1]; q.v[2] = b.v[0]; q.v[3] = b.v[1];
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
+    g[0] = q;
+    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = c;
+    if (k == 0) {   // the arm's first funnel / hemisphere: the straight-line path reads it from the aux block
+        MoveQuad<T>* const x = static_cast<MoveQuad<T>*>(s.aux) + (long)aux_plane * Qp + arm;
+        x[0] = q;
+        reinterpret_cast<MovePair<T>*>(x + Qp)[0] = c;
+    }
+}
+
+// attractor k behind the goal block: rows 0..2 of its frame, p0..p11 of the general image's three slots
+template <typename T, bool VEC>
+__device__ __forceinline__ void move_att_row(const SceneMoveArgs& s, int arm, const T* src, int k) {
+    const long Qp = s.m.Bpad;
+    if (k >= s.m.S) return;
+    const unsigned gs = scene_slot(s, SCENE_ATT, arm, k);
+    if (gs + 2 >= (unsigned)s.m.S) return;        // MOVE_NONE (a real one owns slots gs .. gs + 2)
+    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
+    if (r0.v[0] != r0.v[0]) return;               // NaN: this attractor stays
+    MoveQuad<T> q;
+    MovePair<T> p45, p1011;
+    p45.v[0] = r1.v[0]; p45.v[1] = r1.v[1];
+    q.v[0] = r1.v[2]; q.v[1] = r1.v[3]; q.v[2] = r2.v[0]; q.v[3] = r2.v[1];
+    p1011.v[0] = r2.v[2]; p1011.v[1] = r2.v[3];
+    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
+    g[0] = r0;
+    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = p45;
+    g[2 * Qp] = q;
+    reinterpret_cast<MovePair<T>*>(g + 3 * Qp)[0] = p1011;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) move_scene_kernel(const SceneMoveArgs s) {
+    const MoveArgs& m = s.m;
+    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
+    const long j = arm - m.first_arm;
+    if (m.active && !m.active[j]) return;
+    int k = (int)blockIdx.y;
+    if (m.goal16) {
+        if (k == 0) {
+            move_goal_row<T, VEC>(m, arm, j);
+            return;
+        }
+        --k;
+    }
+    if (m.rep4) {
+        if (k < m.n_rep) {
+            move_rep_row<T, VEC>(m, arm, j, k);
+            return;
+        }
+        k -= m.n_rep;
+    }
+    if (s.fun6) {
+        if (k < s.n_fun) {
+            move_six_row<T, VEC>(s, arm, SCENE_FUN, static_cast<const T*>(s.fun6) + (j * s.n_fun + k) * 6, k, 0);
+            return;
+        }
+        k -= s.n_fun;
+    }
+    if (s.hem6) {
+        if (k < s.n_hem) {
+            move_six_row<T, VEC>(s, arm, SCENE_HEM, static_cast<const T*>(s.hem6) + (j * s.n_hem + k) * 6, k, 3);
+            return;
+        }
+        k -= s.n_hem;
+    }
+    if (s.att16 && k < s.n_att) move_att_row<T, VEC>(s, arm, static_cast<const T*>(s.att16) + (j * s.n_att + k) * 16, k);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The check after block k of a timed move -- `stride` control cycles that ran under gate[] and left the integrated joint angles in q_now: one
+// thread per arm, one kernel for two RULES (JOINT) and two TARGETS (LIST).
+// The Cartesian rule (vfik_goto, vfik_follow): the arrival check of the reference's "send a goal, then wait until the arm is there" calls
+//   (handlers.py:346-440: gotoFrame reads the object-0 entry of /dmonitor/distOut until pos_dist < goal_precision[0] and
+//   orient_dist * pi / 180 < goal_precision[1], handlers.py:374-381) on the goal_dist row the block left in `dist`.  Both compares STRICT, in
+//   double (NaN never arrives), and only while the arm is under way.  An arm without a goal block never arrives: its goal_dist is measured
+//   against the zero frame of an empty block (a tool near the origin would pass), so the block's `present` flag decides.
+// The joint rule (vfik_goto_js, vfik_follow_js): the wait of the reference's joint-space motion call, HandleJController.set_ref_js(js, wait,
+//   goal_precision) (handlers.py:544-576), which sends js to /jpctrl/ref and reads /bridge/encoders until
+//       ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
+//   and returns (result, js - q).  `ref` is the arm's row of the reference as the caller sent it (not the clamped value the controller keeps), q the
+//   row the block integrated.  Both edges are computed as written, in double on the io-typed values, both compares non-strict; NaN in q or in
+//   the row fails a compare, so it never arrives -- a row that starts with NaN (an arm without a controller) included.  diff = (T)(ref - q) for
+//   every arm that ran the block, also after it arrived or finished its list.  The precisions come by value and are indexed by the uniform
+//   loop counter alone: scalar loads from the kernel arguments.
+// One goal: arrived[b] = (k + 1) * stride - 1 at the arm's first successful check, the 0-based cycle whose tool pose / joint angles were measured.
+// A list (vfik_follow: a user of the reference sends a LIST of gotoFrame calls -- approach, grasp, lift, place -- each the moment the previous
+//   one returned true, handlers.py:346-387; vfik_follow_js: a script of set_ref_js calls -- home posture, pre-grasp posture, ...), way[B][W][16]
+//   or [B][W][n]: an arm found at item next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its list goes on -- the
+//   following item as its target.  A frame goes into its goal block: move_goal_row's three quad stores (lanes run over arms: a wave's stores to a
+//   plane lie in one 1 KiB row; plane 3 -- present, slow-down, force, speedScale -- stays), loaded as whole quads by the arriving lanes alone.  A
+//   posture goes into its row of `ref`, the reference row of the HANDLE that every block reads as io->q_ref, copied element by element from
+//   wayq, so the rule reads the posture as the caller sent it.  At most one item per check: the distance to the new goal exists only after the
+//   next block (gotoFrame drops its first read for the same reason, handlers.py:365-384), and the controller has not moved towards the new
+//   posture yet.
+//     precision    via_prec while an item follows, prec at the arm's last one (joint: and past it, last = next >= len - 1);
+//     way_now[b]   the item this check was made against: min(next, len - 1) on entry.
+//   One goal is a list of one item here: len = 1, next = arrived >= 0.
+// For every form:
+//   the arm did not run (gate[b] == 0): the cycle kernel stored nothing for it -- its q row and, in a trace, its distance and item-index rows
+//     repeat, it keeps its diff;
+//   next block's gate: the caller's && len > 0 && !(hold && next == len) -- with `hold` not once the arm arrived or finished its list;
+//   pending[k]: the arms that take part and have next < len -- a wave ballot, one atomic add per wave.
+// k < 0 (uniform): one goal: arrived = -1; a list: reached = -1, next = 0, len = leading rows of way[b] that do not start with NaN; the gate; and
+// item 0 into the goal block of every arm that takes part and has one, or into the arm's row of `ref` -- NaN for an arm that does not take part:
+// no controller, the io->q_ref convention.
+// Rows of n elements per lane, as the cycle kernel's q_out store; no LDS, no scratch, no register array.
+// The stall rule (vfik_set_stall_rule; StallArgs, vfik_kernel.h) is a compile-time switch of the body: check_stall_kernel and
+// script_stall_kernel carry it, check_kernel and script_kernel are the device code they were without it.
+// ------------------------------------------------------------------------------------------------
+// a quad as ONE value (a struct copy through MoveQuad would stay a 16 / 32-byte private object here: the frame's three loads come before the
+// stores they may alias); 16-byte aligned for either I/O type, which is what way16 and the planes guarantee
+template <typename T> struct FollowQuad { typedef T type __attribute__((ext_vector_type(4), aligned(16))); };
+
+template <typename T>
+__device__ __forceinline__ void follow_goal_store(T* goal, int b, long Qp, const T* frame) {
+    typedef typename FollowQuad<T>::type Quad;
+    const Quad* const src = reinterpret_cast<const Quad*>(frame);
+    Quad* const g = reinterpret_cast<Quad*>(goal) + b;
+    const Quad r0 = src[0], r1 = src[1], r2 = src[2];
+    g[0] = r0;
+    g[Qp] = r1;
+    g[2 * Qp] = r2;
+}
+
+// The stall rule's helpers (StallArgs, vfik_kernel.h).  NaN is never progress: every compare is strict, and the joint measure keeps a NaN.
+__device__ __forceinline__ void stall_reset(const StallArgs& st, int b) {
+    st.best[2 * (long)b] = __builtin_inf();
+    st.best[2 * (long)b + 1] = __builtin_inf();
+    st.count[b] = 0;
+}
+__device__ __forceinline__ double stall_max(double e, double v) { return (v > e || v != v) ? v : e; }
+// one evaluation for an arm that ran, is under way and did not arrive: true when this check declares it stalled
+__device__ __forceinline__ bool stall_step(const StallArgs& st, int b, bool joint, double m0, double m1, int cycle) {
+    double* const best = st.best + 2 * (long)b;
+    const double b0 = best[0], b1 = joint ? 0.0 : best[1];
+    const int c = st.count[b];
+    const bool p0 = m0 < b0 - (joint ? st.eps_js : st.eps_pos), p1 = !joint && m1 < b1 - st.eps_rot;
+    if (p0 || p1) {
+        best[0] = m0 < b0 ? m0 : b0;
+        if (!joint) best[1] = m1 < b1 ? m1 : b1;
+        st.count[b] = 0;
+        return false;
+    }
+    st.count[b] = c + 1;
+    if (c + 1 != st.patience) return false;
+    st.stalled[b] = cycle;
+    return true;
+}
+
+// check_kernel and script_kernel, then check_stall_kernel and script_stall_kernel: one text, compiled without and with the stall rule
+#define VFIK_STALL 0
+#include "vfik_check_body.inc"
+#undef VFIK_STALL
+#define VFIK_STALL 1
+#include "vfik_check_body.inc"
+#undef VFIK_STALL
+
+}  // namespace
+
+hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan_out) {
+    const bool ns = kargs.flags & VFIK_F_NULLSPACE;
+    const CyclePlan plan = plan_cycle(kargs, nj, io_dtype, ns, block);
+    if (plan_out) *plan_out = plan;
+    switch (nj) {
+#define X(n)                                                                                                                        \
+    case n:                                                                                                                         \
+        return io_dtype == 32 ? (ns ? launch_cycle_nj##n##_t32_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t32_ns0(kargs, plan, stream))  \
+                              : (ns ? launch_cycle_nj##n##_t64_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t64_ns0(kargs, plan, stream));
+        VFIK_NJ_LIST
+#undef X
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,
+                      void* out, hipStream_t stream) {
+    const int block = 256;
+    const dim3 grid((unsigned)((count + block - 1) / block)), blk(block);
+    if (io_dtype == 32)
+        hipLaunchKernelGGL(mix_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(cmds), w_dev, K, count,
+                           chan_stride, static_cast<float*>(out));
+    else
+        hipLaunchKernelGGL(mix_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(cmds), w_dev, K, count,
+                           chan_stride, static_cast<double*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_probe(int io_dtype, const void* pose, const void* goal, const void* slots, int B, long Bp, int slots_used,
+                        double rot_slow, double cos_slow, void* out, hipStream_t stream) {
+    const int block = 64;
+    const dim3 grid((B + block - 1) / block), blk(block);
+    if (io_dtype == 32)
+        hipLaunchKernelGGL(probe_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose), static_cast<const float*>(goal),
+                           static_cast<const float*>(slots), B, Bp, slots_used, rot_slow, cos_slow, static_cast<float*>(out));
+    else
+        hipLaunchKernelGGL(probe_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose), static_cast<const double*>(goal),
+                           static_cast<const double*>(slots), B, Bp, slots_used, rot_slow, cos_slow, static_cast<double*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active) {
+    const int block = 256;
+    const dim3 grid((unsigned)((count + block - 1) / block)), blk(block);
+    if (io_dtype == 32)
+        hipLaunchKernelGGL(monitor_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose),
+                           static_cast<const float*>(frames), O, count, static_cast<float*>(out), active);
+    else
+        hipLaunchKernelGGL(monitor_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
+                           static_cast<const double*>(frames), O, count, static_cast<double*>(out), active);
+    return hipGetLastError();
+}
+
+hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream) {
+    const int lanes = (m.first_arm & 63) + m.n_arms;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)((m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0))), blk(256);
+    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4) & 15u) == 0;
+    if (io_dtype == 32) {
+        if (vec) hipLaunchKernelGGL((move_kernel<float, true>), grid, blk, 0, stream, m);
+        else hipLaunchKernelGGL((move_kernel<float, false>), grid, blk, 0, stream, m);
+    } else {
+        if (vec) hipLaunchKernelGGL((move_kernel<double, true>), grid, blk, 0, stream, m);
+        else hipLaunchKernelGGL((move_kernel<double, false>), grid, blk, 0, stream, m);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream) {
+    const MoveArgs& m = s.m;
+    const int lanes = (m.first_arm & 63) + m.n_arms;
+    const int rows = (m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0) + (s.fun6 ? s.n_fun : 0) + (s.hem6 ? s.n_hem : 0) + (s.att16 ? s.n_att : 0);
+    if (rows < 1) return hipSuccess;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)rows), blk(256);
+    const size_t pair = io_dtype == 32 ? 8 : 16;
+    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4 | (uintptr_t)s.att16) & 15u) == 0 && (((uintptr_t)s.fun6 | (uintptr_t)s.hem6) & (pair - 1)) == 0;
+    if (io_dtype == 32) {
+        if (vec) hipLaunchKernelGGL((move_scene_kernel<float, true>), grid, blk, 0, stream, s);
+        else hipLaunchKernelGGL((move_scene_kernel<float, false>), grid, blk, 0, stream, s);
+    } else {
+        if (vec) hipLaunchKernelGGL((move_scene_kernel<double, true>), grid, blk, 0, stream, s);
+        else hipLaunchKernelGGL((move_scene_kernel<double, false>), grid, blk, 0, stream, s);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream) {
+    const int block = 256;
+    const dim3 grid((B + block - 1) / block), blk(block);
+    if (io_dtype == 32)
+        hipLaunchKernelGGL(track_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose), static_cast<const float*>(v6),
+                           state, static_cast<float*>(out), active, B);
+    else
+        hipLaunchKernelGGL(track_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
+                           static_cast<const double*>(v6), state, static_cast<double*>(out), active, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream, const StallArgs* st) {
+    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
+    auto launch = [&](auto t) {
+        typedef decltype(t) T;
+        if (st) {   // the handle has a stall rule
+            if (joint) {
+                if (list) hipLaunchKernelGGL((check_stall_kernel<T, true, true>), grid, blk, 0, stream, g, *st);
+                else hipLaunchKernelGGL((check_stall_kernel<T, true, false>), grid, blk, 0, stream, g, *st);
+            } else {
+                if (list) hipLaunchKernelGGL((check_stall_kernel<T, false, true>), grid, blk, 0, stream, g, *st);
+                else hipLaunchKernelGGL((check_stall_kernel<T, false, false>), grid, blk, 0, stream, g, *st);
+            }
+        } else if (joint) {
+            if (list) hipLaunchKernelGGL((check_kernel<T, true, true>), grid, blk, 0, stream, g);
+            else hipLaunchKernelGGL((check_kernel<T, true, false>), grid, blk, 0, stream, g);
+        } else {
+            if (list) hipLaunchKernelGGL((check_kernel<T, false, true>), grid, blk, 0, stream, g);
+            else hipLaunchKernelGGL((check_kernel<T, false, false>), grid, blk, 0, stream, g);
+        }
+    };
+    if (io_dtype == 32) launch(0.0f);
+    else launch(0.0);
+    return hipGetLastError();
+}
+
+hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream, const StallArgs* st) {
+    const dim3 grid((unsigned)((s.c.B + 255) / 256)), blk(256);
+    if (st) {   // the handle has a stall rule
+        if (io_dtype == 32) hipLaunchKernelGGL(script_stall_kernel<float>, grid, blk, 0, stream, s, *st);
+        else hipLaunchKernelGGL(script_stall_kernel<double>, grid, blk, 0, stream, s, *st);
+    } else if (io_dtype == 32) hipLaunchKernelGGL(script_kernel<float>, grid, blk, 0, stream, s);
+    else hipLaunchKernelGGL(script_kernel<double>, grid, blk, 0, stream, s);
+    return hipGetLastError();
+}
+}  // namespace vfik

@@ -1,4 +1,4 @@
-// vfik_check_body.inc -- the check kernels of the timed moves (vfik_kernel.hip, which describes them and includes this text twice): with
+// vfik_check_body.inc -- the check kernels of the timed moves (vfik_aux.hip, which describes them and includes this text twice): with
 // VFIK_STALL 0 it defines check_kernel<T, JOINT, LIST> and script_kernel<T>, with VFIK_STALL 1 check_stall_kernel and script_stall_kernel, which
 // take the handle's stall rule (StallArgs, vfik_kernel.h) as a second argument.  One text, two builds: STALL is a compile-time constant of the
 // body, and every statement of the rule sits in an `if constexpr (STALL)`, so the kernels without the rule stay the device code they were

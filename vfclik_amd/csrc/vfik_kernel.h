@@ -1,4 +1,5 @@
-// vfik_kernel.h -- kernel argument block shared by vfik_kernel.hip (device) and vfik_abi.cpp (host).
+// vfik_kernel.h -- kernel argument blocks, the launch plan and the type-erased launchers shared by vfik_kernel.hip, vfik_aux.hip (device) and
+// vfik_abi.cpp (host).  The chain's constants (KConst, kconst_fill, the DH patterns) are vfik_kconst.h, plain host code, included here.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -9,11 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/vfik_types.h"
-
-// joint counts the library is built for (one fully unrolled kernel each)
-#ifndef VFIK_NJ_LIST
-#define VFIK_NJ_LIST X(6) X(7) X(10) X(14)
-#endif
+#include "vfik_kconst.h"
 
 namespace vfik {
 
@@ -39,80 +36,7 @@ namespace vfik {
 //   lastvec               [(n + 4) / 4][Bpad] quads of FLOAT: the unique basis vector of the last cycle (n values), then
 //                                     sig as +-1 / +-2 (nullspace:91-92; vfik_kernel.hip); chains of up to 7 joints only
 //   ext                   [4][B][n]   last commands of mixer channels 2..5
-// Batch-shared constants: chain geometry, limits and parameters.  They live in DEVICE memory (one
-// copy per handle, rewritten only by vfik_set_chain / vfik_set_params) and are read through the
-// scalar cache; the kernarg block stays small.  Measured: with the 2.3 KB of constants inside the
-// kernarg segment every batch of s_loads was a long-latency fetch in the middle of the kinematics.
-template <int NJ>
-struct KConst {
-    // ---- kinematics block: copied into LDS by every wave (one or two 1-KiB requests) and read from
-    // there as vector operands.  As scalar (SGPR) operands the ~90 doubles did not fit the 100 SGPRs:
-    // the compiler hoisted every s_load to the top and spilled to VGPR lanes (v_writelane/readlane).
-    // Chain in Denavit-Hartenberg form, derived on the host from the z-normal form of vfik_chain
-    // (vfik_kernel.hip: kconst_fill_t): T_ee = base * prod_i [ Screw_z(q_i) Tx(a_i) Rx(alpha_i) ] * Screw_z(tail)
-    double base[12];  // B[0], row-major 3x4
-    // c = crev*cos(q+off) + cprs, s = crev*sin(q+off) + sprs, displacement = qd*q + d: revolute joints have
-    // (crev, cprs, sprs, qd) = (1, 0, 0, 0), prismatic ones (0, cos off, sin off, 1) -- arithmetic blends
-    struct DH { double off, crev, cprs, sprs, qd, d, a, ca, sa, pad; } dh[NJ];   // dh[0].pad: the batch's uniform repeller FORCE (below)
-    // dh[1].pad: 1 / rot_slow (0: no rotational slow-down), which every wave formed with rcp_nr until round 5.  In a pad, so that no member moves:
-    // as a member of its own behind cos_slow it moved every later member by 8 bytes, and a 14-joint general variant then spilled 52 B per lane.
-    // (That rot_slow lies in (0, pi/8) -- the short arctangent of rot_axis_angle -- the kernels read off cos_slow > cos(pi/8).)
-    double tail_c, tail_s, tail_e;  // trailing z-screw of the last fixed transform
-    // safe distance of every decay repeller of the batch when they all share one (and one force, dh[0].pad): the uniform repeller
-    // image of the straight-line path then carries (x y z radius) per slot only (vfik_scene.h: pack_fields, plan_scene)
-    double rep_safe;
-    // ---- everything else: read through the scalar cache.  Ordered by use on the lean paths: the first members share the 1-KiB
-    // rows that every wave copies to LDS for the kinematics block, so the L2 has them by the time the scalar loads ask -- with
-    // one handle after another (inputs from HBM) the first use of lambda2 / rot_slow cost the wave an HBM round trip (round 3).
-    double speed, lambda2, rot_slow, null_gain, lookahead, max_vel;
-    double cos_slow;  // cos(rot_slow): rotation angles with a smaller cosine need no atan2 (scalar = 1)
-    double jp_kp, jp_delta;  // joint P controller (joint_p_controller:55-57)
-    double jl_gain;          // gain of the joint-limit task (jl_k is jl_gain / half^2 of the STATIC limits; per-cycle limits use this)
-    double mix_w[VFIK_MIX_CHANNELS];
-    // shared tool frame (rows 0..2 of the 4x4; per-arm tools are a device array).  In the rows every wave copies to LDS: with the inputs
-    // cold a scalar load from the tail of the block is an HBM round trip of its own (measured on a flag there: C3 +7 %, profiles/r04_ab_tool.txt)
-    double tool[12];
-    double wy[6];    // the batch's IK weights (/weight, vf:295-309), in the copied rows for the same reason
-    double wq[NJ];
-    double q_lo[NJ];
-    double q_hi[NJ];
-    double q_mid[NJ];     // (lo + hi) / 2
-    double inv_half[NJ];  // 2 / (hi - lo)
-    double jl_k[NJ];      // jl_gain / half^2
-    unsigned prismatic_mask;
-    unsigned pad0;
-    static constexpr int KIN_BYTES = (12 + 10 * NJ + 4 + 10 + VFIK_MIX_CHANNELS + 12 + 6 + NJ) * 8;  // through wq: the block every wave copies to LDS
-    static constexpr int KIN_ROWS = (KIN_BYTES + 1023) / 1024;  // 1-KiB LDS rows / requests
-};
-// The device image of the constants is KConst<NJ> padded to a multiple of 1 KiB, then the 1-KiB sin / cos table
-// ((sin, cos)(k pi/32), k = 0..63) that every wave copies to LDS with the kinematics block.
-// where the host patches the uniform repeller pair into the device image (vfik_abi.cpp: write_uniform_pair)
-#define VFIK_KCONST_REP_FORCE_OFF ((12 + 9) * 8)
-#define VFIK_KCONST_ROT_SLOW_INV_OFF ((12 + 10 + 9) * 8)   // dh[1].pad: 1 / rot_slow
-#define VFIK_KCONST_REP_SAFE_OFF(nj) ((12 + 10 * (nj) + 3) * 8)
-static_assert(offsetof(KConst<7>, rep_safe) == VFIK_KCONST_REP_SAFE_OFF(7) && offsetof(KConst<14>, rep_safe) == VFIK_KCONST_REP_SAFE_OFF(14), "KConst::rep_safe");
-static_assert(offsetof(KConst<7>, dh) + offsetof(KConst<7>::DH, pad) == VFIK_KCONST_REP_FORCE_OFF, "KConst::dh[0].pad");
-static_assert(offsetof(KConst<7>, dh) + sizeof(KConst<7>::DH) + offsetof(KConst<7>::DH, pad) == VFIK_KCONST_ROT_SLOW_INV_OFF && offsetof(KConst<14>, dh) == offsetof(KConst<7>, dh), "KConst::dh[1].pad");
-static_assert(offsetof(KConst<7>, wq) + 7 * 8 == KConst<7>::KIN_BYTES && offsetof(KConst<14>, wq) + 14 * 8 == KConst<14>::KIN_BYTES, "KConst::wq closes the LDS-copied block");
-static_assert(KConst<7>::KIN_BYTES <= 1024 && KConst<6>::KIN_BYTES <= 1024 && KConst<10>::KIN_BYTES <= 2048 && KConst<14>::KIN_BYTES <= 2048, "the copied block keeps its row count");
-template <int NJ> struct KTab { static constexpr int OFFSET = ((int)sizeof(KConst<NJ>) + 1023) / 1024 * 1024; };
-
-// DH patterns the lean kernels are built for (cycle_body, DHP): per joint count, bit i of
-//   SWAP: link i has a = 0 and alpha = +pi/2 EXACTLY as the kernel sees it (ca == 0, sa == 1: the host snaps |ca| < 1e-15),
-//   NONE: a = 0 and alpha = 0 (ca == 1, sa == 0),     D0: the link's z-offset d is 0.
-// Pattern 1 per joint count: the KUKA LWR 4+ (vfclik's default robot), two of them in series (BASELINE's C5), the 6-joint arm of
-// robots.py.  A chain qualifies when its own masks contain the pattern's (kconst_fill reports them; vfik_abi.cpp decides).
-//   OFF0 / OFFPI: the joint's angle offset in the DH form is an even / odd multiple of pi (the joint angle itself enters the
-//   sin / cos, an odd multiple negates both),     BASE_I: the base frame B[0] is the identity (joint 1 starts from unit vectors).
-template <int NJ, int DHP> struct DhPattern { static constexpr unsigned SWAP = 0, NONE = 0, D0 = 0, OFF0 = 0, OFFPI = 0; static constexpr bool BASE_I = false; };
-template <> struct DhPattern<7, 1> { static constexpr unsigned SWAP = 0x3Fu, NONE = 0x40u, D0 = 0x2Au, OFF0 = 0x15u, OFFPI = 0x6Au; static constexpr bool BASE_I = true; };
-template <> struct DhPattern<14, 1> {
-    static constexpr unsigned SWAP = 0x1FBFu, NONE = 0x2040u, D0 = 0x152Au, OFF0 = 0xA95u, OFFPI = 0x356Au;
-    static constexpr bool BASE_I = true;
-};
-template <> struct DhPattern<6, 1> { static constexpr unsigned SWAP = 0x1Du, NONE = 0x20u, D0 = 0x16u, OFF0 = 0x27u, OFFPI = 0x18u; static constexpr bool BASE_I = true; };
-// the pattern id of a chain with these masks (0: none built for it)
-int dh_pattern_of(int nj, unsigned swap, unsigned none, unsigned d0, unsigned off0, unsigned offpi, bool base_identity);
+// (Batch-shared constants -- chain geometry, limits and parameters -- are KConst<NJ>: vfik_kconst.h.)
 
 // Per-wave LDS region of the cycle kernel (vfik_kernel.hip, cycle_body), by I/O type T.
 template <typename T> struct Stage {
@@ -238,12 +162,6 @@ struct KLean {
 constexpr int ONE5_BIT = 128;
 static_assert(sizeof(KArgs) == 352 && sizeof(KLean) == 56, "KArgs / KLean: the kernarg sizes the launch costs were measured with");
 
-// size of KConst<nj> for the host (0 if nj is not built); kconst_fill returns the largest
-// recomposition error of the DH conversion (the caller refuses a chain above 1e-9)
-size_t kconst_bytes(int nj);
-// fill a host image of KConst<nj> at dst
-double kconst_fill(int nj, void* dst, const vfik_chain& chain, const vfik_params& p, const double* tool12, int* plain, int* dhp = nullptr);
-
 // ------------------------------------------------------------------------------------------------
 // The launch plan of a control cycle: which kernel variant a launch takes, with which template arguments, grid, block and LDS.
 // Plain host code (no HIP call): vfik_kernel.hip's launcher maps a plan to its instantiation, tests/c_host/launch_plan.cpp prints it.
@@ -286,15 +204,6 @@ struct CyclePlan {
 // Whether an n_cycles > 0 launch runs as ONE in-kernel rollout (ROLL variants: PLAIN chains of up to 7 joints without shared options); else the
 // caller steps it cycle by cycle -- with a tool, IK weights or prismatic joints the loop-carried state no longer fits the registers.
 inline bool rollout_in_kernel(int nj, int plain) { return nj <= VFIK_ROLL_MAX_NJ && plain == 1; }
-
-inline bool has_dh_pattern(int nj) {
-    switch (nj) {
-#define X(n) case n: return DhPattern<n, 1>::SWAP != 0;
-        VFIK_NJ_LIST
-#undef X
-        default: return false;
-    }
-}
 
 // ---- what a launch asks for (KArgs), as the plan reads it
 // no per-arm option: tool, mixer weights, IK weights, extra mixer channels, joint controller, LWR command form, per-cycle limits
@@ -477,33 +386,7 @@ inline std::string cycle_kernel_name(const CyclePlan& p, int nj, int io_bits, bo
     }
 }
 
-// Whether a shared tool (rows 0..2 of the 4 x 4, row-major 3 x 4) can ride on the PLAIN kernels' TOOLC variants, which rebuild the lever arm
-// p_ee - p_tip = -Rt (Rtool^-1 t) and /pose_no_tool from the tool pose: its 3 x 3 block must be invertible to working accuracy --
-// max |Rtool Rtool^T - I| <= VFIK_TOOL_MAX_DEFECT (include/vfik.h states the rule); a block with a larger defect, a singular or a non-finite
-// one is not a plain + tool handle (kconst_fill then reports plain = 0: the general variants, which keep the flange frame).
-// c3 = Rtool^-1 t by cofactors in long double (zeros when the answer is no).  Host code.
-inline bool tool_block_serves_plain(const double* tool12, double* c3) {
-    const long double a = tool12[0], b = tool12[1], c = tool12[2], d = tool12[4], e = tool12[5], f = tool12[6], g = tool12[8], h = tool12[9], i = tool12[10];
-    const long double t[3] = {tool12[3], tool12[7], tool12[11]};
-    const long double co[9] = {e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d};
-    const long double det = a * co[0] + b * co[3] + c * co[6];
-    long double defect = 0.0L;
-    bool finite = true;
-    for (int r = 0; r < 3; ++r)
-        for (int k = 0; k < 3; ++k) {
-            long double s = r == k ? -1.0L : 0.0L;
-            for (int m = 0; m < 3; ++m) s += (long double)tool12[4 * r + m] * (long double)tool12[4 * k + m];
-            s = s < 0.0L ? -s : s;
-            finite = finite && s == s;
-            defect = s > defect ? s : defect;
-        }
-    const bool ok = finite && defect <= (long double)VFIK_TOOL_MAX_DEFECT && det != 0.0L;
-    for (int j = 0; j < 3; ++j) c3[j] = ok ? (double)((co[3 * j] * t[0] + co[3 * j + 1] * t[1] + co[3 * j + 2] * t[2]) / det) : 0.0;
-    return ok;
-}
-
-// Type-erased launchers (implemented in vfik_kernel.hip).  kargs points to a KArgs<nj>.
-uint32_t supported_joints_mask();
+// Type-erased launchers (implemented in vfik_aux.hip).  kargs points to a KArgs<nj>.
 // *plan (may be NULL) receives the launch's plan -- which instantiation it took (cycle_kernel_name), the eight-lanes-per-arm kernel among them
 hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan = nullptr);
 hipError_t launch_probe(int io_dtype, const void* pose, const void* goal, const void* slots, int B, long Bp, int slots_used,
@@ -544,7 +427,7 @@ struct SceneMoveArgs {
     int n_fun, n_hem, n_att, map_planes;
 };
 hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream);
-// The check that runs after block k of a timed move (check_kernel<T, JOINT, LIST>, vfik_kernel.hip), for all four forms: vfik_goto (Cartesian
+// The check that runs after block k of a timed move (check_kernel<T, JOINT, LIST>, vfik_aux.hip), for all four forms: vfik_goto (Cartesian
 // rule, one goal), vfik_follow (Cartesian rule, a LIST of goal frames), vfik_goto_js (joint rule, io->q_ref) and vfik_follow_js (joint rule, a LIST
 // of postures).  A list form's check that finds an arm at item next[b] notes the cycle in reached[b][next], advances next[b] and sends the arm
 // to the following item: its frame into the arm's goal block (move_goal_row's stores), or its posture into the arm's row of `ref`.
@@ -601,7 +484,7 @@ struct StallArgs {
 };
 // st == NULL: the builds without the rule
 hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream, const StallArgs* st = nullptr);
-// The check of a motion script (vfik_script; script_kernel<T>, vfik_kernel.hip): vfik_follow's state machine over a list whose items are goal
+// The check of a motion script (vfik_script; script_kernel<T>, vfik_aux.hip): vfik_follow's state machine over a list whose items are goal
 // frames or postures, kind[b][w] telling which.  `c` is read as a Cartesian list's check reads it -- way = way16, prec / via_prec = the distance
 // pair, ref = the handle's reference row, diff -- and the rest is the script's own: what the joint rule and the switch of controller need.
 // An arm found at step next[b] is sent to the following one: a frame into its goal block, a posture into its row of `ref`, and the mixer quad of

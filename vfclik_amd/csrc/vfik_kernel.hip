@@ -1,4 +1,4 @@
-// vfik_kernel.hip -- the fused control-cycle kernel for gfx950 (MI355X), one LANE per arm.
+// vfik_kernel.hip -- the fused control-cycle kernels for gfx950 (MI355X), one LANE per arm, and their launch plan's launcher.
 //
 // One launch = one control cycle of B arms = the loop bodies of the reference's per-arm processes:
 //   scripts/vf:311-347,455-466        q -> FK -> tool -> field -> twist -> RefPoint -> getIKV -> qdot
@@ -14,7 +14,9 @@
 // Small batches (a handful of arms with vfclik's default process set, up to 4 096 arms when the per-cycle rows are published or
 // no module runs) take cycle_sub8_kernel instead: eight lanes per arm, adopted where the same-box A/B wins.
 // Kernels of this file: cycle_kernel_s / cycle_kernel_x / cycle_kernel_m (variants by template: io type, joints, nullspace module, PLAIN,
-// rollout, field path, LEAN, compile-time flags, ...), cycle_sub8_kernel, mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, check_kernel, script_kernel.
+// rollout, field path, LEAN, compile-time flags, ...) and cycle_sub8_kernel.  The device building blocks they share with the auxiliary
+// kernels are vfik_device.h; mix_kernel, track_kernel, monitor_kernel, probe_kernel, move_kernel, move_scene_kernel, check_kernel,
+// script_kernel and the type-erased launch_* are vfik_aux.hip; the chain's constants (KConst, kconst_fill) are host code, vfik_kconst.h.
 // Which variant a launch takes is decided in ONE place, the launch plan (vfik_kernel.h: plan_cycle, plain host code); launch_plan at the end
 // of this file maps a plan to its instantiation.  Build-time switches: VFIK_STAMPS, VFIK_HEAVY_MIN_NJ, VFIK_NJ_LIST only -- the A/B
 // switches of earlier rounds are retired at their shipped values (profiles/ keeps the measurements; tools/build_variant.sh builds an A/B
@@ -36,670 +38,7 @@ void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, const KArgs&
 #endif
 namespace {
 
-constexpr double EPS_LEN = 1e-12;  // lengths below this are zero (unit vector := 0)
-constexpr double D_FLOOR = 1e-9;   // distance floor inside decay laws
-constexpr double MAG_CAP = 1e6;    // cap of a repeller's magnitude
-
-// ------------------------------------------------------------------------------------------------
-// float64 building blocks.  On gfx950 one wave per SIMD issues a float64 FMA about every 5 cycles
-// (8 when dependent), v_rcp/v_rsq_f64 take ~17-20, and the IEEE sequences the compiler emits for
-// `a / b`, sqrt() and sincos() cost ~65, ~90-110 and ~370 cycles (tools/ubench_fp64.hip).  The
-// control cycle needs none of their corner-case handling, so it uses Newton-refined reciprocals and
-// a branch-free sincos that the scheduler can interleave across the independent joints.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double rcp_nr(double x) {  // 1/x, ~1 ulp, x normal and non-zero
-    double y = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, y, 1.0);
-    y = __builtin_fma(y, e, y);
-    e = __builtin_fma(-x, y, 1.0);
-    return __builtin_fma(y, e, y);
-}
-
-// The flange rotation from the tool pose, Rf = Rt Rtool^-1 (tl: rows 0..2 of the tool, row-major 3 x 4), where /pose_no_tool recomposes it.
-// NOT Rt Rtool^T: a tool read from a float32 file or typed with four decimals is off a rotation by 5e-8 ... 1e-4, and the reference's frame
-// product (KDL) assumes nothing of the nine numbers.  The inverse by cofactors, then row by row: a row of Rt dies as its row of Rf is formed,
-// and the barriers keep the scheduler from interleaving the two phases (the long chains' variants have no registers for both at once).
-// Good to a few ulp times the block's condition number -- the published frame is held to 1e-9.  A block without an inverse gives non-finite values.
-__device__ __forceinline__ void flange_rotation(const double* Rt, const double* tl, double* Rf) {
-    const double a = tl[0], b = tl[1], c = tl[2], d = tl[4], e = tl[5], f = tl[6], g = tl[8], h = tl[9], i = tl[10];
-    double ti[9];
-    ti[0] = __builtin_fma(e, i, -(f * h)); ti[3] = __builtin_fma(f, g, -(d * i)); ti[6] = __builtin_fma(d, h, -(e * g));
-    const double r = rcp_nr(a * ti[0] + b * ti[3] + c * ti[6]);
-    ti[1] = __builtin_fma(c, h, -(b * i)); ti[2] = __builtin_fma(b, f, -(c * e));
-    ti[4] = __builtin_fma(a, i, -(c * g)); ti[5] = __builtin_fma(c, d, -(a * f));
-    ti[7] = __builtin_fma(b, g, -(a * h)); ti[8] = __builtin_fma(a, e, -(b * d));
-#pragma unroll
-    for (int k = 0; k < 9; ++k) ti[k] *= r;
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const double x = Rt[3 * q], y = Rt[3 * q + 1], z = Rt[3 * q + 2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Rf[3 * q + k] = x * ti[k] + y * ti[3 + k] + z * ti[6 + k];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// 1/sqrt(x) from ONE Newton step on v_rsq_f64 (5 instructions): the decay repellers' 1 / D, which is raised to the decay order (up to 127).
-// The step's error is measured directly by tools/ubench_rsqrt.hip (figures in DESIGN 6.2).  An error COMMON to the slots of one order is
-// a common factor of their terms and leaves a normalised sum unchanged but for the goal's share; tests/test_gpu_field_edges.py bounds
-// what the twist sees of it.  sqrt_rsqrt's two Goldschmidt steps (10 instructions) stay where the value itself is published.
-// x = 0 gives a large finite value.
-__device__ __forceinline__ double rsqrt_1nr(double x) {
-    const double y = __builtin_amdgcn_rsq(fmax(x, 1e-300));
-    const double e = __builtin_fma(-(x * y), y, 1.0);
-    return __builtin_fma(0.5 * y, e, y);
-}
-
-__device__ __forceinline__ double rsqrt_1nr_pos(double x) {   // ... for x > 0 known to the caller (no clamp)
-    const double y = __builtin_amdgcn_rsq(x);
-    const double e = __builtin_fma(-(x * y), y, 1.0);
-    return __builtin_fma(0.5 * y, e, y);
-}
-
-// 1/x from ONE Newton step on v_rcp_f64: the LDL^T pivots of the IK's normal matrix.  Measured on gfx950 (profiles/conditioning_accuracy.txt),
-// not assumed: the raw v_rcp_f64 is off by ~5e-9 relative (with it alone the joint velocities miss the reference by 5e7 cond u), so one step
-// leaves ~3e-17, under the rounding of its own last fma -- against the 50-digit reference (tests/test_gpu_conditioning.py) the joint
-// velocities are within 2.5 cond u at lambda = 0.1 and 2.1 cond u at lambda = 1e-2 and 1e-3 (cond up to 1.4e7, singular poses included),
-// cond = (sigma_1^2 + lambda^2) / (sigma_6^2 + lambda^2), u = 2^-53; rcp_nr's second step gives 2.1 at every lambda, the C oracle's
-// plain-double solve 0.5 - 1.5.  No bound on lambda or on cond enters: the test holds every lambda >= 0 it runs to 8 cond u.
-__device__ __forceinline__ double rcp_1nr(double x) {
-    const double y = __builtin_amdgcn_rcp(x);
-    return __builtin_fma(y, __builtin_fma(-x, y, 1.0), y);
-}
-
-// sqrt(x) and 1/sqrt(x) together (Goldschmidt from v_rsq_f64).  x = 0 gives (0, large finite).
-__device__ __forceinline__ void sqrt_rsqrt(double x, double& root, double& inv) {
-    const double y = __builtin_amdgcn_rsq(fmax(x, 1e-300));
-    double g = x * y, h = 0.5 * y;
-    double r = __builtin_fma(-g, h, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    r = __builtin_fma(-g, h, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    root = g;
-    inv = h + h;
-}
-
-// acc + x*w with the product and the sum rounded separately, as CPython evaluates
-// `result[i] += v[i] * w` (command_mixer.py:81).  HIP's __dmul_rn/__dadd_rn are plain operators that
-// the compiler may still fuse, so contraction is switched off for this statement block.
-__device__ __forceinline__ double mac_unfused(double acc, double x, double w) {
-#pragma clang fp contract(off)
-    const double prod = x * w;
-    return acc + prod;
-}
-
-__device__ __forceinline__ double mul_unfused(double x, double w) {
-#pragma clang fp contract(off)
-    return x * w;
-}
-
-// sin and cos: Cody-Waite reduction by pi/2 in three parts, then the classic minimax kernels on
-// [-pi/4, pi/4] (coefficients of fdlibm's __kernel_sin / __kernel_cos), < 1 ulp for |x| up to ~1e5 rad.
-// Joint angles live inside their limits (a few radians).  (The eight-lanes kernel's: not instantiated for the longer chains.)
-[[maybe_unused]] __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
-    const double k = __builtin_rint(x * 6.36619772367581382433e-01);
-    double r = __builtin_fma(-k, 1.57079632673412561417e+00, x);
-    r = __builtin_fma(-k, 6.07710050630396597660e-11, r);
-    r = __builtin_fma(-k, 2.02226624879595063154e-21, r);
-    const double z = r * r;
-    double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-    pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-    ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-    pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-    ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-    pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-    ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
-    pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
-    const double sr = __builtin_fma(z * r, ps, r);
-    const double cr = __builtin_fma(z * z, pc, __builtin_fma(z, -0.5, 1.0));
-    const int n = (int)k;
-    const double sv = (n & 1) ? cr : sr, cv = (n & 1) ? sr : cr;
-    s = (n & 2) ? -sv : sv;
-    c = ((n + 1) & 2) ? -cv : cv;
-}
-
-// The same for N independent arguments, written operation by operation across the N (structure-of-
-// arrays order): a lone wave issues a dependent float64 op every ~8 cycles but independent ones every
-// ~5, and the scheduler mostly keeps source order, so the source is laid out interleaved.
-template <int N>
-__device__ __forceinline__ void sincos_fast_n(const double* x, double* s, double* c) {
-    double k[N], r[N], z[N], ps[N], pc[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) k[i] = __builtin_rint(x[i] * 6.36619772367581382433e-01);
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 1.57079632673412561417e+00, x[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 6.07710050630396597660e-11, r[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 2.02226624879595063154e-21, r[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) z[i] = r[i] * r[i];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-        pc[i] = __builtin_fma(z[i], -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], ps[i], 2.75573137070700676789e-06);
-        pc[i] = __builtin_fma(z[i], pc[i], -2.75573143513906633035e-07);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], ps[i], -1.98412698298579493134e-04);
-        pc[i] = __builtin_fma(z[i], pc[i], 2.48015872894767294178e-05);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], ps[i], 8.33333333332248946124e-03);
-        pc[i] = __builtin_fma(z[i], pc[i], -1.38888888888741095749e-03);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], ps[i], -1.66666666666666324348e-01);
-        pc[i] = __builtin_fma(z[i], pc[i], 4.16666666666666019037e-02);
-    }
-    double zr[N], zz[N], hh[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) { zr[i] = z[i] * r[i]; zz[i] = z[i] * z[i]; hh[i] = __builtin_fma(z[i], -0.5, 1.0); }
-#pragma unroll
-    for (int i = 0; i < N; ++i) { ps[i] = __builtin_fma(zr[i], ps[i], r[i]); pc[i] = __builtin_fma(zz[i], pc[i], hh[i]); }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int n = (int)k[i];
-        const double sv = (n & 1) ? pc[i] : ps[i], cv = (n & 1) ? ps[i] : pc[i];
-        s[i] = (n & 2) ? -sv : sv;
-        c[i] = ((n + 1) & 2) ? -cv : cv;
-    }
-}
-
-// sin and cos of N independent arguments through a 64-entry table: x = k pi/32 + r, |r| <= pi/64, and
-//   sin x = S_k cos r + C_k sin r,   cos x = C_k cos r - S_k sin r
-// with (S_k, C_k) = (sin, cos)(k pi/32) read from the wave's LDS copy of the table (one 16-byte read per angle, index
-// k mod 64) and Taylor polynomials that are exact to the last bit on so short an interval (r^9/9! < 1e-16 r,
-// r^10/10! < 3e-20).  23 instructions an angle against 33 for the pi/2 reduction above, whose minimax kernels need
-// six coefficients each and a sign / swap selection by quadrant; ~2 ulp (the table entries are rounded).  pi/32 is
-// split into a 33-bit head, so that k * head is exact for |x| < 1e5 rad, and a tail.
-template <int N>
-__device__ __forceinline__ void sincos_tab_n(const double* x, const char* tab, double* s, double* c) {
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    // k = rint(x 32/pi) by the magic-number addition: x 32/pi + 1.5 2^52 rounds to an integer, whose low bits are the low dword of
-    // the sum (two's complement, |k| < 2^31) -- one fma and one and for the table index where rint, cvt_i32 and and were.
-    constexpr double MAGIC = 6755399441055744.0;
-    double k[N], r[N], z[N], ps[N], pc[N], S[N], C[N], km[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) km[i] = __builtin_fma(x[i], 10.185916357881302, MAGIC);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const d2 t = *reinterpret_cast<const d2*>(tab + ((unsigned)__double2loint(km[i]) & 63u) * 16);
-        S[i] = t.x; C[i] = t.y;
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) k[i] = km[i] - MAGIC;
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 0.09817477042088285, x[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-k[i], 3.79818781656637e-12, r[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) z[i] = r[i] * r[i];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], -1.98412698412698412698e-04, 8.33333333333333333333e-03);
-        pc[i] = __builtin_fma(z[i], 2.48015873015873015873e-05, -1.38888888888888888889e-03);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        ps[i] = __builtin_fma(z[i], ps[i], -1.66666666666666666667e-01);
-        pc[i] = __builtin_fma(z[i], pc[i], 4.16666666666666666667e-02);
-    }
-    double zr[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) { zr[i] = z[i] * r[i]; pc[i] = __builtin_fma(z[i], pc[i], -0.5); }
-#pragma unroll
-    for (int i = 0; i < N; ++i) { ps[i] = __builtin_fma(zr[i], ps[i], r[i]); pc[i] = __builtin_fma(z[i], pc[i], 1.0); }  // sin r, cos r
-#pragma unroll
-    for (int i = 0; i < N; ++i) { s[i] = S[i] * pc[i]; c[i] = C[i] * pc[i]; }
-#pragma unroll
-    for (int i = 0; i < N; ++i) { s[i] = __builtin_fma(C[i], ps[i], s[i]); c[i] = __builtin_fma(-S[i], ps[i], c[i]); }
-}
-
-// N independent 1/sqrt(x), operation by operation (x = 0 gives a large finite value)
-template <int N>
-__device__ __forceinline__ void rsqrt_n(const double* x, double* inv) {
-    double y[N], g[N], h[N], r[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = __builtin_amdgcn_rsq(fmax(x[i], 1e-300));
-#pragma unroll
-    for (int i = 0; i < N; ++i) { g[i] = x[i] * y[i]; h[i] = 0.5 * y[i]; }
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-g[i], h[i], 0.5);
-#pragma unroll
-    for (int i = 0; i < N; ++i) { g[i] = __builtin_fma(g[i], r[i], g[i]); h[i] = __builtin_fma(h[i], r[i], h[i]); }
-#pragma unroll
-    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(-g[i], h[i], 0.5);
-#pragma unroll
-    for (int i = 0; i < N; ++i) inv[i] = 2.0 * __builtin_fma(h[i], r[i], h[i]);
-}
-
-// x^n, n a wave-uniform small non-negative integer: square-and-multiply with scalar control flow
-__device__ __forceinline__ double powi_uniform(double x, int n) {
-    double r = 1.0, b = x;
-    while (n) {
-        if (n & 1) r *= b;
-        n >>= 1;
-        if (n) b *= b;
-    }
-    return r;
-}
-
-// x^order for x > 0.  Decay orders are small integers in every message the reference sends
-// (object_feeder:277,279,302; README.old:75 uses 20): multiply chain when we can, pow() otherwise.
-__device__ __forceinline__ double pow_order(double x, double order) {
-    const int n = (int)order;
-    const bool isint = (double)n == order && n >= 0 && n < 128;
-    if (__all(isint)) {
-        const int n0 = __builtin_amdgcn_readfirstlane(n);
-        if (__all(n == n0)) return powi_uniform(x, n0);
-        double r = 1.0, b = x;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-            r = (n & (1 << k)) ? r * b : r;
-            b = b * b;
-        }
-        return r;
-    }
-    return isint ? powi_uniform(x, n) : pow(x, order);
-}
-
-// atan(t), |t| <= tan(pi/8): fdlibm's 11-coefficient kernel (s_atan.c, good to < 1 ulp for |t| < 7/16)
-__device__ __forceinline__ double atan_kernel(double t) {
-    const double z = t * t, w = z * z;
-    const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
-                      w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
-    const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
-                      w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
-    return t - t * (s1 + s2);
-}
-
-// atan2(y, x) for y >= 0 (an angle in [0, pi]), branch-free: two reductions bring the argument of the
-// arctangent below tan(pi/8), where atan_kernel (above) is good to < 1 ulp.
-// ocml's atan2 costs a lone wave ~2 000 cycles (tools/stamps.py: the waves that needed it ended the kernel
-// 0.4 us after the rest); this is ~45 instructions.
-__device__ __forceinline__ double atan2_pos(double y, double x) {
-    const double ax = fabs(x);
-    const bool steep = y > ax;                         // angle from the nearer axis: t in [0, 1]
-    const double num = steep ? ax : y, den = steep ? y : ax;
-    double t = den > 0.0 ? num * rcp_nr(den) : 0.0;    // atan2(0, 0) = 0
-    const bool upper = t > 0.41421356237309503;        // tan(pi/8): atan(t) = pi/4 + atan((t - 1) / (t + 1))
-    const double tr = (t - 1.0) * rcp_nr(t + 1.0);
-    t = upper ? tr : t;
-    double a = atan_kernel(t);
-    a = upper ? 0.78539816339744830962 + a : a;        // angle from the nearer axis, in [0, pi/4]
-    a = steep ? 1.57079632679489661923 - a : a;        // angle from the x axis of (|x|, y)
-    return x < 0.0 ? 3.14159265358979323846 - a : a;
-}
-
-// Unit rotation axis (base frame) and angle of the rotation taking R to G, i.e. of log(G R^T) =
-// KDL diff(R, G).rot.  Branch-free main line; the half-turn neighbourhood (sin(theta) < 1e-4, cos < 0),
-// where the antisymmetric part vanishes, is fixed up from the symmetric part under a wave-uniform
-// test.  The angle itself is only needed below the slow-down angle: `need_theta` (wave-uniform) says
-// whether any lane can be that close; otherwise theta is reported as pi (any value >= rot_slow does).
-// A slow-down angle below pi/8 (cos_slow > cos(pi/8); the default is 0.3) makes that evaluation short: a lane inside the angle has
-// s / c <= tan(rot_slow) < tan(pi/8), so neither reduction of atan2_pos can fire for it -- its second reciprocal, the selects and
-// the three additions go, the lane's own operations stay as they were (bit for bit); a lane outside the angle keeps pi.  The waves
-// that get here end the launch: one in eleven of a batch of random goals has such a lane, and every launch waits for its slowest wave.
-// This takes s^2 + c^2 = 1, i.e. goal and tool rotations that ARE rotations (float32 rounding of the goal moves s / c by 1e-7).  A scaled
-// or skewed goal matrix can have c > cos_slow with s / c above tan(pi/8): atan_kernel is then off its interval (still < 1 ulp up
-// to 7/16, degrading beyond), where atan2_pos reduced any (s, c); the value feeds min(1, theta / rot_slow) alone.
-// (SHORT = false: without that short evaluation -- the general field path's variants, which sit at their register limit)
-template <bool SHORT>
-__device__ __forceinline__ void rot_axis_angle(const double* R, const double* G, double cos_slow, double* axis, double& theta,
-                                               bool& has_axis) {
-    double E[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) E[3 * i + j] = G[3 * i] * R[3 * j] + G[3 * i + 1] * R[3 * j + 1] + G[3 * i + 2] * R[3 * j + 2];
-    const double a0 = 0.5 * (E[7] - E[5]), a1 = 0.5 * (E[2] - E[6]), a2 = 0.5 * (E[3] - E[1]);
-    const double c = 0.5 * (E[0] + E[4] + E[8] - 1.0);
-    double s, sinv;
-    sqrt_rsqrt(a0 * a0 + a1 * a1 + a2 * a2, s, sinv);
-    axis[0] = a0 * sinv; axis[1] = a1 * sinv; axis[2] = a2 * sinv;
-    has_axis = s >= EPS_LEN;
-    theta = 3.14159265358979323846;
-    if (__any(c > cos_slow)) {  // some lane is within the slow-down angle
-        if (SHORT && cos_slow > 0.92387953251128674) {  // cos(pi/8): wave-uniform
-            const double th = atan_kernel(s * rcp_nr(c));
-            theta = c > cos_slow ? th : theta;
-        } else {
-            theta = atan2_pos(s, c);
-        }
-    }
-    const bool half_turn = s < 1e-4 && c < 0.0;
-    if (__any(half_turn)) {
-        // theta near pi (4 arms in 65 536 random goals): the axis comes from the symmetric part,
-        // (E + E^T)/2 - c I = (1 - c) a a^T, whose row with the largest diagonal element is parallel to a;
-        // the sign from the (small) antisymmetric part.  Selects, one rsqrt: the waves that get here
-        // used to end the kernel 0.3 us after the others through three divergent branches with divisions.
-        const bool k0 = E[0] >= E[4] && E[0] >= E[8], k1 = !k0 && E[4] >= E[8];
-        const double s01 = 0.5 * (E[1] + E[3]), s02 = 0.5 * (E[2] + E[6]), s12 = 0.5 * (E[5] + E[7]);
-        double x = k0 ? E[0] - c : (k1 ? s01 : s02);
-        double y = k0 ? s01 : (k1 ? E[4] - c : s12);
-        double z = k0 ? s02 : (k1 ? s12 : E[8] - c);
-        const double flip = (x * a0 + y * a1 + z * a2 < 0.0) ? -1.0 : 1.0;
-        double nn, k;
-        sqrt_rsqrt(x * x + y * y + z * z, nn, k);
-        k *= flip;
-        if (half_turn) {
-            axis[0] = x * k; axis[1] = y * k; axis[2] = z * k;
-            has_axis = true;
-            // pi - atan(s / |c|), s / |c| < 1.0001e-4: atan(t) = t - t^3 / 3 to 2e-21, within an ulp of pi of atan2_pos(s, c)
-            const double t = s * rcp_nr(-c);
-            theta = 3.14159265358979323846 - t * __builtin_fma(t * t, -3.33333333333333333333e-01, 1.0);
-        }
-    }
-}
-
-// type 1, point attractor: G = goal rotation (9) + position (3); adds force*vector to tot, scales sc.
-// `on` masks the whole contribution (goal block absent): selects instead of a branch.
-// SHORT (the straight-line variants and the eight-lanes kernel): rot_axis_angle's short arctangent, and 1 / rot_slow from the caller
-// (`rot_slow_inv`: the batch constant); without it the reciprocal is formed here and the argument is not read.
-template <bool SHORT = true>
-__device__ __forceinline__ void attractor(const double* R, const double* p, const double* GR, const double* Gp,
-                                          double slow, double force, double rot_slow, double cos_slow, bool on,
-                                          double* tot, double* sc, double* dist = nullptr, double rot_slow_inv = 0.0) {
-    const double dx = Gp[0] - p[0], dy = Gp[1] - p[1], dz = Gp[2] - p[2];
-    double D, Dinv;
-    sqrt_rsqrt(dx * dx + dy * dy + dz * dz, D, Dinv);
-    const double kt = (on && D > EPS_LEN) ? force * Dinv : 0.0;
-    tot[0] += dx * kt; tot[1] += dy * kt; tot[2] += dz * kt;
-    double ax[3], th;
-    bool has_axis;
-    rot_axis_angle<SHORT>(R, GR, cos_slow, ax, th, has_axis);
-    const bool rot_on = on && has_axis && th > EPS_LEN;  // selects, not a multiply by 0: an absent goal's axis may be NaN
-    tot[3] += rot_on ? ax[0] * force : 0.0; tot[4] += rot_on ? ax[1] * force : 0.0; tot[5] += rot_on ? ax[2] * force : 0.0;
-    const double s0 = slow > 0.0 ? fmin(1.0, D * rcp_nr(slow)) : 1.0;
-    const double s1 = rot_slow > 0.0 ? fmin(1.0, th * (SHORT ? rot_slow_inv : rcp_nr(rot_slow))) : 1.0;
-    sc[0] *= on ? s0 : 1.0;
-    sc[1] *= on ? s1 : 1.0;
-    if (dist) { dist[0] = D; dist[1] = th; }
-}
-
-// Element e (0..7) of slot m of this lane's arm in the quad-plane layout (vfik_kernel.h): plane
-// 2m + e/4, component e%4.  sq points at plane 0, component 0 of the lane's arm; Q = plane pitch in
-// elements (4 * Bpad).
-template <typename T>
-__device__ __forceinline__ double slot_elem(const T* sq, long Q, int m, int e) {
-    return (double)sq[(long)(2 * m + (e >> 2)) * Q + (e & 3)];
-}
-
-// One field slot of any type, read from memory (the general path: mixed primitive types in a wave,
-// fractional decay orders, more slots than the prefetch window).
-// `rd(m, e)` = element e of slot m: SlotGlobal reads the quad planes in memory, SlotLds the rows staged in LDS.
-template <typename RD>
-__device__ void eval_slot(const RD& rd, int m, const double* Rt, const double* pt, double rot_slow, double cos_slow,
-                          double* tot, double* sc) {
-    const int type = (int)rd(m, 7);
-    if (type <= 0) return;
-    const double p0 = rd(m, 0), p1 = rd(m, 1), p2 = rd(m, 2),
-                 p3 = rd(m, 3), p4 = rd(m, 4), p5 = rd(m, 5),
-                 force = rd(m, 6);
-    if (type == VFIK_FIELD_REPELLER) {  // x y z radius safeDist order
-        const double dx = p0 - pt[0], dy = p1 - pt[1], dz = p2 - pt[2];
-        double D, Dinv;
-        sqrt_rsqrt(dx * dx + dy * dy + dz * dz, D, Dinv);
-        Dinv = D < D_FLOOR ? 1.0 / D_FLOOR : Dinv;
-        const double mag = fmin(pow_order((p3 + p4) * Dinv, p5), MAG_CAP);
-        const double k = force * mag * Dinv;
-        tot[0] += dx * k; tot[1] += dy * k; tot[2] += dz * k;
-    } else if (type == VFIK_FIELD_HEMISPHERE) {  // x y z nx ny nz | safeDist order
-        const double safe = rd(m + 1, 0), order = rd(m + 1, 1);
-        double nn, ninv;
-        sqrt_rsqrt(p3 * p3 + p4 * p4 + p5 * p5, nn, ninv);
-        if (nn > EPS_LEN) {
-            const double h = ((pt[0] - p0) * p3 + (pt[1] - p1) * p4 + (pt[2] - p2) * p5) * ninv;
-            const double mag = fmin(pow_order(safe * rcp_nr(fmax(h, D_FLOOR)), order), MAG_CAP);
-            const double k = -force * mag * ninv;
-            tot[0] += p3 * k; tot[1] += p4 * k; tot[2] += p5 * k;
-        }
-    } else if (type == VFIK_FIELD_FUNNEL) {  // x y z ax ay az | cutAngle angleOrder cutDist distOrder
-        const double cutA = rd(m + 1, 0), ordA = rd(m + 1, 1),
-                     cutD = rd(m + 1, 2), ordD = rd(m + 1, 3);
-        double an, ainv;
-        sqrt_rsqrt(p3 * p3 + p4 * p4 + p5 * p5, an, ainv);
-        if (an > EPS_LEN) {
-            const double ax = p3 * ainv, ay = p4 * ainv, az = p5 * ainv;
-            const double wx = pt[0] - p0, wy = pt[1] - p1, wz = pt[2] - p2;
-            const double along = wx * ax + wy * ay + wz * az;
-            const double ex = wx - along * ax, ey = wy - along * ay, ez = wz - along * az;
-            double P, Pinv, dist, dinv;
-            sqrt_rsqrt(ex * ex + ey * ey + ez * ez, P, Pinv);
-            sqrt_rsqrt(wx * wx + wy * wy + wz * wz, dist, dinv);
-            Pinv = P < D_FLOOR ? 1.0 / D_FLOOR : Pinv;
-            dinv = dist < D_FLOOR ? 1.0 / D_FLOOR : dinv;
-            const double phi = atan2_pos(P, along);
-            const double ga = cutA > 0.0 ? fmin(1.0, pow_order(phi * rcp_nr(cutA), ordA)) : 1.0;
-            const double gd = fmin(1.0, pow_order(cutD * dinv, ordD));
-            const double k = -force * ga * gd * Pinv;
-            tot[0] += ex * k; tot[1] += ey * k; tot[2] += ez * k;
-        }
-    } else if (type == VFIK_FIELD_ATTRACTOR) {  // a second attractor: frame16 + slow over 3 slots
-        double GR[9], Gp[3];
-        GR[0] = p0; GR[1] = p1; GR[2] = p2; Gp[0] = p3; GR[3] = p4; GR[4] = p5;
-        GR[5] = rd(m + 1, 0); Gp[1] = rd(m + 1, 1);
-        GR[6] = rd(m + 1, 2); GR[7] = rd(m + 1, 3); GR[8] = rd(m + 1, 4);
-        Gp[2] = rd(m + 1, 5);
-        attractor<false>(Rt, pt, GR, Gp, rd(m + 2, 4), force, rot_slow, cos_slow, true, tot, sc);
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// Nullspace module, chains of up to 7 joints (scripts/nullspace:75-117), shared by cycle_kernel and cycle_sub8_kernel.
-// In: Jm = the Jacobian by columns (destroyed: its rows are orthonormalised in place), the arm's sign memory
-// (lv_r = lastvec, sig_r = sig, has_vec: lastvec holds a vector), c0 = /control[0], jl_task + descent(z) = the
-// joint-limit task's direction.  Out: qn = move_in_nullspace (+ the projected joint-limit task), before check_limits and
-// the gain; status bits; returns true when the sign memory was advanced (a unique nullspace direction exists).
-// Every decision is taken PER LANE (per arm): which path an arm takes never depends on the other arms of its wave, so
-// its result does not depend on where in a batch it sits (wave-wide votes only decide whether a path is executed at all).
-// ------------------------------------------------------------------------------------------------
-// ZFIRST / ZLAST: the Jacobian's first column is (x, y, 0, 0, 0, 1) / its last column (0, 0, 0, z) -- structural zeros of the chain's DH
-// pattern (cycle_body: jzero).  The Gram-Schmidt pass tracks which entries are still exactly zero (a compile-time table once the loops are
-// unrolled) and skips their terms: the last column's linear part stays zero to the end, the first column's zeros fill in at the first
-// two steps -- 44 of the module's ~550 operations.
-template <int NJ, bool ZFIRST = false, bool ZLAST = false, typename ZF>
-__device__ __forceinline__ bool nullspace_core(double (&Jm)[NJ][6], double* lv_r, int& sig_r, bool& has_vec, double c0, bool jl_task,
-                                               ZF&& descent, double* qn, int& status) {
-    // Orthonormal basis (rows) of the row space of J by modified Gram-Schmidt, in place in Jm:
-    // afterwards I - Q^T Q is restrict(I6, J) = I - pinv(J) J (nullspace:75-79).
-    // One pass: loss of orthogonality ~ eps * cond(J), far below the 1e-6 bar wherever J is usable.
-    // Right-looking order: once row s is normalised, the projections of ALL later rows onto it are
-    // independent chains (5, 4, ... of them) that a lone wave can interleave; row by row (left-looking) the
-    // same operations are one serial chain of 7-term dot products (dependent float64 ops issue every ~8
-    // cycles, independent ones every ~5).  Same arithmetic, same order per row: same results.
-    bool Z[NJ][6];   // entry (column i, row r) of J is still structurally zero
-#pragma unroll
-    for (int i = 0; i < NJ; ++i)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) Z[i][r] = (ZFIRST && i == 0 && (r == 2 || r == 3 || r == 4)) || (ZLAST && i == NJ - 1 && r < 3);
-    int rank = 0;
-    double n0[6];  // squared norms of the rows of J: the rank test's yardstick
-#pragma unroll
-    for (int r = 0; r < 6; ++r) n0[r] = 0.0;
-#pragma unroll
-    for (int i = 0; i < NJ; ++i)
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-            if (!Z[i][r]) n0[r] = __builtin_fma(Jm[i][r], Jm[i][r], n0[r]);
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        double n1 = 0.0;
-        if (s == 0) {
-            n1 = n0[0];  // nothing has been projected out of the first row
-        } else {
-#pragma unroll
-            for (int i = 0; i < NJ; ++i)
-                if (!Z[i][s]) n1 += Jm[i][s] * Jm[i][s];
-        }
-        const bool keep = n1 > 1e-24 * n0[s] && n0[s] > 0.0;
-        double n1r, n1i;
-        sqrt_rsqrt(n1, n1r, n1i);
-        const double inv = keep ? n1i : 0.0;
-        rank += keep ? 1 : 0;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i)
-            if (!Z[i][s]) Jm[i][s] *= inv;
-        double c[6];
-#pragma unroll
-        for (int r = s + 1; r < 6; ++r) c[r] = 0.0;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i)
-#pragma unroll
-            for (int r = s + 1; r < 6; ++r)
-                if (!Z[i][s] && !Z[i][r]) c[r] += Jm[i][s] * Jm[i][r];
-#pragma unroll
-        for (int i = 0; i < NJ; ++i)
-#pragma unroll
-            for (int r = s + 1; r < 6; ++r) {
-                if (Z[i][s]) continue;                 // nothing of row s in this column
-                if (Z[i][r]) { Jm[i][r] = -(c[r] * Jm[i][s]); Z[i][r] = false; }
-                else Jm[i][r] -= c[r] * Jm[i][s];
-            }
-    }
-    const int nullity = NJ - rank;
-    bool advanced = false;
-    if (nullity == 1) {
-        double u[NJ];
-        // u <- (I - Q^T Q) u: all six coefficients first (independent dot products), then the update (classical
-        // Gram-Schmidt against an orthonormal Q); returns the largest |coefficient| = how much of u was row space
-        auto project = [&](double* x) {
-            double c[6];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) c[r] = 0.0;
-#pragma unroll
-            for (int i = 0; i < NJ; ++i)
-#pragma unroll
-                for (int r = 0; r < 6; ++r)
-                    if (!Z[i][r]) c[r] += Jm[i][r] * x[i];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int i = 0; i < NJ; ++i)
-                    if (!Z[i][r]) x[i] -= c[r] * Jm[i][r];
-            double cm = fabs(c[0]);
-#pragma unroll
-            for (int r = 1; r < 6; ++r) cm = fmax(cm, fabs(c[r]));
-            return cm;
-        };
-        auto norm2 = [&](const double* x) {
-            double n = 0.0;
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) n += x[i] * x[i];
-            return n;
-        };
-        double nn = 0.0;
-        // Warm start: the nullspace direction turns little between two control cycles, so last cycle's vector
-        // (the sign memory, nullspace:92,104) is projected instead of a unit vector: no search for the best
-        // unit vector, and ONE projection suffices when it removes little (its residual row-space part is
-        // ~ eps cond(J) times what was removed).  An arm without a usable previous vector (first cycle, a
-        // jump that leaves less than half of it) takes the cold path below.
-        bool warm = false;
-        if (__any(has_vec)) {  // (a stored vector is a unit vector)
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) u[i] = lv_r[i];
-            const double cm = project(u);
-            nn = norm2(u);
-            warm = has_vec && nn > 0.25;
-            const bool again = warm && cm > 1e-2;  // a real move: project once more, as the cold path does
-            if (__any(again)) {
-                double u2[NJ];
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) u2[i] = u[i];
-                project(u2);
-                const double nn2 = norm2(u2);
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) u[i] = again ? u2[i] : u[i];
-                nn = again ? nn2 : nn;
-            }
-        }
-        if (__any(!warm)) {
-            // cold: the normalised column of the projector with the largest diagonal, projected twice
-            double dg[NJ], uc[NJ];
-            double best = -1.0;
-            int ib = 0;
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) dg[i] = 1.0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) dg[i] -= Jm[i][r] * Jm[i][r];
-#pragma unroll
-            for (int i = 0; i < NJ; ++i)
-                if (dg[i] > best) { best = dg[i]; ib = i; }
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) uc[i] = (i == ib) ? 1.0 : 0.0;
-            project(uc);  // twice: the second pass squares the residual
-            project(uc);
-            const double nnc = norm2(uc);
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) u[i] = warm ? u[i] : uc[i];
-            nn = warm ? nn : nnc;
-        }
-        double nrm, ninv;
-        sqrt_rsqrt(nn, nrm, ninv);
-        // All three sign decisions are taken on the un-normalised u and applied with the normalisation, in one
-        // multiplication per joint.  (1) The raw vector v as LAPACK's SVD leaves it: the first component that is
-        // not negligible (|v_i| > 1e-9 of the unit vector) is negative (oracle + golden).
-        const double thr = 1e-9 * nrm;
-        bool found = false, negate = false;  // negate: v = -u / |u|
-#pragma unroll
-        for (int i = 0; i < NJ; ++i)
-            if (!found && fabs(u[i]) > thr) { found = true; negate = u[i] > 0.0; }
-        // (2) sign continuity against the previous cycle (nullspace:101-105): sig flips when sig v is farther from
-        // lastvec than -sig v; |sig v - l|^2 - |sig v + l|^2 = -4 sig (v . l), so only the sign of v . l counts
-        double dot = 0.0;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) dot += u[i] * lv_r[i];
-        int sig = sig_r;
-        const double vl = negate ? -dot : dot;
-        if ((sig < 0 ? -vl : vl) < 0.0) sig = -sig;
-        sig_r = sig;
-        has_vec = true;
-        const double k = (negate != (sig < 0)) ? -ninv : ninv;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) {
-            u[i] *= k;
-            lv_r[i] = u[i];
-            qn[i] = u[i] * c0;  // move_in_nullspace (nullspace:113-117): min(n, 4, 1) = 1 row
-        }
-        advanced = true;
-    } else if (nullity >= 2) {
-        status |= VFIK_ST_NULL_AMBIGUOUS;  // SVD basis not unique: /control cannot be honoured
-    }
-    if (jl_task) {
-        double z[NJ];
-        descent(z);
-        double c[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) c[r] = 0.0;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i)
-#pragma unroll
-            for (int r = 0; r < 6; ++r) c[r] += Jm[i][r] * z[i];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) z[i] -= c[r] * Jm[i][r];
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) qn[i] += z[i];
-    }
-    return advanced;
-}
+#include "vfik_device.h"
 
 // ------------------------------------------------------------------------------------------------
 // Staging through LDS (direct global -> LDS loads, no VGPR destination).  Every lane's inputs of
@@ -756,11 +95,7 @@ __device__ __forceinline__ void read_quad(const char* region, int off, int lane,
     }
 }
 
-// slot readers for eval_slot
-template <typename T> struct SlotGlobal {
-    const T* sq; long Q;  // plane 0, component 0 of this lane's arm; plane pitch in elements
-    __device__ __forceinline__ double operator()(int m, int e) const { return slot_elem(sq, Q, m, e); }
-};
+// slot reader for eval_slot: the wave's staging region (SlotGlobal, the quad planes in global memory: vfik_device.h)
 template <typename T> struct SlotLds {
     const char* region; int lane; int nj;  // the wave's staging region: slot m sits in slot quads 2m, 2m + 1 (m < PRE)
     __device__ __forceinline__ double operator()(int m, int e) const {
@@ -2384,446 +1719,6 @@ cycle_kernel_m(const void* base, const void* q, void* qdot_out, const int* activ
     cycle_body<T, NJ, NULLSP, true, false, true, LEAN, -1, FUN, 1, false, true, DHP>(a);
 }
 
-// CommandMixer.read's weighted sum alone (command_mixer.py:78-82): out = sum_k cmd[k] * w[k], left to
-// right from 0.0, multiply and add rounded separately (what CPython does).
-template <typename T>
-__global__ void __launch_bounds__(256) mix_kernel(const T* cmds, const double* w, int K, long count, long chan_stride, T* out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    double acc = 0.0;
-    for (int k = 0; k < K; ++k) acc = mac_unfused(acc, (double)cmds[k * chan_stride + i], w[k]);
-    out[i] = (T)acc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Tracking-error estimator of scripts/vf (vf:349-428), batched, as its own small kernel (a diagnostic:
-// it never feeds qdot).  Per arm it keeps the previous tool frame, the last 4 commanded twists and a
-// frame counter; from the 6th frame on (frame_list longer than 5, vf:354) it compares the twist
-// MEASURED between the two latest frames, scaled by the assumed 150 Hz robot loop (vf:408-411), with
-// the twist COMMANDED check_delay = 4 cycles earlier (vf:363): direction angles, corrected magnitudes,
-// |difference| and arm_tracking = difference < 0.10.  state: [38][B] doubles (12 frame, 24 commands,
-// count, -).  out: [B][8] = vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr,
-// cmd_vel_mag_corr, cmd_rot_mag_corr, ext_int_diff, arm_tracking (vf:418-427); zeros until the 6th frame.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) track_kernel(const T* pose, const T* v6, double* st, T* out, const int* active, int B) {
-    const int arm = blockIdx.x * blockDim.x + threadIdx.x;
-    if (arm >= B) return;
-    if (active && !active[arm]) return;  // inside vf's `if qInBottle` (vf:312-313,349): no fresh q, no new frame
-    const long Bs = B;
-    double F[12], P[12], cmd[4][6];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) { F[k] = (double)pose[(long)arm * 16 + k]; P[k] = st[k * Bs + arm]; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) cmd[j][k] = st[(12 + 6 * j + k) * Bs + arm];
-    const double cnt = st[36 * Bs + arm];  // frames seen before this one
-    // cmd_buffer.append(...); keep the last 4 (vf:350-352): after the shift cmd[0] is the oldest
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) cmd[j][k] = cmd[j + 1][k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) cmd[3][k] = (double)v6[(long)arm * 6 + k];
-    double res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (cnt >= 5.0) {  // len(frame_list) > frame_list_size (vf:354)
-        // ext_diff = PyKDL.diff(previous frame, this frame): vel = dp, rot = log(R_b R_a^T) in the base frame
-        double ev[3] = {F[3] - P[3], F[7] - P[7], F[11] - P[11]};
-        double Ra[9], Rb[9], ax[3], th;
-        bool has_axis;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { Ra[3 * r + c] = P[4 * r + c]; Rb[3 * r + c] = F[4 * r + c]; }
-        rot_axis_angle<false>(Ra, Rb, -2.0, ax, th, has_axis);
-        const double ext_vel_mag = sqrt(ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2]);
-        const double ext_rot_mag = has_axis ? th : 0.0;
-        // the command issued check_delay = 4 cycles ago is the oldest entry of the full buffer (vf:363)
-        const double* c = cmd[0];
-        const double cmd_vel_mag = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-        const double cmd_rot_mag = sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]);
-        double eu[3] = {1, 0, 0}, cu[3] = {1, 0, 0}, er[3] = {1, 0, 0}, cr[3] = {1, 0, 0};  // vf:365-374,390-399
-        if (ext_vel_mag > 0.0) for (int k = 0; k < 3; ++k) eu[k] = ev[k] / ext_vel_mag;
-        if (cmd_vel_mag > 0.0) for (int k = 0; k < 3; ++k) cu[k] = c[k] / cmd_vel_mag;
-        if (ext_rot_mag > 0.0) for (int k = 0; k < 3; ++k) er[k] = ax[k];
-        if (cmd_rot_mag > 0.0) for (int k = 0; k < 3; ++k) cr[k] = c[3 + k] / cmd_rot_mag;
-        const double vd = fmin(1.0, fmax(-1.0, cu[0] * eu[0] + cu[1] * eu[1] + cu[2] * eu[2]));
-        const double rd = fmin(1.0, fmax(-1.0, cr[0] * er[0] + cr[1] * er[1] + cr[2] * er[2]));
-        res[0] = fabs(acos(vd));
-        res[1] = fabs(acos(rd));
-        res[2] = ext_vel_mag * 150.0;   // loop_freq (vf:408)
-        res[3] = ext_rot_mag * 150.0;
-        res[4] = cmd_vel_mag;
-        res[5] = cmd_rot_mag / 5.0;     // vf:412
-        res[6] = fabs((res[4] + res[5]) - (res[2] + res[3]));
-        res[7] = res[6] < 0.10 ? 1.0 : 0.0;  // tracking_th (vf:409,416)
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) out[(long)arm * 8 + k] = (T)res[k];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) st[k * Bs + arm] = F[k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) st[(12 + 6 * j + k) * Bs + arm] = cmd[j][k];
-    st[36 * Bs + arm] = cnt + 1.0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Distance monitor of scripts/monitor_distance (monitor_distance:76-84,148-167), batched: for every arm
-// and every object frame it was told about (/dmonitor/objectsIn: the goal is object 0, obstacles
-// follow), the xyz distance between the tool pose and the object and the rotation angle between their
-// orientations, in DEGREES (orientLength = |diff(current, final).rot| * 180/pi).  One thread per
-// (arm, object); pose [B][16], frames [B][O][16], out [B][O][2].  A diagnostic: it never feeds qdot.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) monitor_kernel(const T* pose, const T* frames, int O, long count, T* out, const int* active) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const long arm = t / O;
-    if (active && !active[arm]) return;  // no fresh q, no new pose (monitor_distance:138-147 acts on a pose that ARRIVED): the rows stay
-    double P[12], F[12];
-    const T* pp = pose + arm * 16;
-    const T* fp = frames + t * 16;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) { P[k] = (double)pp[k]; F[k] = (double)fp[k]; }
-    const double dx = P[3] - F[3], dy = P[7] - F[7], dz = P[11] - F[11];
-    // relative rotation E = R_cur^T R_obj; its angle is what |diff().rot| measures
-    double E[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) E[3 * i + j] = P[i] * F[j] + P[4 + i] * F[4 + j] + P[8 + i] * F[8 + j];
-    const double a0 = 0.5 * (E[7] - E[5]), a1 = 0.5 * (E[2] - E[6]), a2 = 0.5 * (E[3] - E[1]);
-    const double c = 0.5 * (E[0] + E[4] + E[8] - 1.0);
-    const double sn = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
-    out[2 * t] = (T)sqrt(dx * dx + dy * dy + dz * dz);
-    out[2 * t + 1] = (T)(atan2_pos(sn, c) * 57.295779513082320877);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Field probe of scripts/vf (vf:469-503, "for visualizing"): the arm's total field evaluated at a pose that
-// is handed in (/pose_in) instead of the forward kinematics: v6 = speedScale * scalars * normCart(sum)
-// (vf:491-494 = vf:344-347 at another frame).  One thread per arm; goal block and slots are read straight
-// from the quad planes through the general per-slot path.  pose [B][16], out [B][6].
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) probe_kernel(const T* pose, const T* goal, const T* slots, int B, long Bp, int slots_used,
-                                                    double rot_slow, double cos_slow, T* out) {
-    const int arm = blockIdx.x * blockDim.x + threadIdx.x;
-    if (arm >= B) return;
-    double Rt[9], pt[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Rt[3 * r + c] = (double)pose[(long)arm * 16 + 4 * r + c];
-        pt[r] = (double)pose[(long)arm * 16 + 4 * r + 3];
-    }
-    const long Qp = Bp * 4;
-    double gq[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) gq[k] = (double)goal[(long)(k >> 2) * Qp + (long)arm * 4 + (k & 3)];
-    double tot[6] = {0, 0, 0, 0, 0, 0}, sc[2] = {1.0, 1.0};
-    double GR[9], Gp[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) GR[3 * r + c] = gq[4 * r + c];
-        Gp[r] = gq[4 * r + 3];
-    }
-    attractor<false>(Rt, pt, GR, Gp, gq[13], gq[14], rot_slow, cos_slow, gq[12] != 0.0, tot, sc, nullptr);
-    const T* sq = slots + (long)arm * 4;
-    const SlotGlobal<T> rg{sq, Qp};
-    for (int m = 0; m < slots_used; ++m) eval_slot(rg, m, Rt, pt, rot_slow, cos_slow, tot, sc);
-    double nt, nti, nr, nri;
-    sqrt_rsqrt(tot[0] * tot[0] + tot[1] * tot[1] + tot[2] * tot[2], nt, nti);
-    sqrt_rsqrt(tot[3] * tot[3] + tot[4] * tot[4] + tot[5] * tot[5], nr, nri);
-    const double speed = gq[15];
-    const double kt = nt > EPS_LEN ? speed * sc[0] * nti : 0.0;
-    const double kr = nr > EPS_LEN ? speed * sc[1] * nri : 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        out[(long)arm * 6 + k] = (T)(tot[k] * kt);
-        out[(long)arm * 6 + 3 + k] = (T)(tot[3 + k] * kr);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// vfik_move_fields (ABI 6): goals and obstacles that move (object_feeder:214-354 re-sends an object's primitives with new coordinates
-// whenever its pose changes: the goal frame, object_feeder:229-241; x y z radius of the point obstacles and the near-goal repeller,
-// object_feeder:317-334).  One thread per (arm, primitive): lanes run over arms -- aligned to the planes' 64-quad rows, so that every
-// plane write of a wave is one contiguous 1 KiB (2 KiB at float64 I/O) -- and blockIdx.y over the primitives: the goal frame when
-// one is given, then decay repeller k of the caller's rows.  Every image a later launch may read gets the new numbers:
-//   goal block   rows 0..2 of the frame (plane 3 -- present, slow-down, force, speedScale -- stays),
-//   uniform      plane k + 1: the whole quad (x y z radius),
-//   compact      (x0 y0 z0 r0 | s0 f0 x1 y1 | z1 r1 s1 f1): the even slot's first quad; the odd slot's two half quads (s f stay),
-//   general      first plane of the slot repmap names (p0..p3 = x y z radius; p4 p5 force type stay).
-// Rows from the arm's repeller count on find MOVE_NONE in the map and write nothing: an unused slot keeps its -inf radius / zero force.
-// Plain vector stores, no LDS, no loop, no register array.  VEC: the caller's arrays are 16-byte aligned (whole-quad loads).
-// ------------------------------------------------------------------------------------------------
-template <typename T> struct alignas(16) MoveQuad { T v[4]; };
-template <typename T> struct alignas(2 * sizeof(T)) MovePair { T v[2]; };
-
-template <typename T, bool VEC>
-__device__ __forceinline__ MoveQuad<T> move_load(const T* src) {
-    if (VEC) return *reinterpret_cast<const MoveQuad<T>*>(src);
-    MoveQuad<T> r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r.v[e] = src[e];
-    return r;
-}
-
-// the goal frame of one arm: rows 0..2 into the goal block's first three planes
-template <typename T, bool VEC>
-__device__ __forceinline__ void move_goal_row(const MoveArgs& m, int arm, long j) {
-    const long Qp = m.Bpad;  // quads per plane
-    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(m.goal) + arm;
-    if (g[3 * Qp].v[0] == (T)0) return;   // no goal block: the row is ignored
-    const T* src = static_cast<const T*>(m.goal16) + j * 16;
-    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
-    if (r0.v[0] != r0.v[0]) return;       // NaN: this goal stays
-    g[0] = r0;
-    g[Qp] = r1;
-    g[2 * Qp] = r2;
-}
-
-// decay repeller k of one arm: x y z radius into the uniform, the compact and the general image
-template <typename T, bool VEC>
-__device__ __forceinline__ void move_rep_row(const MoveArgs& m, int arm, long j, int k) {
-    const long Qp = m.Bpad;
-    if (k >= m.n_rep || k >= m.S) return;
-    const unsigned gs = m.repmap[((long)(k >> 3) * m.Bpad + arm) * 8 + (k & 7)];
-    if (gs >= (unsigned)m.S) return;              // MOVE_NONE: the arm has no k-th decay repeller
-    const MoveQuad<T> r = move_load<T, VEC>(static_cast<const T*>(m.rep4) + (j * m.n_rep + k) * 4);
-    if (r.v[0] != r.v[0]) return;                 // NaN: this repeller stays
-    static_cast<MoveQuad<T>*>(m.slots_uni)[(long)(k + 1) * Qp + arm] = r;
-    static_cast<MoveQuad<T>*>(m.slots)[(long)(2 * gs) * Qp + arm] = r;
-    MoveQuad<T>* const f = static_cast<MoveQuad<T>*>(m.slots_fast) + (long)(3 * (k >> 1)) * Qp + arm;
-    if (!(k & 1)) {
-        f[0] = r;
-    } else {
-        MovePair<T> lo, hi;
-        lo.v[0] = r.v[0]; lo.v[1] = r.v[1]; hi.v[0] = r.v[2]; hi.v[1] = r.v[3];
-        reinterpret_cast<MovePair<T>*>(f + Qp)[1] = lo;
-        reinterpret_cast<MovePair<T>*>(f + 2 * Qp)[0] = hi;
-    }
-}
-
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) move_kernel(const MoveArgs m) {
-    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
-    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
-    const long j = arm - m.first_arm;
-    if (m.active && !m.active[j]) return;
-    int k = (int)blockIdx.y;
-    if (m.goal16) {
-        if (k == 0) {
-            move_goal_row<T, VEC>(m, arm, j);
-            return;
-        }
-        --k;
-    }
-    move_rep_row<T, VEC>(m, arm, j, k);
-}
-
-// ------------------------------------------------------------------------------------------------
-// vfik_move_scene: the rest of what the object feeder re-sends for an object that moves -- the approach funnel of `set goalAndNormal`
-// (object_feeder:248-303), the surface of `set ObstacleH` (object_feeder:335-354) -- and attractors behind the goal block.  The same
-// thread mapping as move_kernel; blockIdx.y runs over the goal frame, the caller's repeller rows, then its funnel, hemisphere and attractor
-// rows (the class of a block is uniform: scalar branches).  Goal and repellers: move_kernel's stores.  The new classes live in the general
-// image (and the aux block), whose slots keep p0..p5 | force type in two planes:
-//   funnel / hemisphere k, general slot gs   plane 2 gs <- the quad x y z ax; plane 2 gs + 1 <- its FIRST pair ay az (force, type stay);
-//                                            k = 0 also aux planes 0, 1 (funnel) or 3, 4 (hemisphere), laid out alike (cutAngle
-//                                            angleOrder / safe order in the second pair stay);
-//   attractor k, general slot gs             planes 2 gs, 2 gs + 1 (pair), 2 gs + 2, 2 gs + 3 (pair) <- p0..p11; slot gs + 2 (frame row 3,
-//                                            slow-down distance) stays.
-// A wave's pair stores cover the first 8 of every 16 bytes of one contiguous 1-KiB row (2 KiB at float64 I/O): every 128-byte line of the row
-// is touched by ONE instruction -- byte-masked in L2, no line split between instructions -- as move_kernel's odd compact-image slots already are.
-// Rows of six are 8-byte aligned at float32: pair loads (VEC: the caller's 6-rows are pair aligned, its 4- and 16-rows quad aligned).
-// ------------------------------------------------------------------------------------------------
-template <typename T, bool VEC>
-__device__ __forceinline__ MovePair<T> move_load_pair(const T* src) {
-    if (VEC) return *reinterpret_cast<const MovePair<T>*>(src);
-    MovePair<T> r;
-    r.v[0] = src[0]; r.v[1] = src[1];
-    return r;
-}
-
-__device__ __forceinline__ unsigned scene_slot(const SceneMoveArgs& s, int cls, int arm, int k) {
-    return s.scenemap[((long)(cls * s.map_planes + (k >> 3)) * s.m.Bpad + arm) * 8 + (k & 7)];
-}
-
-// funnel / hemisphere k of one arm: six scalars into the slot's first quad and the first pair of its second
-template <typename T, bool VEC>
-__device__ __forceinline__ void move_six_row(const SceneMoveArgs& s, int arm, int cls, const T* src, int k, int aux_plane) {
-    const long Qp = s.m.Bpad;
-    if (k >= s.m.S) return;
-    const unsigned gs = scene_slot(s, cls, arm, k);
-    if (gs + 1 >= (unsigned)s.m.S) return;        // MOVE_NONE: the arm has no k-th primitive of this class (a real one owns slots gs, gs + 1)
-    const MovePair<T> a = move_load_pair<T, VEC>(src), b = move_load_pair<T, VEC>(src + 2), c = move_load_pair<T, VEC>(src + 4);
-    if (a.v[0] != a.v[0]) return;                 // NaN: this primitive stays
-    MoveQuad<T> q;
-    q.v[0] = a.v[0]; q.v[1] = a.v[1]; q.v[2] = b.v[0]; q.v[3] = b.v[1];
-    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
-    g[0] = q;
-    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = c;
-    if (k == 0) {   // the arm's first funnel / hemisphere: the straight-line path reads it from the aux block
-        MoveQuad<T>* const x = static_cast<MoveQuad<T>*>(s.aux) + (long)aux_plane * Qp + arm;
-        x[0] = q;
-        reinterpret_cast<MovePair<T>*>(x + Qp)[0] = c;
-    }
-}
-
-// attractor k behind the goal block: rows 0..2 of its frame, p0..p11 of the general image's three slots
-template <typename T, bool VEC>
-__device__ __forceinline__ void move_att_row(const SceneMoveArgs& s, int arm, const T* src, int k) {
-    const long Qp = s.m.Bpad;
-    if (k >= s.m.S) return;
-    const unsigned gs = scene_slot(s, SCENE_ATT, arm, k);
-    if (gs + 2 >= (unsigned)s.m.S) return;        // MOVE_NONE (a real one owns slots gs .. gs + 2)
-    const MoveQuad<T> r0 = move_load<T, VEC>(src), r1 = move_load<T, VEC>(src + 4), r2 = move_load<T, VEC>(src + 8);
-    if (r0.v[0] != r0.v[0]) return;               // NaN: this attractor stays
-    MoveQuad<T> q;
-    MovePair<T> p45, p1011;
-    p45.v[0] = r1.v[0]; p45.v[1] = r1.v[1];
-    q.v[0] = r1.v[2]; q.v[1] = r1.v[3]; q.v[2] = r2.v[0]; q.v[3] = r2.v[1];
-    p1011.v[0] = r2.v[2]; p1011.v[1] = r2.v[3];
-    MoveQuad<T>* const g = static_cast<MoveQuad<T>*>(s.m.slots) + (long)(2 * gs) * Qp + arm;
-    g[0] = r0;
-    reinterpret_cast<MovePair<T>*>(g + Qp)[0] = p45;
-    g[2 * Qp] = q;
-    reinterpret_cast<MovePair<T>*>(g + 3 * Qp)[0] = p1011;
-}
-
-template <typename T, bool VEC>
-__global__ void __launch_bounds__(256) move_scene_kernel(const SceneMoveArgs s) {
-    const MoveArgs& m = s.m;
-    const int arm = (m.first_arm & ~63) + (int)(blockIdx.x * 256 + threadIdx.x);
-    if (arm < m.first_arm || arm >= m.first_arm + m.n_arms) return;
-    const long j = arm - m.first_arm;
-    if (m.active && !m.active[j]) return;
-    int k = (int)blockIdx.y;
-    if (m.goal16) {
-        if (k == 0) {
-            move_goal_row<T, VEC>(m, arm, j);
-            return;
-        }
-        --k;
-    }
-    if (m.rep4) {
-        if (k < m.n_rep) {
-            move_rep_row<T, VEC>(m, arm, j, k);
-            return;
-        }
-        k -= m.n_rep;
-    }
-    if (s.fun6) {
-        if (k < s.n_fun) {
-            move_six_row<T, VEC>(s, arm, SCENE_FUN, static_cast<const T*>(s.fun6) + (j * s.n_fun + k) * 6, k, 0);
-            return;
-        }
-        k -= s.n_fun;
-    }
-    if (s.hem6) {
-        if (k < s.n_hem) {
-            move_six_row<T, VEC>(s, arm, SCENE_HEM, static_cast<const T*>(s.hem6) + (j * s.n_hem + k) * 6, k, 3);
-            return;
-        }
-        k -= s.n_hem;
-    }
-    if (s.att16 && k < s.n_att) move_att_row<T, VEC>(s, arm, static_cast<const T*>(s.att16) + (j * s.n_att + k) * 16, k);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The check after block k of a timed move -- `stride` control cycles that ran under gate[] and left the integrated joint angles in q_now: one
-// thread per arm, one kernel for two RULES (JOINT) and two TARGETS (LIST).
-// The Cartesian rule (vfik_goto, vfik_follow): the arrival check of the reference's "send a goal, then wait until the arm is there" calls
-//   (handlers.py:346-440: gotoFrame reads the object-0 entry of /dmonitor/distOut until pos_dist < goal_precision[0] and
-//   orient_dist * pi / 180 < goal_precision[1], handlers.py:374-381) on the goal_dist row the block left in `dist`.  Both compares STRICT, in
-//   double (NaN never arrives), and only while the arm is under way.  An arm without a goal block never arrives: its goal_dist is measured
-//   against the zero frame of an empty block (a tool near the origin would pass), so the block's `present` flag decides.
-// The joint rule (vfik_goto_js, vfik_follow_js): the wait of the reference's joint-space motion call, HandleJController.set_ref_js(js, wait,
-//   goal_precision) (handlers.py:544-576), which sends js to /jpctrl/ref and reads /bridge/encoders until
-//       ((js - goal_precision) <= q) * ((js + goal_precision) >= q)).all()
-//   and returns (result, js - q).  `ref` is the arm's row of the reference as the caller sent it (not the clamped value the controller keeps), q the
-//   row the block integrated.  Both edges are computed as written, in double on the io-typed values, both compares non-strict; NaN in q or in
-//   the row fails a compare, so it never arrives -- a row that starts with NaN (an arm without a controller) included.  diff = (T)(ref - q) for
-//   every arm that ran the block, also after it arrived or finished its list.  The precisions come by value and are indexed by the uniform
-//   loop counter alone: scalar loads from the kernel arguments.
-// One goal: arrived[b] = (k + 1) * stride - 1 at the arm's first successful check, the 0-based cycle whose tool pose / joint angles were measured.
-// A list (vfik_follow: a user of the reference sends a LIST of gotoFrame calls -- approach, grasp, lift, place -- each the moment the previous
-//   one returned true, handlers.py:346-387; vfik_follow_js: a script of set_ref_js calls -- home posture, pre-grasp posture, ...), way[B][W][16]
-//   or [B][W][n]: an arm found at item next[b] gets reached[b][next] = (k + 1) * stride - 1 and next + 1, and -- if its list goes on -- the
-//   following item as its target.  A frame goes into its goal block: move_goal_row's three quad stores (lanes run over arms: a wave's stores to a
-//   plane lie in one 1 KiB row; plane 3 -- present, slow-down, force, speedScale -- stays), loaded as whole quads by the arriving lanes alone.  A
-//   posture goes into its row of `ref`, the reference row of the HANDLE that every block reads as io->q_ref, copied element by element from
-//   wayq, so the rule reads the posture as the caller sent it.  At most one item per check: the distance to the new goal exists only after the
-//   next block (gotoFrame drops its first read for the same reason, handlers.py:365-384), and the controller has not moved towards the new
-//   posture yet.
-//     precision    via_prec while an item follows, prec at the arm's last one (joint: and past it, last = next >= len - 1);
-//     way_now[b]   the item this check was made against: min(next, len - 1) on entry.
-//   One goal is a list of one item here: len = 1, next = arrived >= 0.
-// For every form:
-//   the arm did not run (gate[b] == 0): the cycle kernel stored nothing for it -- its q row and, in a trace, its distance and item-index rows
-//     repeat, it keeps its diff;
-//   next block's gate: the caller's && len > 0 && !(hold && next == len) -- with `hold` not once the arm arrived or finished its list;
-//   pending[k]: the arms that take part and have next < len -- a wave ballot, one atomic add per wave.
-// k < 0 (uniform): one goal: arrived = -1; a list: reached = -1, next = 0, len = leading rows of way[b] that do not start with NaN; the gate; and
-// item 0 into the goal block of every arm that takes part and has one, or into the arm's row of `ref` -- NaN for an arm that does not take part:
-// no controller, the io->q_ref convention.
-// Rows of n elements per lane, as the cycle kernel's q_out store; no LDS, no scratch, no register array.
-// The stall rule (vfik_set_stall_rule; StallArgs, vfik_kernel.h) is a compile-time switch of the body: check_stall_kernel and
-// script_stall_kernel carry it, check_kernel and script_kernel are the device code they were without it.
-// ------------------------------------------------------------------------------------------------
-// a quad as ONE value (a struct copy through MoveQuad would stay a 16 / 32-byte private object here: the frame's three loads come before the
-// stores they may alias); 16-byte aligned for either I/O type, which is what way16 and the planes guarantee
-template <typename T> struct FollowQuad { typedef T type __attribute__((ext_vector_type(4), aligned(16))); };
-
-template <typename T>
-__device__ __forceinline__ void follow_goal_store(T* goal, int b, long Qp, const T* frame) {
-    typedef typename FollowQuad<T>::type Quad;
-    const Quad* const src = reinterpret_cast<const Quad*>(frame);
-    Quad* const g = reinterpret_cast<Quad*>(goal) + b;
-    const Quad r0 = src[0], r1 = src[1], r2 = src[2];
-    g[0] = r0;
-    g[Qp] = r1;
-    g[2 * Qp] = r2;
-}
-
-// The stall rule's helpers (StallArgs, vfik_kernel.h).  NaN is never progress: every compare is strict, and the joint measure keeps a NaN.
-__device__ __forceinline__ void stall_reset(const StallArgs& st, int b) {
-    st.best[2 * (long)b] = __builtin_inf();
-    st.best[2 * (long)b + 1] = __builtin_inf();
-    st.count[b] = 0;
-}
-__device__ __forceinline__ double stall_max(double e, double v) { return (v > e || v != v) ? v : e; }
-// one evaluation for an arm that ran, is under way and did not arrive: true when this check declares it stalled
-__device__ __forceinline__ bool stall_step(const StallArgs& st, int b, bool joint, double m0, double m1, int cycle) {
-    double* const best = st.best + 2 * (long)b;
-    const double b0 = best[0], b1 = joint ? 0.0 : best[1];
-    const int c = st.count[b];
-    const bool p0 = m0 < b0 - (joint ? st.eps_js : st.eps_pos), p1 = !joint && m1 < b1 - st.eps_rot;
-    if (p0 || p1) {
-        best[0] = m0 < b0 ? m0 : b0;
-        if (!joint) best[1] = m1 < b1 ? m1 : b1;
-        st.count[b] = 0;
-        return false;
-    }
-    st.count[b] = c + 1;
-    if (c + 1 != st.patience) return false;
-    st.stalled[b] = cycle;
-    return true;
-}
-
-// check_kernel and script_kernel, then check_stall_kernel and script_stall_kernel: one text, compiled without and with the stall rule
-#define VFIK_STALL 0
-#include "vfik_check_body.inc"
-#undef VFIK_STALL
-#define VFIK_STALL 1
-#include "vfik_check_body.inc"
-#undef VFIK_STALL
-
 // ------------------------------------------------------------------------------------------------
 // EIGHT LANES PER ARM (small batches): the mapping BASELINE.json's north_star sketches -- an arm spread over the lanes of
 // a (sub-)wave with cross-lane exchange -- for what vfclik itself runs: a handful of arms (scripts/vfclik:88-105), each
@@ -3406,11 +2301,13 @@ hipError_t launch_plan(const KArgs& a_in, const CyclePlan& p, hipStream_t stream
 
 }  // namespace
 
-// The library is built from this one source compiled several times (csrc/Makefile): per joint count, I/O type and with / without the
-// nullspace module with -DVFIK_ONLY_NJ=<n> -DVFIK_ONLY_T=<32|64> -DVFIK_ONLY_NS=<0|1> (the kernels of that combination, in parallel make
-// jobs: sixteen objects of 20-70 kernels each instead of four of 85-160), once per long chain with -DVFIK_HEAVY_PART, and once with
-// -DVFIK_DISPATCH (the launch plan's dispatch, mixer kernel, host-side constant preparation).
-#ifdef VFIK_ONLY_NJ
+// The library's cycle kernels are built from this one source compiled several times (csrc/Makefile): per joint count, I/O type and with /
+// without the nullspace module with -DVFIK_ONLY_NJ=<n> -DVFIK_ONLY_T=<32|64> -DVFIK_ONLY_NS=<0|1> (the kernels of that combination, in parallel
+// make jobs: sixteen objects of 20-70 kernels each instead of four of 85-160), and once per long chain with -DVFIK_HEAVY_PART.  launch_cycle
+// (vfik_aux.hip) picks the object's entry point.
+#ifndef VFIK_ONLY_NJ
+#error "vfik_kernel.hip is compiled per joint count: -DVFIK_ONLY_NJ=<n> (csrc/Makefile)"
+#endif
 #ifdef VFIK_HEAVY_PART
 // -DVFIK_ONLY_NJ=<n> -DVFIK_HEAVY_PART: the non-lean single-cycle variants of a long chain, and nothing else
 void VFIK_CAT(launch_heavy_nj, VFIK_ONLY_NJ)(int io_dtype, bool ns, const KArgs& a, const CyclePlan& p, hipStream_t stream) {
@@ -3432,347 +2329,3 @@ hipError_t VFIK_PART_NAME(const KArgs& kargs, const CyclePlan& plan, hipStream_t
 }
 #endif
 }  // namespace vfik
-#else  // VFIK_DISPATCH
-
-#define X(n)                                                                                                      \
-    hipError_t launch_cycle_nj##n##_t32_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
-    hipError_t launch_cycle_nj##n##_t32_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
-    hipError_t launch_cycle_nj##n##_t64_ns0(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);      \
-    hipError_t launch_cycle_nj##n##_t64_ns1(const KArgs& kargs, const CyclePlan& plan, hipStream_t stream);
-VFIK_NJ_LIST
-#undef X
-
-namespace {
-// ------------------------------------------------------------------------------------------------
-// host: z-normal form -> DH form.  Every fixed transform factors as
-//     B = Rz(theta) Tz(d) Tx(a) Rx(alpha) Rz(phi) Tz(e)          (ZXZ Euler angles + common normal)
-// and the z-screws commute with the joint motions on either side, so the trailing (phi, e) of B[i]
-// joins the leading (theta, d) of B[i+1] and the variable of joint i+1.  B[0] stays general.
-// ------------------------------------------------------------------------------------------------
-struct Screws { double theta, d, a, alpha, phi, e; };
-
-static Screws dh_factor(const double* B) {
-    const double R00 = B[0], R10 = B[4], R02 = B[2], R12 = B[6], R20 = B[8], R21 = B[9], R22 = B[10];
-    const double tx = B[3], ty = B[7], tz = B[11];
-    Screws s{};
-    const double sa = std::sqrt(R02 * R02 + R12 * R12);
-    s.alpha = std::atan2(sa, R22);
-    if (sa > 1e-12) {
-        s.theta = std::atan2(R02, -R12);
-        s.phi = std::atan2(R20, R21);
-        const double ct = std::cos(s.theta), st = std::sin(s.theta);
-        const double ux = ct * tx + st * ty, uy = -st * tx + ct * ty;
-        s.a = ux;
-        s.e = -uy / sa;
-        s.d = tz - s.e * R22;
-    } else {  // consecutive axes parallel (alpha = 0) or anti-parallel (alpha = pi)
-        s.theta = (tx * tx + ty * ty > 1e-24) ? std::atan2(ty, tx) : 0.0;
-        s.a = std::sqrt(tx * tx + ty * ty);
-        s.e = 0.0;
-        s.d = tz;
-        const double g = std::atan2(R10, R00);
-        s.phi = R22 > 0.0 ? g - s.theta : s.theta - g;
-    }
-    return s;
-}
-
-static void mat_mul(const double* A, const double* B, double* C) {  // 3x4 row-major frames
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) C[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j];
-        C[4 * i + 3] = A[4 * i] * B[3] + A[4 * i + 1] * B[7] + A[4 * i + 2] * B[11] + A[4 * i + 3];
-    }
-}
-
-static double dh_recompose_error(const Screws& s, const double* B) {
-    auto rz = [](double t, double d, double* M) { const double c = std::cos(t), sn = std::sin(t); const double m[12] = {c, -sn, 0, 0, sn, c, 0, 0, 0, 0, 1, d}; memcpy(M, m, sizeof m); };
-    auto rx = [](double al, double a, double* M) { const double c = std::cos(al), sn = std::sin(al); const double m[12] = {1, 0, 0, a, 0, c, -sn, 0, 0, sn, c, 0}; memcpy(M, m, sizeof m); };
-    double A[12], X[12], C[12], T1[12], T2[12];
-    rz(s.theta, s.d, A); rx(s.alpha, s.a, X); rz(s.phi, s.e, C);
-    mat_mul(A, X, T1); mat_mul(T1, C, T2);
-    double err = 0.0;
-    for (int k = 0; k < 12; ++k) err = std::fmax(err, std::fabs(T2[k] - B[k]));
-    return err;
-}
-
-template <int NJ>
-double kconst_fill_t(void* dst, const vfik_chain& ch, const vfik_params& p, const double* tool12, int* plain, int* dhp) {
-    KConst<NJ>& c = *static_cast<KConst<NJ>*>(dst);
-    memset(&c, 0, sizeof c);
-    memcpy(c.base, ch.B[0], sizeof c.base);
-    double phi_prev = 0.0, e_prev = 0.0, worst = 0.0;
-    unsigned m_swap = 0, m_none = 0, m_d0 = 0, m_off0 = 0, m_offpi = 0;   // the chain's DH pattern (vfik_kernel.h: DhPattern)
-    for (int i = 0; i < NJ; ++i) {
-        const Screws s = dh_factor(ch.B[i + 1]);
-        worst = std::fmax(worst, dh_recompose_error(s, ch.B[i + 1]));
-        const double off = phi_prev + s.theta;
-        const bool pris = ch.jtype[i] == 1;
-        c.dh[i].off = off;
-        c.dh[i].crev = pris ? 0.0 : 1.0;
-        c.dh[i].cprs = pris ? std::cos(off) : 0.0;
-        c.dh[i].sprs = pris ? std::sin(off) : 0.0;
-        c.dh[i].qd = pris ? 1.0 : 0.0;
-        c.dh[i].d = e_prev + s.d;
-        c.dh[i].a = s.a;
-        c.dh[i].ca = std::cos(s.alpha);
-        c.dh[i].sa = std::sin(s.alpha);
-        // exact zeros and ones where the geometry has them (cos(pi/2) is 6e-17 in floating point): the DH pattern masks below -- and
-        // the kernel variants that assume them -- rest on EXACT values; the snap moves a frame by less than 1e-15
-        if (std::fabs(c.dh[i].a) < 1e-15) c.dh[i].a = 0.0;
-        if (std::fabs(c.dh[i].d) < 1e-15) c.dh[i].d = 0.0;
-        if (std::fabs(c.dh[i].ca) < 1e-15 && c.dh[i].sa > 0.0) { c.dh[i].ca = 0.0; c.dh[i].sa = 1.0; }
-        if (std::fabs(c.dh[i].sa) < 1e-15 && c.dh[i].ca > 0.0) { c.dh[i].sa = 0.0; c.dh[i].ca = 1.0; }
-        if (!pris && c.dh[i].a == 0.0 && c.dh[i].ca == 0.0 && c.dh[i].sa == 1.0) m_swap |= 1u << i;
-        if (!pris && c.dh[i].a == 0.0 && c.dh[i].ca == 1.0 && c.dh[i].sa == 0.0) m_none |= 1u << i;
-        if (!pris && c.dh[i].d == 0.0) m_d0 |= 1u << i;
-        {   // an offset that is a multiple of pi: snapped to it, so that the pattern's "no offset" / "negate" is exact for this chain
-            const double kpi = off / 3.14159265358979323846;
-            const double kr = std::nearbyint(kpi);
-            if (!pris && std::fabs(kpi - kr) < 1e-12) {
-                c.dh[i].off = kr * 3.14159265358979323846;
-                if (((long)kr) % 2 == 0) m_off0 |= 1u << i; else m_offpi |= 1u << i;
-            }
-        }
-        phi_prev = s.phi;
-        e_prev = s.e;
-        const double half = 0.5 * (ch.q_hi[i] - ch.q_lo[i]);
-        c.q_lo[i] = ch.q_lo[i];
-        c.q_hi[i] = ch.q_hi[i];
-        c.q_mid[i] = 0.5 * (ch.q_lo[i] + ch.q_hi[i]);
-        c.inv_half[i] = 1.0 / half;
-        c.jl_k[i] = p.jl_gain / (half * half);
-        c.wq[i] = p.wq[i];
-        if (ch.jtype[i] == 1) c.prismatic_mask |= 1u << i;
-    }
-    c.tail_c = std::cos(phi_prev);
-    c.tail_s = std::sin(phi_prev);
-    c.tail_e = e_prev;
-    for (int i = 0; i < 6; ++i) c.wy[i] = p.wy[i];
-    for (int i = 0; i < VFIK_MIX_CHANNELS; ++i) c.mix_w[i] = p.mix_w[i];
-    for (int k = 0; k < 12; ++k) c.tool[k] = tool12[k];
-    // The shared tool on the PLAIN kernels (TOOLC): they keep no flange value through the field and rebuild the lever arm p_ee - p_tip =
-    // -Rt (Rtool^-1 t) and /pose_no_tool from the tool pose.  c3 = Rtool^-1 t is formed here, in long double by cofactors, and rides in
-    // dh[2..4].pad (no member moves); the block must be invertible to working accuracy for that -- the rule of include/vfik.h:
-    // max |Rtool Rtool^T - I| <= VFIK_TOOL_MAX_DEFECT, else the handle takes the general variants, which keep the flange frame itself
-    // (vfik_kernel.h: tool_block_serves_plain).
-    static_assert(NJ >= 5, "KConst::dh[2..4].pad");
-    double c3[3];
-    const bool tool_block_ok = tool_block_serves_plain(tool12, c3);
-    for (int j = 0; j < 3; ++j) c.dh[2 + j].pad = c3[j];
-    c.speed = p.speed_scale;
-    c.lambda2 = p.lambda * p.lambda;
-    c.rot_slow = p.rot_slowdown;
-    c.cos_slow = p.rot_slowdown > 0.0 && p.rot_slowdown < 3.14159265358979323846 ? std::cos(p.rot_slowdown) : -2.0;  // -2: always evaluate the angle
-    // (the kernels' rcp_nr(rot_slow) of old is this value: its last Newton step rounds (1 - e^2) / rot_slow with e < 2^-48 once)
-    c.dh[1].pad = p.rot_slowdown > 0.0 ? 1.0 / p.rot_slowdown : 0.0;   // (KConst: 1 / rot_slow)
-    c.null_gain = p.null_gain;
-    c.lookahead = p.lookahead;
-    c.max_vel = p.max_vel;
-    c.jp_kp = p.jp_kp;
-    c.jp_delta = p.jp_delta;
-    c.jl_gain = p.jl_gain;
-    // PLAIN variant of the kernel: revolute joints only, no trailing screw.  *plain: 0 general variants; else 1 + (the batch's shared tool
-    // is not the identity ? 1 : 0) + (its IK weights are not all one ? 2 : 0): the lean float32 kernels and the eight-lanes kernel have
-    // variants that apply a shared tool and shared weights themselves (cycle_body: TOOLC, WTSC), every other launch of such a handle takes
-    // the general variants (plan_cycle).
-    bool pl = c.prismatic_mask == 0 && c.tail_c == 1.0 && c.tail_s == 0.0 && c.tail_e == 0.0 && tool_block_ok;
-    static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    bool tool_ident = true;
-    for (int k = 0; k < 12; ++k) tool_ident = tool_ident && tool12[k] == ident[k];
-    bool unit_w = true;
-    for (int i = 0; i < 6; ++i) unit_w = unit_w && p.wy[i] == 1.0;
-    for (int i = 0; i < NJ; ++i) unit_w = unit_w && p.wq[i] == 1.0;
-    *plain = pl ? 1 + (tool_ident ? 0 : 1) + (unit_w ? 0 : 2) : 0;
-    bool base_i = true;
-    {
-        static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        for (int k = 0; k < 12; ++k) base_i = base_i && c.base[k] == ident[k];
-    }
-    if (dhp) *dhp = pl ? dh_pattern_of(NJ, m_swap, m_none, m_d0, m_off0, m_offpi, base_i) : 0;
-    // (sin, cos)(k pi/32), k = 0 .. 63, for sincos_tab_n
-    double* tab = reinterpret_cast<double*>(static_cast<char*>(dst) + KTab<NJ>::OFFSET);
-    for (int k = 0; k < 64; ++k) {
-        const long double a = (long double)k * 3.14159265358979323846264338327950288L / 32.0L;
-        tab[2 * k] = (double)sinl(a);
-        tab[2 * k + 1] = (double)cosl(a);
-    }
-    return worst;
-}
-
-}  // namespace
-
-int dh_pattern_of(int nj, unsigned swap, unsigned none, unsigned d0, unsigned off0, unsigned offpi, bool base_identity) {
-    unsigned ps = 0, pn = 0, pd = 0, p0 = 0, ppi = 0;
-    bool pb = false;
-    switch (nj) {
-#define X(n) case n: ps = DhPattern<n, 1>::SWAP; pn = DhPattern<n, 1>::NONE; pd = DhPattern<n, 1>::D0; p0 = DhPattern<n, 1>::OFF0; ppi = DhPattern<n, 1>::OFFPI; pb = DhPattern<n, 1>::BASE_I; break;
-        VFIK_NJ_LIST
-#undef X
-        default: break;
-    }
-    if (ps == 0) return 0;
-    // the chain's zeros must CONTAIN the pattern's (more zeros are fine: they are multiplied out); its pi offsets must be the pattern's
-    return ((swap & ps) == ps && (none & pn) == pn && (d0 & pd) == pd && (off0 & p0) == p0 && (offpi & ppi) == ppi && (!pb || base_identity)) ? 1 : 0;
-}
-
-uint32_t supported_joints_mask() {
-    uint32_t m = 0;
-#define X(n) m |= 1u << n;
-    VFIK_NJ_LIST
-#undef X
-    return m;
-}
-
-hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan_out) {
-    const bool ns = kargs.flags & VFIK_F_NULLSPACE;
-    const CyclePlan plan = plan_cycle(kargs, nj, io_dtype, ns, block);
-    if (plan_out) *plan_out = plan;
-    switch (nj) {
-#define X(n)                                                                                                                        \
-    case n:                                                                                                                         \
-        return io_dtype == 32 ? (ns ? launch_cycle_nj##n##_t32_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t32_ns0(kargs, plan, stream))  \
-                              : (ns ? launch_cycle_nj##n##_t64_ns1(kargs, plan, stream) : launch_cycle_nj##n##_t64_ns0(kargs, plan, stream));
-        VFIK_NJ_LIST
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-}
-
-size_t kconst_bytes(int nj) {  // the constants, padded to 1 KiB, and the sin / cos table behind them
-    switch (nj) {
-#define X(n) case n: return KTab<n>::OFFSET + 1024;
-        VFIK_NJ_LIST
-#undef X
-        default: return 0;
-    }
-}
-
-double kconst_fill(int nj, void* dst, const vfik_chain& chain, const vfik_params& p, const double* tool12, int* plain, int* dhp) {
-    switch (nj) {
-#define X(n) case n: return kconst_fill_t<n>(dst, chain, p, tool12, plain, dhp);
-        VFIK_NJ_LIST
-#undef X
-        default: return 1e300;
-    }
-}
-
-hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,
-                      void* out, hipStream_t stream) {
-    const int block = 256;
-    const dim3 grid((unsigned)((count + block - 1) / block)), blk(block);
-    if (io_dtype == 32)
-        hipLaunchKernelGGL(mix_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(cmds), w_dev, K, count,
-                           chan_stride, static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL(mix_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(cmds), w_dev, K, count,
-                           chan_stride, static_cast<double*>(out));
-    return hipGetLastError();
-}
-
-}  // namespace vfik
-
-namespace vfik {
-hipError_t launch_probe(int io_dtype, const void* pose, const void* goal, const void* slots, int B, long Bp, int slots_used,
-                        double rot_slow, double cos_slow, void* out, hipStream_t stream) {
-    const int block = 64;
-    const dim3 grid((B + block - 1) / block), blk(block);
-    if (io_dtype == 32)
-        hipLaunchKernelGGL(probe_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose), static_cast<const float*>(goal),
-                           static_cast<const float*>(slots), B, Bp, slots_used, rot_slow, cos_slow, static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL(probe_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose), static_cast<const double*>(goal),
-                           static_cast<const double*>(slots), B, Bp, slots_used, rot_slow, cos_slow, static_cast<double*>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active) {
-    const int block = 256;
-    const dim3 grid((unsigned)((count + block - 1) / block)), blk(block);
-    if (io_dtype == 32)
-        hipLaunchKernelGGL(monitor_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose),
-                           static_cast<const float*>(frames), O, count, static_cast<float*>(out), active);
-    else
-        hipLaunchKernelGGL(monitor_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
-                           static_cast<const double*>(frames), O, count, static_cast<double*>(out), active);
-    return hipGetLastError();
-}
-
-hipError_t launch_move(int io_dtype, const MoveArgs& m, hipStream_t stream) {
-    const int lanes = (m.first_arm & 63) + m.n_arms;
-    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)((m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0))), blk(256);
-    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4) & 15u) == 0;
-    if (io_dtype == 32) {
-        if (vec) hipLaunchKernelGGL((move_kernel<float, true>), grid, blk, 0, stream, m);
-        else hipLaunchKernelGGL((move_kernel<float, false>), grid, blk, 0, stream, m);
-    } else {
-        if (vec) hipLaunchKernelGGL((move_kernel<double, true>), grid, blk, 0, stream, m);
-        else hipLaunchKernelGGL((move_kernel<double, false>), grid, blk, 0, stream, m);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_move_scene(int io_dtype, const SceneMoveArgs& s, hipStream_t stream) {
-    const MoveArgs& m = s.m;
-    const int lanes = (m.first_arm & 63) + m.n_arms;
-    const int rows = (m.goal16 ? 1 : 0) + (m.rep4 ? m.n_rep : 0) + (s.fun6 ? s.n_fun : 0) + (s.hem6 ? s.n_hem : 0) + (s.att16 ? s.n_att : 0);
-    if (rows < 1) return hipSuccess;
-    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)rows), blk(256);
-    const size_t pair = io_dtype == 32 ? 8 : 16;
-    const bool vec = (((uintptr_t)m.goal16 | (uintptr_t)m.rep4 | (uintptr_t)s.att16) & 15u) == 0 && (((uintptr_t)s.fun6 | (uintptr_t)s.hem6) & (pair - 1)) == 0;
-    if (io_dtype == 32) {
-        if (vec) hipLaunchKernelGGL((move_scene_kernel<float, true>), grid, blk, 0, stream, s);
-        else hipLaunchKernelGGL((move_scene_kernel<float, false>), grid, blk, 0, stream, s);
-    } else {
-        if (vec) hipLaunchKernelGGL((move_scene_kernel<double, true>), grid, blk, 0, stream, s);
-        else hipLaunchKernelGGL((move_scene_kernel<double, false>), grid, blk, 0, stream, s);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream) {
-    const int block = 256;
-    const dim3 grid((B + block - 1) / block), blk(block);
-    if (io_dtype == 32)
-        hipLaunchKernelGGL(track_kernel<float>, grid, blk, 0, stream, static_cast<const float*>(pose), static_cast<const float*>(v6),
-                           state, static_cast<float*>(out), active, B);
-    else
-        hipLaunchKernelGGL(track_kernel<double>, grid, blk, 0, stream, static_cast<const double*>(pose),
-                           static_cast<const double*>(v6), state, static_cast<double*>(out), active, B);
-    return hipGetLastError();
-}
-
-hipError_t launch_check(int io_dtype, bool joint, bool list, const CheckArgs& g, hipStream_t stream, const StallArgs* st) {
-    const dim3 grid((unsigned)((g.B + 255) / 256)), blk(256);
-    auto launch = [&](auto t) {
-        typedef decltype(t) T;
-        if (st) {   // the handle has a stall rule
-            if (joint) {
-                if (list) hipLaunchKernelGGL((check_stall_kernel<T, true, true>), grid, blk, 0, stream, g, *st);
-                else hipLaunchKernelGGL((check_stall_kernel<T, true, false>), grid, blk, 0, stream, g, *st);
-            } else {
-                if (list) hipLaunchKernelGGL((check_stall_kernel<T, false, true>), grid, blk, 0, stream, g, *st);
-                else hipLaunchKernelGGL((check_stall_kernel<T, false, false>), grid, blk, 0, stream, g, *st);
-            }
-        } else if (joint) {
-            if (list) hipLaunchKernelGGL((check_kernel<T, true, true>), grid, blk, 0, stream, g);
-            else hipLaunchKernelGGL((check_kernel<T, true, false>), grid, blk, 0, stream, g);
-        } else {
-            if (list) hipLaunchKernelGGL((check_kernel<T, false, true>), grid, blk, 0, stream, g);
-            else hipLaunchKernelGGL((check_kernel<T, false, false>), grid, blk, 0, stream, g);
-        }
-    };
-    if (io_dtype == 32) launch(0.0f);
-    else launch(0.0);
-    return hipGetLastError();
-}
-
-hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream, const StallArgs* st) {
-    const dim3 grid((unsigned)((s.c.B + 255) / 256)), blk(256);
-    if (st) {   // the handle has a stall rule
-        if (io_dtype == 32) hipLaunchKernelGGL(script_stall_kernel<float>, grid, blk, 0, stream, s, *st);
-        else hipLaunchKernelGGL(script_stall_kernel<double>, grid, blk, 0, stream, s, *st);
-    } else if (io_dtype == 32) hipLaunchKernelGGL(script_kernel<float>, grid, blk, 0, stream, s);
-    else hipLaunchKernelGGL(script_kernel<double>, grid, blk, 0, stream, s);
-    return hipGetLastError();
-}
-}  // namespace vfik
-#endif  // VFIK_ONLY_NJ / VFIK_DISPATCH
