@@ -559,6 +559,66 @@ size_t vfik_stall_rule_size(void);
 int vfik_set_stall_rule(vfik_handle* h, const vfik_stall_rule* r);   /* NULL: off (the default) */
 int vfik_stalled_host(vfik_handle* h, int32_t* out /* host [B] */);  /* synchronises; the last timed move's */
 
+/* Arms as each other's obstacles.  The reference runs one process set per arm -- `left` and `right` instances of the same robot
+ * (old/system_start.sh.old:60,237) -- and an arm learns where its neighbour is only as `set ObstacleP` objects that somebody re-sends
+ * whenever they move (object_feeder:317-334).  Here a handle carries up to VFIK_MAX_LINK_SPHERES spheres fixed to links of its chain
+ * (vfik_link_sphere, vfik_types.h), and vfik_link_points places them from a batch of joint angles ON THE DEVICE, in the exact shape
+ * vfik_move_fields takes as rep4 (and vfik_scene_move as its rep4 member): [vfik_link_points; vfik_move_fields; vfik_step] on one stream is
+ * the per-cycle form, with no host wait.
+ *
+ * vfik_set_link_spheres is a setter like vfik_set_fields: it may allocate, synchronises, and moves vfik_launch_epoch.  Frames are those of
+ * the PUBLIC chain (vfik_chain's z-normal form), link 0 = the base frame B[0], link n = the flange; a tool is not applied -- add its offset
+ * to c on link n.  L = 0 or s == NULL: no spheres.  A new list switches a coupling off (vfik_set_coupling: its buffer has the old list's
+ * rows); vfik_set_chain drops the spheres and the coupling.
+ * VFIK_E_ARG: L outside 0..16, a link outside 0..n, a centre that is not finite, a radius that is negative or not finite, reserved != 0;
+ * VFIK_E_STATE: no chain yet. */
+size_t vfik_link_sphere_size(void);
+int vfik_set_link_spheres(vfik_handle* h, const vfik_link_sphere* s, int L);
+
+/* For every arm b of the batch: s = src_arm[b] is the arm whose links become b's obstacles (src_arm == NULL: s = b).  q[s][0..n) is widened
+ * to double and the chain is walked once in float64; for sphere j in the CALLER's order P = X_link(q_s) c_j, and with xform12 -- [B][12],
+ * row-major 3x4 [R_b | t_b]: where the source's base stands as seen from arm b's base, taken as given, rotation or not -- P becomes
+ * R_b P + t_b.  Row first_rep + j of rep4[b][n_rep][4] becomes (P, radius_j) rounded to the I/O type.  Rows outside first_rep ..
+ * first_rep + L - 1 are NOT written: a caller fills them with NaN once, and vfik_move_fields then leaves those repellers alone.
+ *   s < 0 or s >= B   all L rows of the arm are NaN ("leave as it is") and q is not read for it; no index of src_arm is used unchecked.
+ *   NaN in q[s]       all L rows of the arm are NaN.
+ * Device pointers, io dtype (src_arm int32), asynchronous on the handle's stream, no allocation; ordered like vfik_move_fields: after the
+ * launches enqueued before it and before those enqueued after it, and like it the call first waits for outstanding vfik_submit_host
+ * tickets.  Nothing a launch decides at enqueue time changes and vfik_launch_epoch does not move.
+ * Robots whose arms differ (left and right arms with other chains or bases) take two handles: handle A's vfik_link_points output is handle
+ * B's rep4 argument when both run on one stream (vfik_set_stream) or the caller orders them; there is no cross-handle plumbing.
+ * VFIK_E_ARG: q or rep4 NULL, rep4 not 16-byte aligned, first_rep < 0, first_rep + L > n_rep, n_rep > max_slots; VFIK_E_STATE: no spheres. */
+int vfik_link_points(vfik_handle* h, const void* q, const int32_t* src_arm, const void* xform12, void* rep4, int n_rep, int first_rep);
+/* The same with HOST arrays: q [B][n], xform12 [B][12] doubles, rounded to the io dtype as vfik_move_fields_host rounds its rows, src_arm
+ * int32 [B]; rep4 [B][n_rep][4] doubles receives rows first_rep .. first_rep + L - 1 (the io-typed values, widened), its other rows are
+ * not touched.  Copies, launches and synchronises; the alignment rule does not apply. */
+int vfik_link_points_host(vfik_handle* h, const double* q, const int32_t* src_arm, const double* xform12, double* rep4, int n_rep, int first_rep);
+
+/* Coupling inside the timed moves: state of the HANDLE like the stall rule, off by default; with the coupling off nothing changes -- the
+ * same launches, the same results.  While one is set, every block k of vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js and vfik_script
+ * enqueues, in front of its cycles, vfik_link_points on the block's INPUT row of joint angles (block 0: io->q, block k: what block k - 1
+ * left) into a buffer of the handle, [B][first_rep + L][4], and the launch vfik_move_fields makes for that buffer as rep4: the arm's
+ * first_rep-th .. (first_rep + L - 1)-th decay repellers in ascending-id order follow the source arm's links from check to check, with no
+ * host taking part; its repellers before first_rep stay (the buffer's rows there are NaN).  An arm that is gated off, held at arrival,
+ * stalled or kept out carries its row of joint angles forward, so it is an obstacle at the posture it holds.  After the move the
+ * repellers stay where the last block put them.
+ *   link_traj   when given, row k receives the L rows per arm block k started from: vfik_link_points of block k's input row with n_rep = L,
+ *               first_rep = 0.  The caller sizes it for the n_checks of the moves it runs.
+ * vfik_set_coupling allocates the handle's buffer and fills it with NaN (never under capture: VFIK_E_STATE), synchronises and leaves
+ * vfik_launch_epoch alone; the moves allocate nothing for it, and a captured stream stays valid.  The pointers are kept, not copied: the
+ * arrays stay the caller's and alive while the coupling is set.  vfik_set_coupling(h, NULL) switches it off.
+ * VFIK_E_ARG: first_rep < 0, first_rep + L > max_slots, reserved != 0, src_arm / xform12 / link_traj no device pointer of its alignment
+ * (int32; the io type; 16 bytes); VFIK_E_STATE: no spheres set.  A timed move under a coupling before any vfik_set_fields: VFIK_E_STATE. */
+typedef struct vfik_coupling {
+    const int32_t* src_arm;  /* device [B], may be NULL (every arm its own source) */
+    const void*    xform12;  /* device [B][12] io dtype, may be NULL */
+    int32_t first_rep;       /* the arm's first_rep-th .. (first_rep + L - 1)-th decay repeller, ascending id */
+    int32_t reserved;        /* 0 */
+    void*   link_traj;       /* device [n_checks][B][L][4] io dtype or NULL: the rows each block started from */
+} vfik_coupling;
+size_t vfik_coupling_size(void);
+int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c);   /* NULL: off (the default) */
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

@@ -62,6 +62,17 @@ typedef struct vfik_chain {
     double q_hi[VFIK_MAX_JOINTS];
 } vfik_chain;
 
+/* A sphere fixed to one link of the chain (vfik.h: vfik_set_link_spheres): what an arm is for its neighbour, the `set ObstacleP`
+ * objects somebody re-sends whenever the other arm moves (scripts/object_feeder:317-334). */
+#define VFIK_MAX_LINK_SPHERES 16
+typedef struct vfik_link_sphere {
+    int32_t link;      /* 0..n: frame X_link = B[0] Jz(q_1) B[1] ... Jz(q_link) B[link] of vfik_chain's z-normal form;
+                          0 = the base frame, n = the flange (no tool) */
+    int32_t reserved;  /* 0 */
+    double  c[3];      /* centre in that frame */
+    double  radius;    /* finite, >= 0 */
+} vfik_link_sphere;
+
 /* feature flags (vfik_params.flags) */
 enum {
     VFIK_F_NULLSPACE = 1u << 0, /* run the nullspace module (launcher option --no_nullspace absent, vfclik:72-79) */

@@ -100,6 +100,20 @@ class StallRule(C.Structure):
                 ("stalled", C.c_void_p)]
 
 
+MAX_LINK_SPHERES = 16  # include/vfik_types.h: VFIK_MAX_LINK_SPHERES
+
+
+class LinkSphere(C.Structure):
+    """``struct vfik_link_sphere`` (include/vfik_types.h; vfik_set_link_spheres)."""
+    _fields_ = [("link", C.c_int32), ("reserved", C.c_int32), ("c", C.c_double * 3), ("radius", C.c_double)]
+
+
+class Coupling(C.Structure):
+    """``struct vfik_coupling`` (include/vfik.h: vfik_set_coupling)."""
+    _fields_ = [("src_arm", C.c_void_p), ("xform12", C.c_void_p), ("first_rep", C.c_int32), ("reserved", C.c_int32),
+                ("link_traj", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

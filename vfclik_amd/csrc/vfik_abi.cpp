@@ -113,6 +113,16 @@ struct vfik_handle {
     double* d_stall_best = nullptr;
     int* d_stall_count = nullptr;
     int* d_stall_own = nullptr;
+    // vfik_set_link_spheres: the caller's list (n_links of them) and its device image (vfik_links.h), which link_kernel reads; the staging of
+    // vfik_link_points_host.  vfik_set_coupling: the coupling every block of a timed move applies (couple_on) and the handle's rep4 buffer
+    // [B][first_rep + n_links][4], NaN outside the rows link_kernel writes
+    int n_links = 0;
+    vfik_link_sphere links[VFIK_MAX_LINK_SPHERES] = {};
+    void* d_link_img = nullptr;
+    DevBuf link_stage;
+    bool couple_on = false;
+    vfik_coupling couple{};
+    DevBuf couple_rep;
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -434,7 +444,8 @@ void vfik_destroy(vfik_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
-                    h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw, h->d_stall_best, h->d_stall_count, h->d_stall_own};
+                    h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw, h->d_stall_best, h->d_stall_count, h->d_stall_own,
+                    h->d_link_img, h->link_stage.p, h->couple_rep.p};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -481,6 +492,7 @@ int vfik_set_chain(vfik_handle* h, const vfik_chain* c) {
     h->chain_set = true;
     const int rc = upload_kconst(h);
     if (rc != VFIK_OK) { h->chain = saved; h->chain_set = was_set; }
+    else { h->n_links = 0; h->couple_on = false; }   // (the link spheres were those of the old chain's frames)
     return rc;
 }
 
@@ -758,6 +770,117 @@ int vfik_move_fields_host(vfik_handle* h, int first_arm, int n_arms, const doubl
     const int rl = move_launch(h, first_arm, n_arms, goal16 ? d : nullptr, rep4 ? d + ng * h->esz : nullptr, n_rep, nullptr);
     if (rl != VFIK_OK) return rl;
     HIP_TRY(hipStreamSynchronize(h->stream));   // `buf` and the stage are reused
+    return VFIK_OK;
+}
+
+// ---- link spheres: the other arm as an obstacle (link_kernel, vfik_aux.hip; the image and the checks of the list: vfik_links.h) ----
+size_t vfik_link_sphere_size(void) { return sizeof(vfik_link_sphere); }
+
+int vfik_set_link_spheres(vfik_handle* h, const vfik_link_sphere* s, int L) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
+    if (!s) L = 0;
+    if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_link_spheres before vfik_set_chain: the spheres sit on the chain's links");
+    char msg[160];
+    if (vfik::links_check(h->chain, s, L, msg, sizeof msg)) return fail(VFIK_E_ARG, "%s", msg);
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_set_link_spheres uploads the handle's link image: call it before capturing the stream")) return VFIK_E_STATE;
+    if (!h->d_link_img && dev_alloc(h, &h->d_link_img, sizeof(vfik::LinkImage), false)) return VFIK_E_HIP;
+    vfik::LinkImage img;
+    vfik::links_fill(h->chain, s, L, &img);
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (an earlier vfik_link_points may still read the old image)
+    HIP_TRY(hipMemcpyAsync(h->d_link_img, &img, sizeof img, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int j = 0; j < L; ++j) h->links[j] = s[j];
+    h->n_links = L;
+    h->couple_on = false;   // (its buffer has the old list's rows)
+    return VFIK_OK;
+}
+
+// the checks the two forms of vfik_link_points share
+static int link_check(vfik_handle* h, const void* q, const void* rep4, int n_rep, int first_rep) {
+    if (!q || !rep4) return fail(VFIK_E_ARG, "vfik_link_points: q and rep4 are required");
+    if (first_rep < 0 || first_rep + h->n_links > n_rep) return fail(VFIK_E_ARG, "rows [%d, %d) outside the %d rows of rep4", first_rep, first_rep + h->n_links, n_rep);
+    if (n_rep > h->max_slots) return fail(VFIK_E_ARG, "n_rep %d outside [0, %d]", n_rep, h->max_slots);
+    if (h->n_links < 1) return fail(VFIK_E_STATE, "vfik_link_points before vfik_set_link_spheres: there is nothing to place");
+    return VFIK_OK;
+}
+
+static int link_launch(vfik_handle* h, const void* q, const int32_t* src_arm, const void* xform12, void* rep4, void* traj, int n_rep, int first_rep) {
+    vfik::LinkArgs a{};
+    a.img = static_cast<const vfik::LinkImage*>(h->d_link_img);
+    a.q = q; a.src_arm = src_arm; a.xform12 = xform12; a.rep4 = rep4; a.traj = traj;
+    a.B = h->B; a.n_rep = n_rep; a.first_rep = first_rep;
+    const hipError_t e = vfik::launch_link(h->io_dtype, a, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "link launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+int vfik_link_points(vfik_handle* h, const void* q, const int32_t* src_arm, const void* xform12, void* rep4, int n_rep, int first_rep) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = link_check(h, q, rep4, n_rep, first_rep);
+    if (rc != VFIK_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(rep4) % 16) return fail(VFIK_E_ARG, "rep4 must be 16-byte aligned: the kernel stores its rows in 16-byte pieces");
+    HIP_TRY(hipSetDevice(h->device));
+    return link_launch(h, q, src_arm, xform12, rep4, nullptr, n_rep, first_rep);
+}
+
+int vfik_link_points_host(vfik_handle* h, const double* q, const int32_t* src_arm, const double* xform12, double* rep4, int n_rep, int first_rep) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const int rc = link_check(h, q, rep4, n_rep, first_rep);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    // one stage: q | xform12 | the L rows per arm (16-byte aligned) | src_arm
+    const size_t B = (size_t)h->B, L = (size_t)h->n_links;
+    const size_t nq = B * h->n, nx = xform12 ? B * 12 : 0;
+    const size_t out_off = ((nq + nx) * h->esz + 15) / 16 * 16, out_bytes = B * L * 4 * h->esz, src_off = out_off + out_bytes;
+    std::vector<char> buf(src_off + (src_arm ? B * sizeof(int32_t) : 0));
+    for (size_t k = 0; k < nq + nx; ++k) put_io(h, buf, k, k < nq ? q[k] : xform12[k - nq]);
+    if (src_arm) std::memcpy(buf.data() + src_off, src_arm, B * sizeof(int32_t));
+    if (reserve(h, h->link_stage, buf.size(), true, true) != VFIK_OK) return VFIK_E_HIP;
+    char* d = static_cast<char*>(h->link_stage.p);
+    HIP_TRY(hipMemcpyAsync(d, buf.data(), buf.size(), hipMemcpyHostToDevice, h->stream));
+    const int rl = link_launch(h, d, src_arm ? reinterpret_cast<const int32_t*>(d + src_off) : nullptr, xform12 ? d + nq * h->esz : nullptr,
+                               d + out_off, nullptr, (int)L, 0);
+    if (rl != VFIK_OK) return rl;
+    HIP_TRY(hipMemcpyAsync(buf.data() + out_off, d + out_off, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t k = 0; k < L * 4; ++k) {
+            const char* src = buf.data() + out_off + (b * L * 4 + k) * h->esz;
+            double v;
+            if (h->io_dtype == 32) { float f; std::memcpy(&f, src, sizeof f); v = f; } else std::memcpy(&v, src, sizeof v);
+            rep4[(b * (size_t)n_rep + (size_t)first_rep) * 4 + k] = v;
+        }
+    return VFIK_OK;
+}
+
+size_t vfik_coupling_size(void) { return sizeof(vfik_coupling); }
+
+int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!c) { h->couple_on = false; return VFIK_OK; }
+    if (h->n_links < 1) return fail(VFIK_E_STATE, "vfik_set_coupling before vfik_set_link_spheres: there is nothing to couple");
+    if (c->reserved != 0) return fail(VFIK_E_ARG, "coupling: reserved must be 0");
+    if (c->first_rep < 0 || c->first_rep + h->n_links > h->max_slots)
+        return fail(VFIK_E_ARG, "coupling: repellers [%d, %d) outside the %d slots of the handle", c->first_rep, c->first_rep + h->n_links, h->max_slots);
+    if (c->src_arm && (!gpu_visible(c->src_arm) || reinterpret_cast<uintptr_t>(c->src_arm) % sizeof(int32_t)))
+        return fail(VFIK_E_ARG, "coupling: src_arm must be an int32-aligned DEVICE pointer (NULL: every arm its own source)");
+    if (c->xform12 && (!gpu_visible(c->xform12) || reinterpret_cast<uintptr_t>(c->xform12) % h->esz))
+        return fail(VFIK_E_ARG, "coupling: xform12 must be a DEVICE pointer aligned to the I/O type");
+    if (c->link_traj && (!gpu_visible(c->link_traj) || reinterpret_cast<uintptr_t>(c->link_traj) % 16))
+        return fail(VFIK_E_ARG, "coupling: link_traj must be a 16-byte aligned DEVICE pointer");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_set_coupling allocates the handle's repeller rows: call it before capturing the stream")) return VFIK_E_STATE;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    const size_t bytes = (size_t)h->B * (size_t)(c->first_rep + h->n_links) * 4 * h->esz;
+    if (reserve(h, h->couple_rep, bytes, true, true) != VFIK_OK) return VFIK_E_HIP;
+    HIP_TRY(hipMemsetAsync(h->couple_rep.p, 0xFF, h->couple_rep.bytes, h->stream));   // (all bits set is a NaN of either I/O type: "leave as it is")
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->couple = *c;
+    h->couple_on = true;
     return VFIK_OK;
 }
 
@@ -1221,6 +1344,7 @@ int timed_check(vfik_handle* h, TimedMove& m) {
     if (io->track_error || io->obj_dist) return fail(VFIK_E_ARG, "io->track_error / io->obj_dist are per control cycle: vfik_step only, not a goto");
     if (!io->q_lo != !io->q_hi) return fail(VFIK_E_ARG, "io->q_lo and io->q_hi come together (both or neither)");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
+    if (h->couple_on && !h->fields_set) return fail(VFIK_E_STATE, "a timed move under a coupling before any vfik_set_fields: there are no repellers to move");
     m.n_checks = m.n_cycles / m.stride;
     m.gated = m.hold || io->active || m.list || (h->stall_on && h->stall.stop);   // (a stalled arm that stops is gated like a held one)
     return VFIK_OK;
@@ -1413,6 +1537,16 @@ int timed_begin(vfik_handle* h, TimedMove& m) {
     return rc != VFIK_OK ? rc : timed_launch_check(h, m, -1, nullptr);
 }
 
+// The handle's coupling (vfik_set_coupling) in front of block k's cycles: the link spheres of every arm's source at the block's input row into
+// the handle's rows, then the launch vfik_move_fields makes for them (move_launch: the tickets were drained when the move began).
+int couple_block(vfik_handle* h, int k, const void* q_prev) {
+    const int L = h->n_links, n_rep = h->couple.first_rep + L;
+    char* const traj = static_cast<char*>(h->couple.link_traj);
+    const int rc = link_launch(h, q_prev, h->couple.src_arm, h->couple.xform12, h->couple_rep.p,
+                               traj ? traj + (size_t)k * h->B * L * 4 * h->esz : nullptr, n_rep, h->couple.first_rep);
+    return rc != VFIK_OK ? rc : move_launch(h, 0, h->B, nullptr, h->couple_rep.p, n_rep, nullptr);
+}
+
 // block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
 int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     const vfik::BlockRows w = vfik::block_rows(m, timed_dims(h, m), k, h->d_gotoq, h->d_goto_dist);
@@ -1421,6 +1555,10 @@ int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     b.goal_dist = w.dist;
     if ((m.joint && m.list) || m.script) b.q_ref = h->d_js_ref;
     b.active = m.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
+    if (h->couple_on) {
+        const int rl = couple_block(h, k, w.q_prev);
+        if (rl != VFIK_OK) return rl;
+    }
     const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0, m.script ? h->d_script_mixw : nullptr);
     return rc != VFIK_OK ? rc : timed_launch_check(h, m, k, &w);
 }

@@ -2,6 +2,7 @@
 //   mix_kernel, track_kernel, monitor_kernel, probe_kernel      the mixer's sum alone, the tracking estimator, the distance monitor, the field probe
 //   move_kernel, move_scene_kernel                              goals, obstacles, funnels, hemispheres and attractors that move
 //   check_kernel, script_kernel (+ the _stall_ builds)          the check after each block of a timed move (vfik_check_body.inc, twice)
+//   link_kernel                                                 sphere centres on the links of a source arm: the other arm as an obstacle
 //   launch_cycle                                                a launch's plan (vfik_kernel.h: plan_cycle) -> the entry point of the object that holds
 //                                                               its kernel (vfik_kernel.hip, compiled per joint count, I/O type, nullspace module)
 // Compiled once (csrc/Makefile: vfik_dispatch.o).  The float64 building blocks are vfik_device.h, shared with the cycle kernels.
@@ -465,7 +466,111 @@ __device__ __forceinline__ bool stall_step(const StallArgs& st, int b, bool join
 #include "vfik_check_body.inc"
 #undef VFIK_STALL
 
+// ------------------------------------------------------------------------------------------------
+// vfik_link_points: the other arm as an obstacle.  The reference runs one process set per arm (old/system_start.sh.old:60,237) and an arm
+// learns where its neighbour is only as `set ObstacleP` objects that somebody re-sends whenever they move (object_feeder:317-334).  Here one
+// lane per arm b walks the chain of the arm's SOURCE s = src_arm[b] (NULL: b itself) once, in float64, in the frames of the public chain
+// (LinkArgs, vfik_kernel.h; LinkImage, vfik_links.h):
+//     X_0 = B[0],   X_i = X_{i-1} Jz(q_s[i-1]) B[i]
+// and when the walk stands at link i it emits every sphere of that link -- the image holds them sorted by link, the loop over them and the
+// one over the joints have uniform bounds, the image is read at uniform addresses, jtype is a uniform branch -- as (R_b (X_i c) + t_b, radius)
+// into the caller's row first_rep + perm of rep4[b].  The running frame is twelve named doubles: no frame array, no register array indexed at
+// run time, no scratch.  sin and cos: sincos_fast (vfik_device.h), whose contract covers joint ranges.  A row is one 16-byte store (float32)
+// or two (float64).  The image is a kernel argument of its own, __restrict__: beside the kernel's vector stores that is what lets the compiler
+// read it with scalar loads.
+// A source outside [0, B) -- no index of the caller's is used unchecked -- writes L rows of NaN without reading q; so does a q row that holds
+// a NaN anywhere (a first pass over the row: the spheres of link 0 are emitted before the joints are read).
+// ------------------------------------------------------------------------------------------------
+struct LinkFrame { double r00, r01, r02, p0, r10, r11, r12, p1, r20, r21, r22, p2; };
+
+// X <- X Jz(q): a rotation about, or a shift along, the frame's own z
+__device__ __forceinline__ void link_joint(LinkFrame& X, int jtype, double q) {
+    if (jtype == 0) {
+        double s, c;
+        sincos_fast(q, s, c);
+        const double a0 = X.r00, a1 = X.r10, a2 = X.r20;
+        X.r00 = __builtin_fma(X.r01, s, a0 * c); X.r01 = __builtin_fma(-a0, s, X.r01 * c);
+        X.r10 = __builtin_fma(X.r11, s, a1 * c); X.r11 = __builtin_fma(-a1, s, X.r11 * c);
+        X.r20 = __builtin_fma(X.r21, s, a2 * c); X.r21 = __builtin_fma(-a2, s, X.r21 * c);
+    } else {
+        X.p0 = __builtin_fma(X.r02, q, X.p0);
+        X.p1 = __builtin_fma(X.r12, q, X.p1);
+        X.p2 = __builtin_fma(X.r22, q, X.p2);
+    }
+}
+
+// one row of X <- X [Rb | pb]
+__device__ __forceinline__ void link_fixed_row(double& r0, double& r1, double& r2, double& p, const double* __restrict__ b) {
+    const double a0 = r0, a1 = r1, a2 = r2;
+    r0 = __builtin_fma(a2, b[8], __builtin_fma(a1, b[4], a0 * b[0]));
+    r1 = __builtin_fma(a2, b[9], __builtin_fma(a1, b[5], a0 * b[1]));
+    r2 = __builtin_fma(a2, b[10], __builtin_fma(a1, b[6], a0 * b[2]));
+    p = __builtin_fma(a2, b[11], __builtin_fma(a1, b[7], __builtin_fma(a0, b[3], p)));
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) link_kernel(const LinkImage* __restrict__ im, const LinkArgs a) {
+    typedef typename FollowQuad<T>::type Quad;
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (b >= a.B) return;
+    const int n = im->n, L = im->L;
+    const int s = a.src_arm ? a.src_arm[b] : b;
+    bool bad = s < 0 || s >= a.B;
+    const T* const qs = static_cast<const T*>(a.q) + (long)(bad ? 0 : s) * n;
+    if (!bad)
+        for (int i = 0; i < n; ++i) {
+            const T v = qs[i];
+            bad = bad || v != v;
+        }
+    // where the source's base stands as seen from this arm's base: taken as given, rotation or not
+    double t00 = 1, t01 = 0, t02 = 0, t03 = 0, t10 = 0, t11 = 1, t12 = 0, t13 = 0, t20 = 0, t21 = 0, t22 = 1, t23 = 0;
+    if (a.xform12) {
+        const T* const x = static_cast<const T*>(a.xform12) + (long)b * 12;
+        t00 = (double)x[0]; t01 = (double)x[1]; t02 = (double)x[2]; t03 = (double)x[3];
+        t10 = (double)x[4]; t11 = (double)x[5]; t12 = (double)x[6]; t13 = (double)x[7];
+        t20 = (double)x[8]; t21 = (double)x[9]; t22 = (double)x[10]; t23 = (double)x[11];
+    }
+    Quad* const out = static_cast<Quad*>(a.rep4) + (long)b * a.n_rep + a.first_rep;
+    Quad* const trj = a.traj ? static_cast<Quad*>(a.traj) + (long)b * L : nullptr;
+    const T nan = (T)__builtin_nan("");
+    LinkFrame X = {im->B[0][0], im->B[0][1], im->B[0][2], im->B[0][3], im->B[0][4], im->B[0][5],
+                   im->B[0][6], im->B[0][7], im->B[0][8], im->B[0][9], im->B[0][10], im->B[0][11]};
+    int j = 0;
+    for (int i = 0;; ++i) {
+        for (; j < L && im->link[j] == i; ++j) {
+            const double cx = im->c[j][0], cy = im->c[j][1], cz = im->c[j][2];
+            double px = __builtin_fma(X.r02, cz, __builtin_fma(X.r01, cy, __builtin_fma(X.r00, cx, X.p0)));
+            double py = __builtin_fma(X.r12, cz, __builtin_fma(X.r11, cy, __builtin_fma(X.r10, cx, X.p1)));
+            double pz = __builtin_fma(X.r22, cz, __builtin_fma(X.r21, cy, __builtin_fma(X.r20, cx, X.p2)));
+            if (a.xform12) {
+                const double ux = px, uy = py, uz = pz;
+                px = __builtin_fma(t02, uz, __builtin_fma(t01, uy, __builtin_fma(t00, ux, t03)));
+                py = __builtin_fma(t12, uz, __builtin_fma(t11, uy, __builtin_fma(t10, ux, t13)));
+                pz = __builtin_fma(t22, uz, __builtin_fma(t21, uy, __builtin_fma(t20, ux, t23)));
+            }
+            Quad v;
+            v.x = bad ? nan : (T)px; v.y = bad ? nan : (T)py; v.z = bad ? nan : (T)pz; v.w = bad ? nan : (T)im->c[j][3];
+            const int row = im->perm[j];
+            out[row] = v;
+            if (trj) trj[row] = v;
+        }
+        if (i >= n) break;
+        link_joint(X, im->jtype[i], bad ? 0.0 : (double)qs[i]);
+        const double* __restrict__ const Bn = im->B[i + 1];
+        link_fixed_row(X.r00, X.r01, X.r02, X.p0, Bn);
+        link_fixed_row(X.r10, X.r11, X.r12, X.p1, Bn);
+        link_fixed_row(X.r20, X.r21, X.r22, X.p2, Bn);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_link(int io_dtype, const LinkArgs& a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.B + 255) / 256)), blk(256);
+    if (io_dtype == 32) hipLaunchKernelGGL(link_kernel<float>, grid, blk, 0, stream, a.img, a);
+    else hipLaunchKernelGGL(link_kernel<double>, grid, blk, 0, stream, a.img, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_cycle(int io_dtype, int nj, const KArgs& kargs, int block, hipStream_t stream, CyclePlan* plan_out) {
     const bool ns = kargs.flags & VFIK_F_NULLSPACE;

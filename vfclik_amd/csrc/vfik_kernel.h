@@ -11,6 +11,7 @@
 
 #include "../../include/vfik_types.h"
 #include "vfik_kconst.h"
+#include "vfik_links.h"
 
 namespace vfik {
 
@@ -501,6 +502,22 @@ struct ScriptArgs {
     double js_prec[VFIK_MAX_JOINTS], js_via_prec[VFIK_MAX_JOINTS];   // the joint rule's band: at an arm's last step, at those before it
 };
 hipError_t launch_script(int io_dtype, const ScriptArgs& s, hipStream_t stream, const StallArgs* st = nullptr);
+// vfik_link_points (link_kernel<T>, vfik_aux.hip): the centres of the handle's link spheres for every arm, from the joint angles of the arm's
+// SOURCE arm, in the shape vfik_move_fields takes as rep4.  One lane per arm b: s = src_arm ? src_arm[b] : b; a source outside [0, B) or a NaN in
+// q[s] gives L rows of NaN and q is not read for an out-of-range source.  The chain of `img` (vfik_links.h: LinkImage, device memory, read at
+// uniform addresses) is walked once in float64; sphere j of the caller's list goes into row first_rep + j of rep4[b][n_rep][4] as
+// (R_b P + t_b, radius) -- xform12[b] = [R_b | t_b] row-major 3x4, or NULL -- and, when `traj` is given, into row j of traj[b][L][4] too (the
+// trace of a coupled timed move).  Rows outside first_rep .. first_rep + L - 1 are not written.  rep4 and traj are 16-byte aligned.
+struct LinkArgs {
+    const LinkImage* img;
+    const void* q;              // [B][n]
+    const int* src_arm;         // [B] or NULL
+    const void* xform12;        // [B][12] or NULL
+    void* rep4;                 // [B][n_rep][4]
+    void* traj;                 // [B][L][4] or NULL
+    int B, n_rep, first_rep;
+};
+hipError_t launch_link(int io_dtype, const LinkArgs& a, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

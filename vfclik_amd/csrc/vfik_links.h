@@ -1,0 +1,85 @@
+// vfik_links.h -- spheres fixed to links of the chain (vfik_set_link_spheres) and how the host derives what link_kernel reads: the checks of
+// the caller's list, and links_fill: vfik_chain + the spheres -> LinkImage, a small block in device memory that the kernel reads at
+// wave-uniform addresses (scalar loads).  Pure host code on the C++ standard library and include/vfik_types.h: no HIP symbol, so a
+// stand-alone program holds it on the CPU (tests/test_links_host.py).  The device code reads LinkImage through vfik_kernel.h, which includes
+// this header; vfik_abi.cpp uploads the image.
+//
+// Frames are those of the PUBLIC chain, X_link = B[0] Jz(q_1) B[1] ... Jz(q_link) B[link] (vfik_types.h).  The DH form of the cycle kernels
+// (vfik_kconst.h: dh_factor) moves z-screws between neighbouring links -- its intermediate frames are not the caller's -- so KConst is of
+// no use here and the image carries B[0..n] as they came.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+
+#include <stdint.h>
+
+#include "../../include/vfik_types.h"
+
+namespace vfik {
+
+// The walk emits a sphere when it reaches the sphere's link, so the spheres are SORTED BY LINK (stable: spheres of one link keep the caller's
+// order) and perm[] leads back: the sphere at sorted position i is the caller's sphere perm[i], and goes into the caller's row perm[i].
+struct LinkImage {
+    int32_t n, L;                              // joints, spheres
+    int32_t jtype[VFIK_MAX_JOINTS];            // 0 revolute, 1 prismatic; entries from n on are 0
+    int32_t link[VFIK_MAX_LINK_SPHERES];       // ascending; entries from L on are -1
+    int32_t perm[VFIK_MAX_LINK_SPHERES];       // sorted position -> the caller's index; entries from L on are 0
+    double B[VFIK_MAX_JOINTS + 1][12];         // row-major 3x4 [R | p]; entries beyond n are 0
+    double c[VFIK_MAX_LINK_SPHERES][4];        // x y z radius, sorted; entries from L on are 0
+};
+
+// 0, or -1 (VFIK_E_ARG) with the reason in msg: L outside 0..16, a missing list, a link outside 0..n, a centre that is not finite, a radius
+// that is negative or not finite, reserved != 0.
+inline int links_check(const vfik_chain& ch, const vfik_link_sphere* s, int L, char* msg, size_t len) {
+    if (L < 0 || L > VFIK_MAX_LINK_SPHERES) {
+        std::snprintf(msg, len, "%d link spheres: 0..%d", L, VFIK_MAX_LINK_SPHERES);
+        return -1;
+    }
+    if (L > 0 && !s) {
+        std::snprintf(msg, len, "%d link spheres and no list", L);
+        return -1;
+    }
+    for (int j = 0; j < L; ++j) {
+        if (s[j].link < 0 || s[j].link > ch.n) {
+            std::snprintf(msg, len, "link sphere %d: link %d outside 0..%d", j, s[j].link, ch.n);
+            return -1;
+        }
+        if (s[j].reserved != 0) {
+            std::snprintf(msg, len, "link sphere %d: reserved must be 0", j);
+            return -1;
+        }
+        if (!std::isfinite(s[j].c[0]) || !std::isfinite(s[j].c[1]) || !std::isfinite(s[j].c[2])) {
+            std::snprintf(msg, len, "link sphere %d: the centre is not finite", j);
+            return -1;
+        }
+        if (!std::isfinite(s[j].radius) || s[j].radius < 0.0) {
+            std::snprintf(msg, len, "link sphere %d: radius %g must be finite and not negative", j, s[j].radius);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+// The image of a checked list (links_check returned 0).
+inline void links_fill(const vfik_chain& ch, const vfik_link_sphere* s, int L, LinkImage* im) {
+    std::memset(im, 0, sizeof *im);
+    im->n = ch.n;
+    im->L = L;
+    for (int i = 0; i < ch.n; ++i) im->jtype[i] = ch.jtype[i];
+    for (int i = 0; i <= ch.n; ++i) std::memcpy(im->B[i], ch.B[i], sizeof im->B[i]);
+    for (int j = 0; j < VFIK_MAX_LINK_SPHERES; ++j) im->link[j] = -1;
+    int at = 0;
+    for (int l = 0; l <= ch.n; ++l)         // a counting sort by link: stable
+        for (int j = 0; j < L; ++j) {
+            if (s[j].link != l) continue;
+            im->link[at] = l;
+            im->perm[at] = j;
+            im->c[at][0] = s[j].c[0]; im->c[at][1] = s[j].c[1]; im->c[at][2] = s[j].c[2];
+            im->c[at][3] = s[j].radius;
+            ++at;
+        }
+}
+
+}  // namespace vfik

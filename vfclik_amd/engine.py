@@ -96,6 +96,12 @@ def load_library(path=None):
         "vfik_stall_rule_size": (C.c_size_t, []),
         "vfik_set_stall_rule": (C.c_int, [H, C.POINTER(_abi.StallRule)]),
         "vfik_stalled_host": (C.c_int, [H, C.c_void_p]),
+        "vfik_link_sphere_size": (C.c_size_t, []),
+        "vfik_set_link_spheres": (C.c_int, [H, C.c_void_p, C.c_int]),
+        "vfik_link_points": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+        "vfik_link_points_host": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+        "vfik_coupling_size": (C.c_size_t, []),
+        "vfik_set_coupling": (C.c_int, [H, C.POINTER(_abi.Coupling)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -148,7 +154,9 @@ def load_library(path=None):
     for name, size, mirror in (("vfik_goto_js_opts", lib.vfik_goto_js_opts_size(), _abi.GotoJsOpts),
                                ("vfik_follow_js_opts", lib.vfik_follow_js_opts_size(), _abi.FollowJsOpts),
                                ("vfik_script_opts", lib.vfik_script_opts_size(), _abi.ScriptOpts),
-                               ("vfik_stall_rule", lib.vfik_stall_rule_size(), _abi.StallRule)):
+                               ("vfik_stall_rule", lib.vfik_stall_rule_size(), _abi.StallRule),
+                               ("vfik_link_sphere", lib.vfik_link_sphere_size(), _abi.LinkSphere),
+                               ("vfik_coupling", lib.vfik_coupling_size(), _abi.Coupling)):
         if size != C.sizeof(mirror):
             raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
@@ -191,6 +199,8 @@ class Engine:
         self._torch_out = {}
         self.n_objects = 0  # object frames of the distance monitor held by the handle (set_objects)
         self._stall_rule = None  # the stall rule of the timed moves (set_stall_rule), with the caller's stalled array kept alive
+        self.n_links = 0  # link spheres held by the handle (set_link_spheres)
+        self._coupling = None  # the coupling of the timed moves (set_coupling): the device arrays it reads and writes, kept alive
         self._make_specs()
 
     # -- plumbing -------------------------------------------------------------------------------
@@ -201,6 +211,7 @@ class Engine:
     def close(self):
         if getattr(self, "h", None):
             self.lib.vfik_sync(self.h)
+            self._drop_coupling()
             for p in self._pinned:  # arrays handed out by host_array() die with the engine
                 self.lib.vfik_host_free(self.h, C.c_void_p(p))
             self._pinned = []
@@ -302,6 +313,142 @@ class Engine:
             raise ValueError("give goal, repellers or both")
         self._chk(self.lib.vfik_move_fields_host(self.h, int(first_arm), n_arms, None if g is None else g.ctypes.data,
                                                  None if r is None else r.ctypes.data, n_rep))
+
+    # -- arms as each other's obstacles: spheres on links, placed on the device (vfik_set_link_spheres, vfik_link_points, vfik_set_coupling) --
+    def set_link_spheres(self, spheres):
+        """Spheres fixed to links of the chain (include/vfik.h: vfik_set_link_spheres): a sequence of up to 16 ``(link, centre, radius)``
+        -- ``link`` 0 (the base frame) .. n (the flange, no tool), ``centre`` three coordinates in that link's frame of the PUBLIC chain
+        (``Chain.B``), ``radius`` >= 0.  ``None`` or an empty sequence: none.  A new list switches a coupling off."""
+        spheres = list(spheres or ())
+        arr = (_abi.LinkSphere * max(len(spheres), 1))()
+        for s, (link, centre, radius) in zip(arr, spheres):
+            s.link, s.radius = int(link), float(radius)
+            c = np.asarray(centre, dtype=np.float64).reshape(-1)
+            if c.shape != (3,):
+                raise ValueError("a sphere's centre has three coordinates, got %s" % (c.shape,))
+            s.c[0], s.c[1], s.c[2] = c
+        self._chk(self.lib.vfik_set_link_spheres(self.h, C.cast(arr, C.c_void_p) if spheres else None, len(spheres)))
+        self.n_links = len(spheres)
+        self._drop_coupling()
+
+    def link_points(self, q, src_arm=None, xform=None, out=None, n_rep=None, first_rep=0):
+        """Where the link spheres of every arm's source arm are, on the device (include/vfik.h: vfik_link_points): asynchronous on the
+        engine's stream.  ``q`` (batch, n) of the engine's dtype; ``src_arm`` int32 (batch,) -- arm b's obstacles are the links of arm
+        ``src_arm[b]``, itself when None, and a source outside the batch gives NaN rows; ``xform`` (batch, 12) or (batch, 3, 4): where
+        the source's base stands as seen from arm b's.  Rows ``first_rep .. first_rep + L - 1`` of ``out`` (batch, n_rep, 4) = x y z
+        radius are written, the others are not: the shape ``move_fields(repellers=out)`` takes.  Torch tensors on this device, or raw
+        addresses (then ``out`` and ``n_rep`` are required).  Without ``out`` a tensor of ``n_rep`` (default first_rep + L) rows per arm
+        is made, NaN outside the rows written.  Returns ``out``."""
+        B, ft = self.batch, self.io_dtype.name
+        if out is None:
+            import torch
+            n_rep = int(first_rep) + self.n_links if n_rep is None else int(n_rep)
+            out = torch.full((B, n_rep, 4), float("nan"), dtype=getattr(torch, ft), device="cuda:%d" % self.device)
+        elif isinstance(out, int):
+            if n_rep is None:
+                raise ValueError("a raw out address needs n_rep")
+        else:
+            if out.dim() != 3 or out.shape[0] != B or out.shape[2] != 4 or (n_rep is not None and n_rep != out.shape[1]):
+                raise ValueError("out must be (%d, n_rep, 4), got %s" % (B, tuple(out.shape)))
+            n_rep = out.shape[1]
+        if xform is not None and not isinstance(xform, int) and xform.numel() != B * 12:
+            raise ValueError("xform must be (%d, 12) or (%d, 3, 4), got %s" % (B, B, tuple(xform.shape)))
+        self._check_dev((("q", q, (B, self.n), ft), ("src_arm", src_arm, (B,), "int32"), ("xform", xform, None, ft), ("out", out, None, ft)))
+        self._chk(self.lib.vfik_link_points(self.h, C.c_void_p(_ptr(q)), C.c_void_p(_ptr(src_arm)), C.c_void_p(_ptr(xform)),
+                                            C.c_void_p(_ptr(out)), int(n_rep), int(first_rep)))
+        return out
+
+    def link_points_host(self, q, src_arm=None, xform=None, out=None, n_rep=None, first_rep=0):
+        """The host form (vfik_link_points_host; synchronous): NumPy arrays of doubles, ``q`` and ``xform`` rounded to the engine's dtype.
+        Returns float64 (batch, n_rep, 4): ``out`` with the rows ``first_rep .. first_rep + L - 1`` replaced by the engine-typed values, or
+        a new array that is NaN elsewhere."""
+        B = self.batch
+        qh = np.ascontiguousarray(q, dtype=np.float64)
+        if qh.shape != (B, self.n):
+            raise ValueError("q must be (%d, %d), got %s" % (B, self.n, qh.shape))
+        sh = None if src_arm is None else np.ascontiguousarray(src_arm, dtype=np.int32)
+        if sh is not None and sh.shape != (B,):
+            raise ValueError("src_arm must be (%d,), got %s" % (B, sh.shape))
+        xh = None if xform is None else np.ascontiguousarray(xform, dtype=np.float64)
+        if xh is not None and xh.size != B * 12:
+            raise ValueError("xform must be (%d, 12) or (%d, 3, 4), got %s" % (B, B, xh.shape))
+        if out is None:
+            n_rep = int(first_rep) + self.n_links if n_rep is None else int(n_rep)
+            out = np.full((B, n_rep, 4), np.nan)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.ndim == 3
+                  and out.shape[0] == B and out.shape[2] == 4 and n_rep in (None, out.shape[1])):
+            raise ValueError("out must be a contiguous float64 array of shape (%d, n_rep, 4)" % B)
+        self._chk(self.lib.vfik_link_points_host(self.h, qh.ctypes.data, None if sh is None else sh.ctypes.data,
+                                                 None if xh is None else xh.ctypes.data, out.ctypes.data, out.shape[1], int(first_rep)))
+        return out
+
+    def _drop_coupling(self):
+        if self._coupling is not None:
+            if self._coupling["own"]:
+                self.lib.vfik_sync(self.h)   # an enqueued move may still read the arrays the engine uploaded
+            for p in self._coupling["own"]:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            self._coupling = None
+
+    def _upload(self, arr, own):
+        p = self.dev_alloc(max(arr.nbytes, 16))
+        own.append(p)
+        self.h2d(p, arr)
+        return p
+
+    def set_coupling(self, src_arm=None, xform=None, first_rep=0, link_traj=None, trace_checks=None):
+        """Couple the arms inside every timed move from now on (include/vfik.h: vfik_set_coupling): in front of each block the link spheres
+        of arm ``src_arm[b]`` (-1: none), seen through ``xform[b]``, become arm b's ``first_rep``-th .. decay repellers in ascending-id
+        order.  ``src_arm`` / ``xform``: torch tensors on this device or raw addresses, used as they are, or NumPy arrays / sequences,
+        which are uploaded (``xform`` rounded to the engine's dtype) and kept alive by the engine.  ``link_traj``: a device array
+        (n_checks, batch, L, 4) that receives the rows every block started from; ``trace_checks=N`` instead: the engine keeps such a trace
+        of N checks itself, read with :meth:`link_traj`.  ``set_coupling(None)`` -- no source, no transform, no trace -- switches the
+        coupling off, the default; arms that are their own sources take ``src_arm=np.arange(batch)``."""
+        self._chk(self.lib.vfik_set_coupling(self.h, None))
+        self._drop_coupling()
+        if src_arm is None and xform is None and link_traj is None and trace_checks is None:
+            if first_rep != 0:
+                raise ValueError("first_rep without a source, a transform or a trace: set_coupling(None) switches the coupling off")
+            return
+        if link_traj is not None and trace_checks is not None:
+            raise ValueError("give link_traj (a device array of the caller's) or trace_checks (a trace of the engine's), not both")
+        B, L, ft, own = self.batch, self.n_links, self.io_dtype, []
+        try:
+            if src_arm is not None and not isinstance(src_arm, int) and not hasattr(src_arm, "data_ptr"):
+                sa = np.ascontiguousarray(src_arm, dtype=np.int32)
+                if sa.shape != (B,):
+                    raise ValueError("src_arm must be (%d,), got %s" % (B, sa.shape))
+                src_arm = self._upload(sa, own)
+            if xform is not None and not isinstance(xform, int) and not hasattr(xform, "data_ptr"):
+                xa = np.ascontiguousarray(xform, dtype=ft)
+                if xa.size != B * 12:
+                    raise ValueError("xform must be (%d, 12) or (%d, 3, 4), got %s" % (B, B, xa.shape))
+                xform = self._upload(xa, own)
+            n_traj = None
+            if trace_checks is not None:
+                n_traj = int(trace_checks)
+                if n_traj < 1:
+                    raise ValueError("trace_checks must be at least 1, got %d" % n_traj)
+                link_traj = self._upload(np.full((n_traj, B, L, 4), np.nan, dtype=ft), own)
+            self._check_dev((("src_arm", src_arm, (B,), "int32"), ("xform", xform, None, ft.name), ("link_traj", link_traj, None, ft.name)))
+            c = _abi.Coupling()
+            c.src_arm, c.xform12, c.link_traj, c.first_rep = _ptr(src_arm), _ptr(xform), _ptr(link_traj), int(first_rep)
+            self._chk(self.lib.vfik_set_coupling(self.h, C.byref(c)))
+        except Exception:
+            for p in own:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            raise
+        self._coupling = {"own": own, "keep": (src_arm, xform, link_traj), "traj": link_traj if n_traj else None, "n_traj": n_traj}
+
+    def link_traj(self):
+        """The engine's own trace of a coupling set with ``trace_checks=n_checks``: (n_checks, batch, L, 4) of the engine's dtype, row k what
+        block k of the last timed move started from (NaN: a block that never ran).  Synchronises."""
+        if self._coupling is None or self._coupling["traj"] is None:
+            raise VfikError("no coupling with a trace of the engine's own: set_coupling(..., trace_checks=n_checks)")
+        out = np.empty((self._coupling["n_traj"], self.batch, self.n_links, 4), dtype=self.io_dtype)
+        self.sync()
+        self.d2h(out, self._coupling["traj"])
+        return out
 
     # (name, vfik_scene_move member, its count member, elements per row; None: one row per arm)
     _SCENE_ROWS = (("goal", "goal16", None, 16), ("repellers", "rep4", "n_rep", 4), ("funnels", "fun6", "n_fun", 6),

@@ -274,6 +274,58 @@ class ShardedEngine:
         import numpy as np
         return np.concatenate([e.stalled() for e in self.engines], axis=0)
 
+    # -- arms as each other's obstacles: a source arm must live on the engine of the arm it is an obstacle for -----------------------------
+    def set_link_spheres(self, spheres):
+        """Engine.set_link_spheres on every engine of this rank: the spheres sit on the chain's links, the same for every arm."""
+        for e in self.engines:
+            e.set_link_spheres(spheres)
+
+    def _local_sources(self, src_arm, global_rows):
+        """src_arm in GLOBAL arm indices (global or this rank's rows) -> per part the indices inside that part's engine; None: every arm
+        its own source.  A negative index stays (no source).  ValueError when an arm's source lies on another engine: there is no
+        plumbing between handles (include/vfik.h: vfik_link_points)."""
+        import numpy as np
+        if src_arm is None:
+            return [None] * len(self.parts)
+        out = []
+        for (a, b, _), rows in zip(self.parts, self._rows(np.asarray(src_arm), "src_arm", global_rows)):
+            rows = np.asarray(rows, dtype=np.int64)
+            away = (rows >= 0) & ((rows < a) | (rows >= b))
+            if away.any():
+                k = int(np.flatnonzero(away)[0])
+                raise ValueError("arm %d: its source arm %d lies in another shard (this one holds arms %d..%d)" % (a + k, rows[k], a, b - 1))
+            out.append(np.where(rows >= 0, rows - a, rows).astype(np.int32))
+        return out
+
+    def link_points_host(self, q, src_arm=None, xform=None, n_rep=None, first_rep=0, global_rows=True):
+        """Engine.link_points_host over this rank's arms: ``q`` (rows, n) and ``xform`` (rows, 12) are sharded with the arms, ``src_arm``
+        (rows,) holds GLOBAL arm indices and is translated per shard.  Returns this rank's rows (local_rows, n_rep, 4) in arm order."""
+        import numpy as np
+        srcs = self._local_sources(src_arm, global_rows)
+        qs = self._rows(np.asarray(q), "q", global_rows)
+        xs = self._rows(None if xform is None else np.asarray(xform).reshape(len(xform), 12), "xform", global_rows)
+        outs = [e.link_points_host(qs[i], srcs[i], xs[i], n_rep=n_rep, first_rep=first_rep) for i, e in enumerate(self.engines)]
+        return np.concatenate(outs, axis=0) if outs else np.zeros((0, n_rep or 0, 4))
+
+    def set_coupling(self, src_arm=None, xform=None, first_rep=0, trace_checks=None, global_rows=True):
+        """Engine.set_coupling on every engine of this rank; ``src_arm`` in GLOBAL arm indices, ``xform`` sharded with the arms, both
+        host arrays; ``trace_checks``: None or the number of checks every engine keeps a trace of (:meth:`link_traj`).
+        ``set_coupling(None)`` switches the coupling off."""
+        import numpy as np
+        if src_arm is None and xform is None and trace_checks is None:
+            for e in self.engines:
+                e.set_coupling(None)
+            return
+        srcs = self._local_sources(src_arm, global_rows)   # (None: every arm its own source, on whichever engine it lives)
+        xs = self._rows(None if xform is None else np.asarray(xform).reshape(len(xform), 12), "xform", global_rows)
+        for i, e in enumerate(self.engines):
+            e.set_coupling(src_arm=srcs[i], xform=xs[i], first_rep=first_rep, trace_checks=trace_checks)
+
+    def link_traj(self):
+        """Engine.link_traj of this rank's arms, along their arm axis."""
+        import numpy as np
+        return np.concatenate([e.link_traj() for e in self.engines], axis=1)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
