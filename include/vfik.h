@@ -292,8 +292,16 @@ int vfik_wait(vfik_handle* h, long ticket);
  * configuration; the outputs named in io are those of the LAST cycle; q_out[B][n] (may be NULL) receives
  * the joint angles after it.  Field sets, tools, weights and /control stay fixed during the launch,
  * as they do between two messages in the reference; the nullspace sign memory advances every cycle.
- * Chains of up to 7 joints run all cycles inside one kernel; longer chains (no registers left for
- * loop-carried state) run n_cycles single-cycle launches that integrate q on the way out -- same results.
+ * All-revolute chains of up to 7 joints whose batch-wide tool is the identity and whose batch-wide IK
+ * weights are all 1 run all cycles inside one kernel, q carried in double from cycle to cycle.  Every
+ * other handle -- a longer chain, a prismatic joint, a shared tool or batch-wide weights other than
+ * those, and ANY per-arm tool or per-arm weight array the handle holds, whatever its values (equal
+ * per-arm rows that vfik_set_tool / vfik_set_arm_weights stored as batch-wide ones count as batch-wide):
+ * no registers left for loop-carried state -- runs n_cycles single-cycle launches that integrate q on
+ * the way out.  Those hand q from launch to launch in the io dtype: the same results at float64 I/O,
+ * and at float32 I/O the results of a caller that steps the cycles itself and keeps q in float32 (q is
+ * rounded to float32 behind every cycle, not only behind the last one).  A block of vfik_goto and its
+ * kin is such a rollout of `stride` cycles.
  * Device pointers, asynchronous; vfik_rollout_host takes host pointers and synchronises. */
 int vfik_rollout(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp_to_limits, void* q_out);
 int vfik_rollout_host(vfik_handle* h, const vfik_io* io, int n_cycles, double dt, int clamp_to_limits, void* q_out);
