@@ -627,6 +627,70 @@ typedef struct vfik_coupling {
 size_t vfik_coupling_size(void);
 int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c);   /* NULL: off (the default) */
 
+/* Link-sphere clearance.  The field is evaluated at one point, the tool: repellers push the hand away from a neighbour's links and do
+ * nothing for the elbow.  vfik_link_clearance is the measurement: for every arm b, how much room is left between its OWN link spheres
+ * (vfik_set_link_spheres) at q[b] and a set of other spheres, and which pair is the closest.  The reference has no such thing (its arms
+ * meet only as re-sent ObstacleP objects).
+ *   q      [B][n], pts4 [B][n_rep][4]: DEVICE arrays of the io dtype.  pts4 holds x y z radius rows, the shape vfik_link_points writes and
+ *          vfik_move_fields reads: a neighbour's links (this handle's or another handle's on the same stream), the handle's own links
+ *          for self-collision, or static obstacles.  Only rows first .. first + count - 1 of an arm are looked at.
+ *   walk   the chain is walked once from q[b] in float64, in the frames vfik_link_points uses (the public chain, link 0 the base, link n
+ *          the flange, no tool).  Own sphere i, in the CALLER's order, sits at P_i = X_link_i(q_b) c_i; row j (counted from `first`) is
+ *          (Q_j, R_j) widened exactly;  d_ij = sqrt(|P_i - Q_j|^2) - r_i - R_j  from the coordinate differences, in float64.
+ *   clear  [B] io dtype: the minimum of d_ij over the pairs considered, rounded to the io dtype;  pair [B] int32 or NULL: i * 32 + j of it.
+ *   pairs  considered when mask == NULL or bit j of mask[i] is set (a HOST array of L words, read during the call), and row j holds no
+ *          NaN: the library's "leave as it is" row is no obstacle.  Ties take the smallest code.  No pair considered: clear = +inf,
+ *          pair = -1.  A NaN anywhere in q[b]: clear = NaN, pair = -1.
+ * Asynchronous on the handle's stream, no allocation, ordered like vfik_link_points (the wait for outstanding vfik_submit_host tickets
+ * included); no launch decision and no epoch moves; valid under stream capture.
+ * VFIK_E_ARG: count outside 1..32, first < 0, first + count > n_rep, q / pts4 / clear NULL, pts4 not 16-byte aligned, a mask bit at or
+ * beyond count; VFIK_E_STATE: no spheres set. */
+int vfik_link_clearance(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count,
+                        const uint32_t* mask /* host [L] or NULL */, void* clear /* [B] io dtype */, int32_t* pair /* [B] or NULL */);
+/* The same with HOST arrays: q [B][n] and pts4 [B][n_rep][4] doubles, rounded to the io dtype as vfik_link_points_host rounds its rows;
+ * clear [B] doubles receives the io-typed values, widened; pair int32 [B] or NULL.  Copies, launches and synchronises; the alignment rule
+ * does not apply. */
+int vfik_link_clearance_host(vfik_handle* h, const double* q, const double* pts4, int n_rep, int first, int count, const uint32_t* mask,
+                             double* clear, int32_t* pair);
+
+/* Arms that wait for room: stop-and-wait by priority inside the timed moves.  State of the HANDLE like the stall rule and the coupling, off
+ * by default; with the rule off nothing changes -- the same launches, the same results.  The rule needs a coupling (vfik_set_coupling) and
+ * goes when the coupling goes: a new sphere list, vfik_set_coupling(h, NULL), vfik_set_chain.
+ * While it is set, every block k of the five timed moves enqueues, after the coupling's two launches and in front of its cycles, the
+ * measurement of vfik_link_clearance on the block's INPUT row of joint angles against rows first_rep .. first_rep + L - 1 of the handle's
+ * coupling buffer: the partner's links as just placed, NaN for an arm without a source.  It
+ *   writes clear_traj[k][b] and pair_traj[k][b] for every arm (where given), and
+ *   for an arm with gate[b] == 1 and yields[b] != 0 whose io-typed clearance, widened to double, is < min_clearance: sets gate[b] = 0 for
+ *   this block and counts it in waited[b].  The compare is strict: NaN and +inf never wait.  Block 0 stores the count, later blocks add.
+ * The check after the block treats a gated arm as one that did not run -- its rows repeat, no arrival rule and no stall rule is applied
+ * to it, it stays in pending -- and rewrites the gate from the state machine alone, so a waiting arm runs again as soon as the room is
+ * back.  A move under a rule always runs under the handle's gate (as with hold); the *_host forms copy the caller's rows of the gated
+ * outputs in first (an arm that waits through block 0 has no distance row of its own yet).
+ *   min_clearance  finite.
+ *   yields         DEVICE int32 [B] or NULL (every arm): only an arm with yields[b] != 0 ever waits -- the caller's priority tool.
+ *   mask           own sphere i against partner sphere j, as in vfik_link_clearance; all sixteen words zero = every pair.
+ *   clear_traj, pair_traj   DEVICE [n_checks][B] (io dtype, int32) or NULL; the caller sizes them for the moves it runs.
+ *   waited         DEVICE int32 [B], or NULL: an array of the handle, read with vfik_waited_host.
+ * Deliberately out of scope: an arm that never gets room waits until the time-out and keeps pending up; two arms that both yield can wait
+ * for each other -- `yields` is the remedy: one arm of a pair yields, the other does not.  Taking a waiting arm out of pending after a
+ * patience count belongs in the check kernels, next to the stall rule.
+ * vfik_set_wait_rule may allocate (never under capture: VFIK_E_STATE), synchronises, and leaves vfik_launch_epoch and every launch
+ * decision alone; the pointers are kept, not copied.  VFIK_E_ARG: min_clearance not finite, reserved != 0, a mask bit at or beyond L,
+ * yields / clear_traj / pair_traj / waited no device pointer of its alignment (int32; the io type); VFIK_E_STATE: no coupling set.
+ * vfik_waited_host copies waited[B] of the last timed move to the host and synchronises; VFIK_E_STATE without a rule or under capture. */
+typedef struct vfik_wait_rule {
+    double min_clearance;        /* finite */
+    const int32_t* yields;       /* device [B] or NULL (every arm): only an arm with yields[b] != 0 ever waits */
+    uint32_t mask[16];           /* own sphere i against partner sphere j; all zero = every pair */
+    void* clear_traj;            /* device [n_checks][B] io dtype or NULL */
+    int32_t* pair_traj;          /* device [n_checks][B] or NULL */
+    int32_t* waited;             /* device [B] or NULL: the handle's own array, read with vfik_waited_host */
+    int32_t reserved;            /* 0 */
+} vfik_wait_rule;
+size_t vfik_wait_rule_size(void);
+int vfik_set_wait_rule(vfik_handle* h, const vfik_wait_rule* r);   /* NULL: off (the default) */
+int vfik_waited_host(vfik_handle* h, int32_t* out /* host [B] */);
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

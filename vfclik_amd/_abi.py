@@ -114,6 +114,12 @@ class Coupling(C.Structure):
                 ("link_traj", C.c_void_p)]
 
 
+class WaitRule(C.Structure):
+    """``struct vfik_wait_rule`` (include/vfik.h: vfik_set_wait_rule)."""
+    _fields_ = [("min_clearance", C.c_double), ("yields", C.c_void_p), ("mask", C.c_uint32 * MAX_LINK_SPHERES), ("clear_traj", C.c_void_p),
+                ("pair_traj", C.c_void_p), ("waited", C.c_void_p), ("reserved", C.c_int32)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

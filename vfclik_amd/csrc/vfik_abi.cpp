@@ -123,6 +123,13 @@ struct vfik_handle {
     bool couple_on = false;
     vfik_coupling couple{};
     DevBuf couple_rep;
+    // vfik_link_clearance: the image as the host keeps it (the mask is permuted by its perm[]); vfik_set_wait_rule: the rule every block of a
+    // timed move under a coupling applies (wait_on), its mask in the image's order, and waited[B] where the caller names no array of its own
+    vfik::LinkImage link_img{};
+    bool wait_on = false;
+    vfik_wait_rule wait{};
+    uint32_t wait_mask[VFIK_MAX_LINK_SPHERES] = {};
+    int* d_wait_own = nullptr;
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -445,7 +452,7 @@ void vfik_destroy(vfik_handle* h) {
     void* ptrs[] = {h->d_arena, h->d_tool, h->d_ext, h->d_mixw, h->d_stamps, h->d_mixw_arm, h->d_track, h->d_wts, h->d_rollq[0], h->d_rollq[1], h->d_objects, h->d_obs_pose, h->d_obs_v6,
                     h->d_qalign, h->d_repmap, h->d_scenemap, h->move_stage.p, h->d_goto_gate, h->goto_pending.p, h->d_goto_dist, h->d_gotoq[0], h->d_gotoq[1],
                     h->goto_stage.p, h->d_follow_len, h->d_js_ref, h->d_script_mixw, h->d_stall_best, h->d_stall_count, h->d_stall_own,
-                    h->d_link_img, h->link_stage.p, h->couple_rep.p};
+                    h->d_link_img, h->link_stage.p, h->couple_rep.p, h->d_wait_own};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->arena_dev) (void)hipFree(h->arena_dev);
     if (h->arena_host) (void)hipHostFree(h->arena_host);
@@ -492,7 +499,7 @@ int vfik_set_chain(vfik_handle* h, const vfik_chain* c) {
     h->chain_set = true;
     const int rc = upload_kconst(h);
     if (rc != VFIK_OK) { h->chain = saved; h->chain_set = was_set; }
-    else { h->n_links = 0; h->couple_on = false; }   // (the link spheres were those of the old chain's frames)
+    else { h->n_links = 0; h->couple_on = false; h->wait_on = false; }   // (the link spheres were those of the old chain's frames)
     return rc;
 }
 
@@ -791,9 +798,11 @@ int vfik_set_link_spheres(vfik_handle* h, const vfik_link_sphere* s, int L) {
     HIP_TRY(hipStreamSynchronize(h->stream));   // (an earlier vfik_link_points may still read the old image)
     HIP_TRY(hipMemcpyAsync(h->d_link_img, &img, sizeof img, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->link_img = img;
     for (int j = 0; j < L; ++j) h->links[j] = s[j];
     h->n_links = L;
     h->couple_on = false;   // (its buffer has the old list's rows)
+    h->wait_on = false;     // (the rule reads that buffer)
     return VFIK_OK;
 }
 
@@ -861,7 +870,7 @@ size_t vfik_coupling_size(void) { return sizeof(vfik_coupling); }
 
 int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c) {
     if (check_handle(h)) return VFIK_E_ARG;
-    if (!c) { h->couple_on = false; return VFIK_OK; }
+    if (!c) { h->couple_on = false; h->wait_on = false; return VFIK_OK; }
     if (h->n_links < 1) return fail(VFIK_E_STATE, "vfik_set_coupling before vfik_set_link_spheres: there is nothing to couple");
     if (c->reserved != 0) return fail(VFIK_E_ARG, "coupling: reserved must be 0");
     if (c->first_rep < 0 || c->first_rep + h->n_links > h->max_slots)
@@ -881,6 +890,116 @@ int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->couple = *c;
     h->couple_on = true;
+    return VFIK_OK;
+}
+
+// ---- link-sphere clearance (clear_kernel, vfik_aux.hip; the checks and the mask's permutation: vfik_links.h) ----
+// what the two forms of vfik_link_clearance share: the checks, then the mask in the image's order into the kernel's arguments
+static int clear_args(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count, const uint32_t* mask, void* clear,
+                      vfik::ClearArgs& a) {
+    char msg[160];
+    const int rc = vfik::clear_check(h->n_links, q, pts4, clear, n_rep, first, count, mask, msg, sizeof msg);
+    if (rc != 0) return fail(rc, "vfik_link_clearance: %s", msg);
+    a = vfik::ClearArgs{};
+    a.img = static_cast<const vfik::LinkImage*>(h->d_link_img);
+    a.B = h->B; a.n_rep = n_rep; a.first = first; a.count = count;
+    vfik::clear_mask(h->link_img, mask, count, a.mask);
+    return VFIK_OK;
+}
+
+static int clear_launch(vfik_handle* h, const vfik::ClearArgs& a) {
+    const hipError_t e = vfik::launch_clear(h->io_dtype, a, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "clearance launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+int vfik_link_clearance(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count, const uint32_t* mask, void* clear,
+                        int32_t* pair) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    vfik::ClearArgs a;
+    const int rc = clear_args(h, q, pts4, n_rep, first, count, mask, clear, a);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    a.q = q; a.pts4 = pts4; a.clear = clear; a.pair = pair;
+    return clear_launch(h, a);
+}
+
+int vfik_link_clearance_host(vfik_handle* h, const double* q, const double* pts4, int n_rep, int first, int count, const uint32_t* mask,
+                             double* clear, int32_t* pair) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    vfik::ClearArgs a;
+    alignas(16) static const char aligned_stand_in = 0;   // (the caller's pts4 is copied: its alignment is not the kernel's concern)
+    const int rc = clear_args(h, q, pts4 ? &aligned_stand_in : nullptr, n_rep, first, count, mask, clear, a);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_link_clearance_host copies and synchronises: not while the stream is being captured")) return VFIK_E_STATE;
+    // one stage: q | the rows (16-byte aligned) | clear | pair
+    const size_t B = (size_t)h->B, nq = B * h->n, np = B * (size_t)n_rep * 4;
+    const size_t pts_off = (nq * h->esz + 15) / 16 * 16, clear_off = pts_off + np * h->esz, pair_off = (clear_off + B * h->esz + 15) / 16 * 16;
+    std::vector<char> buf(pair_off + B * sizeof(int32_t));
+    for (size_t k = 0; k < nq; ++k) put_io(h, buf, k, q[k]);
+    for (size_t k = 0; k < np; ++k) put_io(h, buf, pts_off / h->esz + k, pts4[k]);
+    if (reserve(h, h->link_stage, buf.size(), true, true) != VFIK_OK) return VFIK_E_HIP;
+    char* const d = static_cast<char*>(h->link_stage.p);
+    HIP_TRY(hipMemcpyAsync(d, buf.data(), clear_off, hipMemcpyHostToDevice, h->stream));
+    a.q = d; a.pts4 = d + pts_off; a.clear = d + clear_off; a.pair = reinterpret_cast<int32_t*>(d + pair_off);
+    const int rl = clear_launch(h, a);
+    if (rl != VFIK_OK) return rl;
+    HIP_TRY(hipMemcpyAsync(buf.data() + clear_off, d + clear_off, buf.size() - clear_off, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b) {
+        const char* src = buf.data() + clear_off + b * h->esz;
+        if (h->io_dtype == 32) { float f; std::memcpy(&f, src, sizeof f); clear[b] = f; } else std::memcpy(&clear[b], src, sizeof(double));
+    }
+    if (pair) std::memcpy(pair, buf.data() + pair_off, B * sizeof(int32_t));
+    return VFIK_OK;
+}
+
+// ---- arms that wait for room: the rule every block of a timed move under a coupling applies (wait_block) ----
+size_t vfik_wait_rule_size(void) { return sizeof(vfik_wait_rule); }
+
+int vfik_set_wait_rule(vfik_handle* h, const vfik_wait_rule* r) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!r) { h->wait_on = false; return VFIK_OK; }
+    if (!h->couple_on) return fail(VFIK_E_STATE, "vfik_set_wait_rule before vfik_set_coupling: the rule measures against the coupling's rows");
+    if (!std::isfinite(r->min_clearance)) return fail(VFIK_E_ARG, "wait rule: min_clearance must be finite");
+    if (r->reserved != 0) return fail(VFIK_E_ARG, "wait rule: reserved must be 0");
+    const int L = h->n_links;
+    bool any = false;
+    for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i) any = any || r->mask[i] != 0;
+    for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i)
+        if ((i >= L && r->mask[i] != 0) || (r->mask[i] >> L) != 0)
+            return fail(VFIK_E_ARG, "wait rule: mask[%d] = 0x%08x names a sphere at or beyond the %d of the handle", i, (unsigned)r->mask[i], L);
+    const struct { const char* name; const void* p; } ints[] = {{"yields", r->yields}, {"pair_traj", r->pair_traj}, {"waited", r->waited}};
+    for (const auto& x : ints)
+        if (x.p && (!gpu_visible(x.p) || reinterpret_cast<uintptr_t>(x.p) % sizeof(int32_t)))
+            return fail(VFIK_E_ARG, "wait rule: %s must be an int32-aligned DEVICE pointer", x.name);
+    if (r->clear_traj && (!gpu_visible(r->clear_traj) || reinterpret_cast<uintptr_t>(r->clear_traj) % h->esz))
+        return fail(VFIK_E_ARG, "wait rule: clear_traj must be a DEVICE pointer aligned to the I/O type");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_set_wait_rule allocates the handle's waited[B]: call it before capturing the stream")) return VFIK_E_STATE;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    if (!h->d_wait_own) {
+        if (dev_alloc(h, (void**)&h->d_wait_own, (size_t)h->B * sizeof(int32_t), false)) return VFIK_E_HIP;
+        HIP_TRY(hipMemsetAsync(h->d_wait_own, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (nobody waited before the first timed move)
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->wait = *r;
+    vfik::clear_mask(h->link_img, any ? r->mask : nullptr, L, h->wait_mask);
+    h->wait_on = true;
+    return VFIK_OK;
+}
+
+int vfik_waited_host(vfik_handle* h, int32_t* out) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (!out) return fail(VFIK_E_ARG, "vfik_waited_host: out[B] is required");
+    if (!h->wait_on) return fail(VFIK_E_STATE, "vfik_waited_host: the handle has no wait rule (vfik_set_wait_rule)");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_waited_host copies to the host and synchronises: not while the stream is being captured")) return VFIK_E_STATE;
+    HIP_TRY(hipMemcpyAsync(out, h->wait.waited ? h->wait.waited : h->d_wait_own, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return VFIK_OK;
 }
 
@@ -1346,7 +1465,7 @@ int timed_check(vfik_handle* h, TimedMove& m) {
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
     if (h->couple_on && !h->fields_set) return fail(VFIK_E_STATE, "a timed move under a coupling before any vfik_set_fields: there are no repellers to move");
     m.n_checks = m.n_cycles / m.stride;
-    m.gated = m.hold || io->active || m.list || (h->stall_on && h->stall.stop);   // (a stalled arm that stops is gated like a held one)
+    m.gated = m.hold || io->active || m.list || (h->stall_on && h->stall.stop) || h->wait_on;   // (a stalled arm that stops, and one that waits, are gated like a held one)
     return VFIK_OK;
 }
 
@@ -1547,6 +1666,24 @@ int couple_block(vfik_handle* h, int k, const void* q_prev) {
     return rc != VFIK_OK ? rc : move_launch(h, 0, h->B, nullptr, h->couple_rep.p, n_rep, nullptr);
 }
 
+// The handle's wait rule (vfik_set_wait_rule) behind the coupling's two launches: every arm's clearance at the block's input row against the
+// partner's rows as just placed, into row k of the rule's traces, and the gate of this block cleared for the arms that yield and lack room.
+int wait_block(vfik_handle* h, int k, const void* q_prev) {
+    const int L = h->n_links;
+    vfik::ClearArgs a{};
+    a.img = static_cast<const vfik::LinkImage*>(h->d_link_img);
+    a.q = q_prev; a.pts4 = h->couple_rep.p;
+    a.B = h->B; a.n_rep = h->couple.first_rep + L; a.first = h->couple.first_rep; a.count = L;
+    std::memcpy(a.mask, h->wait_mask, sizeof a.mask);
+    if (h->wait.clear_traj) a.clear = static_cast<char*>(h->wait.clear_traj) + (size_t)k * h->B * h->esz;
+    if (h->wait.pair_traj) a.pair = h->wait.pair_traj + (size_t)k * h->B;
+    a.gate = h->d_goto_gate; a.yields = h->wait.yields;
+    a.waited = h->wait.waited ? h->wait.waited : h->d_wait_own;
+    a.min_clearance = h->wait.min_clearance;
+    a.first_block = k == 0;
+    return clear_launch(h, a);
+}
+
 // block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
 int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     const vfik::BlockRows w = vfik::block_rows(m, timed_dims(h, m), k, h->d_gotoq, h->d_goto_dist);
@@ -1556,7 +1693,8 @@ int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     if ((m.joint && m.list) || m.script) b.q_ref = h->d_js_ref;
     b.active = m.gated ? h->d_goto_gate : nullptr;   // (the gate is all ones from start to end: the launch without one stores the same rows)
     if (h->couple_on) {
-        const int rl = couple_block(h, k, w.q_prev);
+        int rl = couple_block(h, k, w.q_prev);
+        if (rl == VFIK_OK && h->wait_on) rl = wait_block(h, k, w.q_prev);
         if (rl != VFIK_OK) return rl;
     }
     const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0, m.script ? h->d_script_mixw : nullptr);
@@ -1620,7 +1758,7 @@ int timed_run_host(vfik_handle* h, TimedMove& m, int poll_checks, int* checks_ru
     st.map(h->goto_stage.p);
     int rc = copy_members(st, IoStaging::INPUTS, h->stream);
     if (rc != VFIK_OK) return rc;
-    const bool kept_out = m.io->active || (m.script ? any_arm_without_script(h, static_cast<const int32_t*>(m.x[vfik::X_KIND]), d.W)
+    const bool kept_out = m.io->active || h->wait_on || (m.script ? any_arm_without_script(h, static_cast<const int32_t*>(m.x[vfik::X_KIND]), d.W)
                                                     : m.list && any_arm_kept_out(h, m.x[m.joint ? vfik::X_WAYQ : vfik::X_WAY16], d.W * (m.joint ? d.n : 16)));
     if (kept_out && (rc = copy_members(st, IoStaging::GATED_OUTPUTS, h->stream)) != VFIK_OK) return rc;
     if (m.script && !kept_out) {   // an arm that meets no posture step keeps its diff row, under no gate at all

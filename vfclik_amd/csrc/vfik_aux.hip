@@ -3,6 +3,7 @@
 //   move_kernel, move_scene_kernel                              goals, obstacles, funnels, hemispheres and attractors that move
 //   check_kernel, script_kernel (+ the _stall_ builds)          the check after each block of a timed move (vfik_check_body.inc, twice)
 //   link_kernel                                                 sphere centres on the links of a source arm: the other arm as an obstacle
+//   clear_kernel                                                the room between an arm's own link spheres and other spheres; the wait rule
 //   launch_cycle                                                a launch's plan (vfik_kernel.h: plan_cycle) -> the entry point of the object that holds
 //                                                               its kernel (vfik_kernel.hip, compiled per joint count, I/O type, nullspace module)
 // Compiled once (csrc/Makefile: vfik_dispatch.o).  The float64 building blocks are vfik_device.h, shared with the cycle kernels.
@@ -563,7 +564,104 @@ __global__ void __launch_bounds__(256) link_kernel(const LinkImage* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// vfik_link_clearance: the room between an arm's own link spheres and a set of other spheres (ClearArgs, vfik_kernel.h).  link_kernel's walk
+// with another thing done at every sphere: one lane per arm b walks its OWN chain from q[b] -- link_joint, link_fixed_row, twelve named
+// doubles, the image read at uniform addresses -- and when the walk stands at a link, every sphere of that link meets the arm's `count` rows
+// of pts4: the distance from the coordinate differences in float64, less both radii.  The running minimum is one double and one code; the
+// pair mask comes by value in the image's sorted order and is indexed by the uniform sphere counter alone (a scalar load from the kernel
+// arguments), so a masked pair costs a scalar branch and no load.  The kernel visits own spheres in LINK order, not the caller's: a tie is
+// settled by a compare on the code.  No register array indexed at run time, no scratch.
+// The rows: an arm's `count` rows are wanted once per own sphere, up to 16 times, and lie at a per-lane stride of n_rep quads in memory.  They
+// are read from there ONCE and staged in LDS -- 16-byte units, unit u of lane t at [u * 64 + t]: a wave's ds_read_b128 covers 1 KiB of
+// consecutive banks, no conflict -- in blocks of ONE wave: count KiB of dynamic LDS at float32, twice that at float64, 64 KiB at the most, so
+// a CU's 160 KiB hold two workgroups (float64, count 32) or more -- at count 8 and under as many as there are wave slots.  Every lane reads back only what it wrote: no barrier.  Against
+// re-reading the rows through the cache this is 19 % (float32) to 28 % (float64) faster at L = count = 8 and 2 to 4 % slower at 3
+// (profiles/clearance_cost.txt).
+// With a gate (the wait rule of the timed moves) the lane then decides whether its arm waits through the block that follows.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned int ClearU4 __attribute__((ext_vector_type(4)));
+typedef float ClearF4 __attribute__((ext_vector_type(4)));
+typedef double ClearD2 __attribute__((ext_vector_type(2)));
+
+// a staged row, its 16-byte units 64 apart, widened exactly
+__device__ __forceinline__ void clear_row(const ClearU4* p, float, double& x, double& y, double& z, double& w) {
+    const ClearF4 f = (ClearF4)p[0];
+    x = (double)f.x; y = (double)f.y; z = (double)f.z; w = (double)f.w;
+}
+__device__ __forceinline__ void clear_row(const ClearU4* p, double, double& x, double& y, double& z, double& w) {
+    const ClearD2 a = (ClearD2)p[0], b = (ClearD2)p[64];
+    x = a.x; y = a.y; z = b.x; w = b.y;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) clear_kernel(const LinkImage* __restrict__ im, const ClearArgs a) {
+    constexpr int U = (int)(4 * sizeof(T) / 16);   // 16-byte units per row
+    extern __shared__ ClearU4 clear_lds[];
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= a.B) return;
+    const int n = im->n, L = im->L, count = a.count;
+    const T* const qs = static_cast<const T*>(a.q) + (long)b * n;
+    bool bad = false;
+    for (int i = 0; i < n; ++i) {
+        const T v = qs[i];
+        bad = bad || v != v;
+    }
+    const ClearU4* const rows = static_cast<const ClearU4*>(a.pts4) + ((long)b * a.n_rep + a.first) * U;
+    for (int u = 0; u < count * U; ++u) clear_lds[u * 64 + threadIdx.x] = rows[u];
+    double best = __builtin_inf();
+    int code = -1;
+    LinkFrame X = {im->B[0][0], im->B[0][1], im->B[0][2], im->B[0][3], im->B[0][4], im->B[0][5],
+                   im->B[0][6], im->B[0][7], im->B[0][8], im->B[0][9], im->B[0][10], im->B[0][11]};
+    int j = 0;
+    for (int i = 0;; ++i) {
+        for (; j < L && im->link[j] == i; ++j) {
+            const unsigned m = a.mask[j];
+            if (m == 0u) continue;
+            const double cx = im->c[j][0], cy = im->c[j][1], cz = im->c[j][2], ri = im->c[j][3];
+            const double px = __builtin_fma(X.r02, cz, __builtin_fma(X.r01, cy, __builtin_fma(X.r00, cx, X.p0)));
+            const double py = __builtin_fma(X.r12, cz, __builtin_fma(X.r11, cy, __builtin_fma(X.r10, cx, X.p1)));
+            const double pz = __builtin_fma(X.r22, cz, __builtin_fma(X.r21, cy, __builtin_fma(X.r20, cx, X.p2)));
+            const int own = im->perm[j] * 32;
+            for (int r = 0; r < count; ++r) {
+                if (!((m >> r) & 1u)) continue;
+                double x, y, z, R;
+                clear_row(clear_lds + r * U * 64 + threadIdx.x, T(), x, y, z, R);
+                const double dx = px - x, dy = py - y, dz = pz - z;
+                const double d = (sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx))) - ri) - R;
+                const bool row_ok = x == x && y == y && z == z && R == R;   // a NaN row is "leave as it is": no obstacle
+                const int c = own + r;
+                const bool take = row_ok && (code < 0 || d < best || (d == best && c < code));
+                best = take ? d : best;
+                code = take ? c : code;
+            }
+        }
+        if (i >= n) break;
+        link_joint(X, im->jtype[i], bad ? 0.0 : (double)qs[i]);
+        const double* __restrict__ const Bn = im->B[i + 1];
+        link_fixed_row(X.r00, X.r01, X.r02, X.p0, Bn);
+        link_fixed_row(X.r10, X.r11, X.r12, X.p1, Bn);
+        link_fixed_row(X.r20, X.r21, X.r22, X.p2, Bn);
+    }
+    const T out = bad ? (T)__builtin_nan("") : (T)best;
+    if (bad) code = -1;
+    if (a.clear) static_cast<T*>(a.clear)[b] = out;
+    if (a.pair) a.pair[b] = code;
+    if (a.gate) {   // the wait rule: strict, on the io-typed value, so NaN and +inf never wait
+        const bool wait = a.gate[b] == 1 && (!a.yields || a.yields[b] != 0) && (double)out < a.min_clearance;
+        if (wait) a.gate[b] = 0;
+        if (a.waited) a.waited[b] = (a.first_block ? 0 : a.waited[b]) + (wait ? 1 : 0);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_clear(int io_dtype, const ClearArgs& a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.B + 63) / 64)), blk(64);   // one wave a block; the arm's rows: count x 16 bytes (float64: 32) a lane of LDS
+    if (io_dtype == 32) hipLaunchKernelGGL(clear_kernel<float>, grid, blk, (size_t)a.count * 1024, stream, a.img, a);
+    else hipLaunchKernelGGL(clear_kernel<double>, grid, blk, (size_t)a.count * 2048, stream, a.img, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_link(int io_dtype, const LinkArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.B + 255) / 256)), blk(256);

@@ -518,6 +518,29 @@ struct LinkArgs {
     int B, n_rep, first_rep;
 };
 hipError_t launch_link(int io_dtype, const LinkArgs& a, hipStream_t stream);
+// vfik_link_clearance and the wait rule of the timed moves (clear_kernel<T>, vfik_aux.hip): how much room is left between an arm's own link
+// spheres and `count` rows of pts4[b][n_rep][4] (x y z radius, from row `first`).  One lane per arm b walks the chain of `img` once from q[b],
+// as link_kernel does, and when the walk stands at a link compares every sphere of that link with the arm's rows:
+//     d = sqrt(|P - Q|^2) - r_own - R_row    in float64;    clear[b] = (T) min d;    pair[b] = own * 32 + row (own: the CALLER's index)
+// over the pairs whose bit `row` of mask[own's sorted position] is set and whose row holds no NaN; ties take the smallest code.  No pair:
+// +inf and -1; a NaN in q[b]: NaN and -1.  clear and pair may be NULL.
+// The wait rule (gate != NULL; vfik_set_wait_rule): an arm with gate[b] == 1 and yields[b] != 0 (yields NULL: every arm) whose (double)(T)
+// clearance is < min_clearance gets gate[b] = 0 and counts in waited[b] -- stored when `first_block`, else added.
+struct ClearArgs {
+    const LinkImage* img;
+    const void* q;              // [B][n]
+    const void* pts4;           // [B][n_rep][4], 16-byte aligned
+    void* clear;                // [B] io dtype or NULL
+    int* pair;                  // [B] or NULL
+    int B, n_rep, first, count;
+    uint32_t mask[VFIK_MAX_LINK_SPHERES];   // the image's sorted order (vfik_links.h: clear_mask)
+    int* gate;                  // [B] or NULL: no rule
+    const int* yields;          // [B] or NULL
+    int* waited;                // [B] or NULL
+    double min_clearance;
+    int first_block;
+};
+hipError_t launch_clear(int io_dtype, const ClearArgs& a, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

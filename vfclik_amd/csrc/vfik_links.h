@@ -2,7 +2,8 @@
 // the caller's list, and links_fill: vfik_chain + the spheres -> LinkImage, a small block in device memory that the kernel reads at
 // wave-uniform addresses (scalar loads).  Pure host code on the C++ standard library and include/vfik_types.h: no HIP symbol, so a
 // stand-alone program holds it on the CPU (tests/test_links_host.py).  The device code reads LinkImage through vfik_kernel.h, which includes
-// this header; vfik_abi.cpp uploads the image.
+// this header; vfik_abi.cpp uploads the image.  Behind them, likewise pure host code: the argument checks of vfik_link_clearance and the
+// pair mask in the image's order (clear_check, clear_mask; tests/test_clearance_host.py).
 //
 // Frames are those of the PUBLIC chain, X_link = B[0] Jz(q_1) B[1] ... Jz(q_link) B[link] (vfik_types.h).  The DH form of the cycle kernels
 // (vfik_kconst.h: dh_factor) moves z-screws between neighbouring links -- its intermediate frames are not the caller's -- so KConst is of
@@ -80,6 +81,53 @@ inline void links_fill(const vfik_chain& ch, const vfik_link_sphere* s, int L, L
             im->c[at][3] = s[j].radius;
             ++at;
         }
+}
+
+// ---- vfik_link_clearance / vfik_set_wait_rule: the checks of the caller's row window and pair mask, and the mask as clear_kernel reads it ----
+// A pair mask is one word per OWN sphere in the caller's order: bit j of mask[i] lets own sphere i meet row first + j.  The kernel visits
+// the own spheres in the image's sorted order, so the mask travels permuted: sorted[i] = mask[perm[i]].
+
+// 0, -1 (VFIK_E_ARG) or -4 (VFIK_E_STATE: no spheres set) with the reason in msg.  L own spheres; rows first .. first + count - 1 of n_rep;
+// q, pts4, clear as the caller gave them (only NULL and pts4's alignment are looked at); mask: L words or NULL (every pair).
+inline int clear_check(int L, const void* q, const void* pts4, const void* clear, int n_rep, int first, int count, const uint32_t* mask, char* msg,
+                       size_t len) {
+    if (!q || !pts4 || !clear) {
+        std::snprintf(msg, len, "q, pts4 and clear are required");
+        return -1;
+    }
+    if (reinterpret_cast<uintptr_t>(pts4) % 16) {
+        std::snprintf(msg, len, "pts4 must be 16-byte aligned: the kernel loads its rows in 16-byte pieces");
+        return -1;
+    }
+    if (count < 1 || count > 32) {
+        std::snprintf(msg, len, "count %d outside 1..32", count);
+        return -1;
+    }
+    if (first < 0 || n_rep < 0 || first > n_rep - count) {
+        std::snprintf(msg, len, "rows [%d, %d + %d) outside the %d rows of pts4", first, first, count, n_rep);
+        return -1;
+    }
+    if (L < 1) {
+        std::snprintf(msg, len, "no link spheres set: there is nothing to measure from");
+        return -4;
+    }
+    if (L > VFIK_MAX_LINK_SPHERES) {
+        std::snprintf(msg, len, "%d link spheres: 1..%d", L, VFIK_MAX_LINK_SPHERES);
+        return -1;
+    }
+    for (int i = 0; mask && i < L; ++i)
+        if (count < 32 && (mask[i] >> count) != 0) {
+            std::snprintf(msg, len, "mask[%d] = 0x%08x names a row at or beyond count %d", i, (unsigned)mask[i], count);
+            return -1;
+        }
+    return 0;
+}
+
+// The mask of a checked request in the image's order: sorted[i] = mask[perm[i]], every one of the `count` rows where mask is NULL; words
+// from L on are 0.
+inline void clear_mask(const LinkImage& im, const uint32_t* mask, int count, uint32_t sorted[VFIK_MAX_LINK_SPHERES]) {
+    const uint32_t all = count >= 32 ? 0xFFFFFFFFu : ((1u << count) - 1u);
+    for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i) sorted[i] = i < im.L ? (mask ? mask[im.perm[i]] : all) : 0u;
 }
 
 }  // namespace vfik

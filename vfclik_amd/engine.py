@@ -102,6 +102,11 @@ def load_library(path=None):
         "vfik_link_points_host": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
         "vfik_coupling_size": (C.c_size_t, []),
         "vfik_set_coupling": (C.c_int, [H, C.POINTER(_abi.Coupling)]),
+        "vfik_link_clearance": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "vfik_link_clearance_host": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "vfik_wait_rule_size": (C.c_size_t, []),
+        "vfik_set_wait_rule": (C.c_int, [H, C.POINTER(_abi.WaitRule)]),
+        "vfik_waited_host": (C.c_int, [H, C.c_void_p]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -156,7 +161,8 @@ def load_library(path=None):
                                ("vfik_script_opts", lib.vfik_script_opts_size(), _abi.ScriptOpts),
                                ("vfik_stall_rule", lib.vfik_stall_rule_size(), _abi.StallRule),
                                ("vfik_link_sphere", lib.vfik_link_sphere_size(), _abi.LinkSphere),
-                               ("vfik_coupling", lib.vfik_coupling_size(), _abi.Coupling)):
+                               ("vfik_coupling", lib.vfik_coupling_size(), _abi.Coupling),
+                               ("vfik_wait_rule", lib.vfik_wait_rule_size(), _abi.WaitRule)):
         if size != C.sizeof(mirror):
             raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
@@ -201,6 +207,7 @@ class Engine:
         self._stall_rule = None  # the stall rule of the timed moves (set_stall_rule), with the caller's stalled array kept alive
         self.n_links = 0  # link spheres held by the handle (set_link_spheres)
         self._coupling = None  # the coupling of the timed moves (set_coupling): the device arrays it reads and writes, kept alive
+        self._wait_rule = None  # the wait rule of the timed moves (set_wait_rule): likewise
         self._make_specs()
 
     # -- plumbing -------------------------------------------------------------------------------
@@ -382,7 +389,146 @@ class Engine:
                                                  None if xh is None else xh.ctypes.data, out.ctypes.data, out.shape[1], int(first_rep)))
         return out
 
+    # -- link-sphere clearance and arms that wait for room (vfik_link_clearance, vfik_set_wait_rule) --
+    def _mask_words(self, mask, count):
+        """A pair mask as the library reads it: uint32 (L,), bit j of word i lets own sphere i meet row j.  ``mask``: None (every pair),
+        L integers, or an (L, count) array of booleans."""
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        if m.ndim == 2:
+            if m.shape != (self.n_links, count):
+                raise ValueError("a mask matrix must be (%d, %d): own spheres by rows, got %s" % (self.n_links, count, m.shape))
+            m = (m.astype(bool).astype(np.uint64) << np.arange(count, dtype=np.uint64)[None, :]).sum(axis=1)
+        if m.shape != (self.n_links,):
+            raise ValueError("a mask has one word per own sphere (%d), got shape %s" % (self.n_links, m.shape))
+        if np.any(m.astype(np.int64) < 0) or np.any(m.astype(np.uint64) >> np.uint64(32)):
+            raise ValueError("mask words are 32 bits")
+        return np.ascontiguousarray(m, dtype=np.uint32)
+
+    def link_clearance(self, q, points, first=0, count=None, mask=None, out=None, pair=None):
+        """How much room is left between every arm's own link spheres and a set of other spheres, on the device (include/vfik.h:
+        vfik_link_clearance): asynchronous on the engine's stream.  ``q`` (batch, n) and ``points`` (batch, n_rep, 4) = x y z radius of the
+        engine's dtype -- what :meth:`link_points` writes: a neighbour's links, the arm's own, or static obstacles; a NaN row is no
+        obstacle.  Rows ``first .. first + count - 1`` are looked at (``count`` default: the rest, at most 32).  ``mask``: see
+        :meth:`_mask_words`.  Returns ``(out, pair)``: (batch,) of the engine's dtype, the smallest centre distance less both radii
+        (+inf: no pair; NaN: a NaN in q), and int32 (batch,), own sphere * 32 + row of the closest pair (-1: none).  Torch tensors on this
+        device; ``out`` / ``pair`` are made when not given."""
+        import torch
+        B, ft = self.batch, self.io_dtype.name
+        if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 4:
+            raise ValueError("points must be (%d, n_rep, 4), got %s" % (B, tuple(points.shape)))
+        n_rep = points.shape[1]
+        count = n_rep - int(first) if count is None else int(count)
+        dev = "cuda:%d" % self.device
+        if out is None:
+            out = torch.empty((B,), dtype=getattr(torch, ft), device=dev)
+        if pair is None:
+            pair = torch.empty((B,), dtype=torch.int32, device=dev)
+        self._check_dev((("q", q, (B, self.n), ft), ("points", points, None, ft), ("out", out, (B,), ft), ("pair", pair, (B,), "int32")))
+        mw = self._mask_words(mask, count)
+        self._chk(self.lib.vfik_link_clearance(self.h, C.c_void_p(_ptr(q)), C.c_void_p(_ptr(points)), n_rep, int(first), count,
+                                               None if mw is None else mw.ctypes.data, C.c_void_p(_ptr(out)), C.c_void_p(_ptr(pair))))
+        return out, pair
+
+    def link_clearance_host(self, q, points, first=0, count=None, mask=None):
+        """The host form (vfik_link_clearance_host; synchronous): NumPy arrays of doubles, rounded to the engine's dtype.  Returns
+        ``(clear, pair)``: float64 (batch,) holding the engine-typed values, and int32 (batch,)."""
+        B = self.batch
+        qh = np.ascontiguousarray(q, dtype=np.float64)
+        if qh.shape != (B, self.n):
+            raise ValueError("q must be (%d, %d), got %s" % (B, self.n, qh.shape))
+        ph = np.ascontiguousarray(points, dtype=np.float64)
+        if ph.ndim != 3 or ph.shape[0] != B or ph.shape[2] != 4:
+            raise ValueError("points must be (%d, n_rep, 4), got %s" % (B, ph.shape))
+        n_rep = ph.shape[1]
+        count = n_rep - int(first) if count is None else int(count)
+        mw = self._mask_words(mask, count)
+        clear, pair = np.empty(B, dtype=np.float64), np.empty(B, dtype=np.int32)
+        self._chk(self.lib.vfik_link_clearance_host(self.h, qh.ctypes.data, ph.ctypes.data, n_rep, int(first), count,
+                                                    None if mw is None else mw.ctypes.data, clear.ctypes.data, pair.ctypes.data))
+        return clear, pair
+
+    def _drop_wait_rule(self):
+        if self._wait_rule is not None:
+            if self._wait_rule["own"]:
+                self.lib.vfik_sync(self.h)   # an enqueued move may still read and write the arrays the engine uploaded
+            for p in self._wait_rule["own"]:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            self._wait_rule = None
+
+    def set_wait_rule(self, min_clearance, yields=None, mask=None, trace_checks=None, clear_traj=None, pair_traj=None, waited=None):
+        """Let arms wait for room inside every timed move from now on (include/vfik.h: vfik_set_wait_rule); needs a coupling
+        (:meth:`set_coupling`), and goes when the coupling goes.  In front of each block every arm's clearance against its partner's
+        link spheres is measured, and an arm that takes part, has ``yields[b] != 0`` (None: every arm) and less than ``min_clearance``
+        of room sits the block out; it runs again once the room is back.  One arm of a pair should yield and the other not: two arms
+        that both yield can wait for each other, and an arm that never gets room waits until the move's time-out.
+        ``yields``: int32 (batch,) -- a torch tensor on this device or a raw address, used as it is, or a NumPy array / sequence, uploaded
+        and kept alive.  ``mask``: own sphere i against partner sphere j (:meth:`_mask_words`), None: every pair.  ``clear_traj`` /
+        ``pair_traj``: device arrays (n_checks, batch) of the engine's dtype / int32 that receive every block's clearance and closest
+        pair; ``trace_checks=N`` instead: the engine keeps both for N checks itself (:meth:`clearance_traj`).  ``waited``: int32 (batch,)
+        device array for the count of blocks each arm waited, else the engine's own (:meth:`waited`).  ``min_clearance=None`` switches
+        the rule off, the default.  While a rule is set every ``*_host`` form returns a ``"waited"`` key."""
+        self._chk(self.lib.vfik_set_wait_rule(self.h, None))
+        self._drop_wait_rule()
+        if min_clearance is None:
+            return
+        if trace_checks is not None and (clear_traj is not None or pair_traj is not None):
+            raise ValueError("give clear_traj / pair_traj (device arrays of the caller's) or trace_checks (traces of the engine's), not both")
+        B, L, ft, own = self.batch, self.n_links, self.io_dtype, []
+        mw = self._mask_words(mask, L)
+        if mw is not None and not mw.any():
+            raise ValueError("a mask without a pair: the library reads all zeros as every pair")
+        try:
+            if yields is not None and not isinstance(yields, int) and not hasattr(yields, "data_ptr"):
+                ya = np.ascontiguousarray(yields, dtype=np.int32)
+                if ya.shape != (B,):
+                    raise ValueError("yields must be (%d,), got %s" % (B, ya.shape))
+                yields = self._upload(ya, own)
+            n_traj = None
+            if trace_checks is not None:
+                n_traj = int(trace_checks)
+                if n_traj < 1:
+                    raise ValueError("trace_checks must be at least 1, got %d" % n_traj)
+                clear_traj = self._upload(np.full((n_traj, B), np.nan, dtype=ft), own)
+                pair_traj = self._upload(np.full((n_traj, B), -1, dtype=np.int32), own)
+            self._check_dev((("yields", yields, (B,), "int32"), ("clear_traj", clear_traj, None, ft.name), ("pair_traj", pair_traj, None, "int32"),
+                             ("waited", waited, (B,), "int32")))
+            r = _abi.WaitRule()
+            r.min_clearance = float(min_clearance)
+            r.yields, r.clear_traj, r.pair_traj, r.waited = _ptr(yields), _ptr(clear_traj), _ptr(pair_traj), _ptr(waited)
+            for i in range(L if mw is not None else 0):
+                r.mask[i] = int(mw[i])
+            self._chk(self.lib.vfik_set_wait_rule(self.h, C.byref(r)))
+        except Exception:
+            for p in own:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            raise
+        self._wait_rule = {"own": own, "keep": (yields, clear_traj, pair_traj, waited), "n_traj": n_traj,
+                           "traj": (clear_traj, pair_traj) if n_traj else None}
+
+    def waited(self):
+        """int32 (batch,): how many blocks of the last timed move each arm waited for room (vfik_waited_host; synchronises).  Needs a
+        wait rule."""
+        out = np.empty(self.batch, dtype=np.int32)
+        self._chk(self.lib.vfik_waited_host(self.h, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def clearance_traj(self):
+        """The engine's own traces of a wait rule set with ``trace_checks=n_checks``: ``(clear_traj, pair_traj)``, (n_checks, batch) of
+        the engine's dtype and int32 -- row k what was measured in front of block k of the last timed move (NaN / -1: a block that
+        never ran).  Synchronises."""
+        if self._wait_rule is None or self._wait_rule["traj"] is None:
+            raise VfikError("no wait rule with traces of the engine's own: set_wait_rule(..., trace_checks=n_checks)")
+        n = self._wait_rule["n_traj"]
+        clear, pair = np.empty((n, self.batch), dtype=self.io_dtype), np.empty((n, self.batch), dtype=np.int32)
+        self.sync()
+        self.d2h(clear, self._wait_rule["traj"][0])
+        self.d2h(pair, self._wait_rule["traj"][1])
+        return clear, pair
+
     def _drop_coupling(self):
+        self._drop_wait_rule()   # (the library switched the rule off with the coupling)
         if self._coupling is not None:
             if self._coupling["own"]:
                 self.lib.vfik_sync(self.h)   # an enqueued move may still read the arrays the engine uploaded
@@ -768,6 +914,8 @@ class Engine:
         out["checks_run"] = int(ran.value)
         if self._stall_rule is not None:
             out["stalled"] = self.stalled()
+        if self._wait_rule is not None:
+            out["waited"] = self.waited()
         for k in ("pending",) + traces:
             out[k] = out[k][:out["checks_run"]]
         return out

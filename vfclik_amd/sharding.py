@@ -326,6 +326,32 @@ class ShardedEngine:
         import numpy as np
         return np.concatenate([e.link_traj() for e in self.engines], axis=1)
 
+    # -- clearance and the wait rule: per arm, so the one cross-shard case is the source arm that set_coupling refuses already ------------
+    def link_clearance_host(self, q, points, first=0, count=None, mask=None, global_rows=True):
+        """Engine.link_clearance_host over this rank's arms: ``q`` (rows, n) and ``points`` (rows, n_rep, 4) are sharded with the arms.
+        Returns this rank's ``(clear, pair)`` in arm order."""
+        import numpy as np
+        qs = self._rows(np.asarray(q), "q", global_rows)
+        ps = self._rows(np.asarray(points), "points", global_rows)
+        outs = [e.link_clearance_host(qs[i], ps[i], first=first, count=count, mask=mask) for i, e in enumerate(self.engines)]
+        if not outs:
+            return np.zeros(0), np.zeros(0, dtype=np.int32)
+        return np.concatenate([o[0] for o in outs], axis=0), np.concatenate([o[1] for o in outs], axis=0)
+
+    def set_wait_rule(self, min_clearance, yields=None, mask=None, trace_checks=None, global_rows=True):
+        """Engine.set_wait_rule on every engine of this rank (``min_clearance=None``: off); ``yields`` (rows,) is a host array sharded with
+        the arms.  Each engine keeps its own ``waited`` array and, with ``trace_checks``, its own traces.  While the rule is set the host
+        forms return ``waited`` in arm order beside their other per-arm rows."""
+        import numpy as np
+        ys = self._rows(None if yields is None else np.asarray(yields), "yields", global_rows)
+        for i, e in enumerate(self.engines):
+            e.set_wait_rule(min_clearance, yields=ys[i], mask=mask, trace_checks=trace_checks)
+
+    def waited(self):
+        """Engine.waited of this rank's arms, in arm order."""
+        import numpy as np
+        return np.concatenate([e.waited() for e in self.engines], axis=0)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
