@@ -691,6 +691,75 @@ size_t vfik_wait_rule_size(void);
 int vfik_set_wait_rule(vfik_handle* h, const vfik_wait_rule* r);   /* NULL: off (the default) */
 int vfik_waited_host(vfik_handle* h, int32_t* out /* host [B] */);
 
+/* Whole-arm avoidance: link spheres that push their own joints.  The wait rule can only stop an arm; here the elbow gives way while the
+ * hand keeps tracking its goal.  The reference's bridge keeps three command ports free for such extra joint commands, /bridge/mechanismcmd,
+ * /bridge/xtra1cmd and /bridge/xtra2cmd (scripts/bridge:568-570,593-596): mixer channels 3..5, which the cycle kernels read from the
+ * handle's ext buffer.  vfik_link_avoid computes such a command on the device.  For arm b, with the handle's link spheres
+ * (link_i, c_i, r_i), i < L, rows first .. first + count - 1 of pts4[b][n_rep][4] = (Q_j, R_j) widened exactly, and the pair mask and the
+ * NaN-row rule exactly as in vfik_link_clearance (bit j of mask[i]; a row that holds a NaN is no obstacle):
+ *     P_i   = X_link_i(q_b) c_i               the public chain's frames, as vfik_link_points / vfik_link_clearance
+ *     s_ij  = sqrt(|P_i - Q_j|^2)             from the coordinate differences, float64
+ *     d_ij  = s_ij - r_i - R_j
+ *     a_ij  = 1 - d_ij / d0                   the pair is ACTIVE iff a_ij > 0 (strict, so NaN never is) and s_ij > 0
+ *     F_i   = gain * scale[b] * sum_j a_ij (P_i - Q_j) / s_ij          over the active pairs
+ *     tau_k = sum over spheres with link_i > k of
+ *               revolute joint k :  z_k . ((P_i - o_k) x F_i)
+ *               prismatic joint k:  z_k . F_i
+ *             z_k, o_k = third and fourth column of X_k, the frame of link k (joint k turns about / shifts along it)
+ *     out[b][k] = (T) tau_k
+ * The law is continuous at d_ij = d0, where the term is 0, and grows linearly into penetration; the only discontinuity is s_ij == 0, where
+ * no direction exists: that pair contributes nothing.  A NaN anywhere in q[b] gives a row of ZEROS, not NaN (one NaN command would poison
+ * qdot_out through a zero mixer weight); an arm with no active pair gets a row of zeros; every arm b < B is written on every call, so a
+ * channel never keeps a stale push.
+ *   d0     finite and > 0;  gain finite.
+ *   scale  DEVICE [B] of the io dtype, or NULL for all ones: the per-arm priority tool, in the role yields has for the wait rule -- 0
+ *          means this arm does not give way.
+ *   out    DEVICE [B][n] of the io dtype, or NULL when a channel is named.
+ *   channel  -1, or 3..5: the command is ALSO written into that channel of the handle's ext buffer (layout [4][B][n]), which must
+ *          exist -- VFIK_E_STATE when neither vfik_set_ext_cmd nor vfik_set_avoid_rule has allocated it.  Channel 2 is the joint
+ *          controller's and is refused.  The mixer weight of the channel is the caller's (vfik_params.mix_w, vfik_set_mixer_weights).
+ * Asynchronous on the handle's stream, no allocation, ordered like vfik_link_clearance (the wait for outstanding vfik_submit_host tickets
+ * included); no launch decision and no epoch moves; valid under stream capture.  [link_points; move_fields; link_avoid(channel = 4); step]
+ * on one stream is the per-cycle form.
+ * KNOWN COST: a handle whose ext buffer exists runs no lean cycle kernel (an ext command is a per-arm option), as after any
+ * vfik_set_ext_cmd with a command.
+ * VFIK_E_ARG: the window and mask refusals of vfik_link_clearance, d0 / gain as above, a channel outside {-1, 3, 4, 5}, neither out nor
+ * a channel; VFIK_E_STATE: no spheres set, a channel without an ext buffer. */
+int vfik_link_avoid(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count,
+                    const uint32_t* mask /* host [L] or NULL */, double gain, double d0, const void* scale /* device [B] or NULL */,
+                    void* out /* device [B][n] or NULL */, int channel);
+/* The same with HOST arrays: q [B][n], pts4 [B][n_rep][4] and scale [B] (or NULL) doubles, rounded to the io dtype as
+ * vfik_link_clearance_host rounds them; out [B][n] doubles receives the io-typed values, widened.  Copies, launches and synchronises; no
+ * channel. */
+int vfik_link_avoid_host(vfik_handle* h, const double* q, const double* pts4, int n_rep, int first, int count, const uint32_t* mask,
+                         double gain, double d0, const double* scale, double* out);
+
+/* The avoid rule: that command in front of every block of the timed moves.  State of the HANDLE like the wait rule, off by default; with
+ * the rule off nothing changes -- the same launches, the same results.  It needs a coupling and goes when the coupling goes: a new sphere
+ * list, vfik_set_coupling(h, NULL), vfik_set_chain.
+ * While it is set, every block k of vfik_goto, vfik_follow, vfik_goto_js, vfik_follow_js and vfik_script enqueues avoid_kernel behind the
+ * coupling's two launches (and behind the wait rule's, when there is one), on the block's INPUT row of joint angles against rows
+ * first_rep .. first_rep + L - 1 of the coupling buffer; it writes the rule's channel and avoid_traj[k].  The command holds for the block's
+ * `stride` cycles, as the coupling's repellers do.  When the move ends the channel is zeroed by one asynchronous memset on the stream: a
+ * velocity push must not outlive the move, unlike a repeller's position.
+ * The mixer weight of the channel is the caller's: vfik_params.mix_w or vfik_set_mixer_weights.  In vfik_script the weights of channels 4
+ * and 5 come from the arm's own row (mix_frame / mix_posture carry 0..3), so channel 4 is the natural choice there.  A timed move under
+ * the rule needs VFIK_F_MIXER (VFIK_E_STATE without).
+ * vfik_set_avoid_rule is a setter like vfik_set_ext_cmd: it moves vfik_launch_epoch, may allocate the ext buffer (never under capture:
+ * VFIK_E_STATE), zeroes the channel and synchronises; the pointers are kept, not copied.  While the rule is set, vfik_set_ext_cmd on the
+ * rule's channel is refused (VFIK_E_STATE).  KNOWN COST as above: the ext buffer takes launches off the lean kernels.
+ * VFIK_E_ARG: d0 not finite or <= 0, gain not finite, channel outside 3..5, reserved != 0, a mask bit at or beyond L, scale / avoid_traj
+ * no device pointer aligned to the io type; VFIK_E_STATE: no coupling set. */
+typedef struct vfik_avoid_rule {
+    double gain, d0;
+    int32_t channel, reserved;   /* 3..5; 0 */
+    const void* scale;           /* device [B] io dtype or NULL (all ones) */
+    uint32_t mask[16];           /* own sphere i against partner sphere j; all zero = every pair */
+    void* avoid_traj;            /* device [n_checks][B][n] io dtype or NULL */
+} vfik_avoid_rule;
+size_t vfik_avoid_rule_size(void);
+int vfik_set_avoid_rule(vfik_handle* h, const vfik_avoid_rule* r);   /* NULL: off (the default) */
+
 /* Tracking-error estimator of scripts/vf (vf:349-428) for the batch: feed it, once per cycle, the tool
  * poses and field twists that vfik_step produced (device pointers pose[B][16], v6[B][6]); out[B][8] gets
  * vel_diff_angle, rot_diff_angle, ext_vel_mag_corr, ext_rot_mag_corr, cmd_vel_mag_corr, cmd_rot_mag_corr,

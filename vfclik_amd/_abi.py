@@ -120,6 +120,12 @@ class WaitRule(C.Structure):
                 ("pair_traj", C.c_void_p), ("waited", C.c_void_p), ("reserved", C.c_int32)]
 
 
+class AvoidRule(C.Structure):
+    """``struct vfik_avoid_rule`` (include/vfik.h: vfik_set_avoid_rule)."""
+    _fields_ = [("gain", C.c_double), ("d0", C.c_double), ("channel", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_void_p),
+                ("mask", C.c_uint32 * MAX_LINK_SPHERES), ("avoid_traj", C.c_void_p)]
+
+
 def default_params(**kw):
     """Defaults: speedScale 1.0 (vf:136), nullspace gain 0.5 / look-ahead 0.3 (nullspace:62,121),
     mixer weights [1,1,0,0,0,0] (bridge:596); lambda / rot_slowdown / jl_gain are build-defined."""

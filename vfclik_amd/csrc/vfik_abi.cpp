@@ -130,6 +130,10 @@ struct vfik_handle {
     vfik_wait_rule wait{};
     uint32_t wait_mask[VFIK_MAX_LINK_SPHERES] = {};
     int* d_wait_own = nullptr;
+    // vfik_set_avoid_rule: the push every block of a timed move under a coupling writes into one ext channel (avoid_on), its mask in the image's order
+    bool avoid_on = false;
+    vfik_avoid_rule avoid{};
+    uint32_t avoid_mask[VFIK_MAX_LINK_SPHERES] = {};
     double* d_wts = nullptr;    // per-arm IK weights [6 + n][Bpad], allocated by vfik_set_arm_weights
     // equal rows of a whole-batch vfik_set_arm_weights: the batch's IK weights from then on, kept apart from the caller's vfik_params (whose
     // wy / wq a later vfik_set_params compares against) until a vfik_set_params changes wy or wq
@@ -499,7 +503,7 @@ int vfik_set_chain(vfik_handle* h, const vfik_chain* c) {
     h->chain_set = true;
     const int rc = upload_kconst(h);
     if (rc != VFIK_OK) { h->chain = saved; h->chain_set = was_set; }
-    else { h->n_links = 0; h->couple_on = false; h->wait_on = false; }   // (the link spheres were those of the old chain's frames)
+    else { h->n_links = 0; h->couple_on = false; h->wait_on = false; h->avoid_on = false; }   // (the link spheres were those of the old chain's frames)
     return rc;
 }
 
@@ -803,6 +807,7 @@ int vfik_set_link_spheres(vfik_handle* h, const vfik_link_sphere* s, int L) {
     h->n_links = L;
     h->couple_on = false;   // (its buffer has the old list's rows)
     h->wait_on = false;     // (the rule reads that buffer)
+    h->avoid_on = false;    // (likewise)
     return VFIK_OK;
 }
 
@@ -870,7 +875,7 @@ size_t vfik_coupling_size(void) { return sizeof(vfik_coupling); }
 
 int vfik_set_coupling(vfik_handle* h, const vfik_coupling* c) {
     if (check_handle(h)) return VFIK_E_ARG;
-    if (!c) { h->couple_on = false; h->wait_on = false; return VFIK_OK; }
+    if (!c) { h->couple_on = false; h->wait_on = false; h->avoid_on = false; return VFIK_OK; }
     if (h->n_links < 1) return fail(VFIK_E_STATE, "vfik_set_coupling before vfik_set_link_spheres: there is nothing to couple");
     if (c->reserved != 0) return fail(VFIK_E_ARG, "coupling: reserved must be 0");
     if (c->first_rep < 0 || c->first_rep + h->n_links > h->max_slots)
@@ -1000,6 +1005,103 @@ int vfik_waited_host(vfik_handle* h, int32_t* out) {
     if (refuse_capture(h->stream, "vfik_waited_host copies to the host and synchronises: not while the stream is being captured")) return VFIK_E_STATE;
     HIP_TRY(hipMemcpyAsync(out, h->wait.waited ? h->wait.waited : h->d_wait_own, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return VFIK_OK;
+}
+
+// ---- whole-arm avoidance (avoid_kernel, vfik_aux.hip; the checks: vfik_links.h) ----
+static size_t ext_chan_bytes(const vfik_handle* h) { return (size_t)h->B * h->n * h->esz; }
+static void* ext_chan(const vfik_handle* h, int channel) { return static_cast<char*>(h->d_ext) + ext_chan_bytes(h) * (channel - 2); }
+
+// what the two forms of vfik_link_avoid share: the checks, then the mask in the image's order and the law into the kernel's arguments
+static int avoid_args(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count, const uint32_t* mask, double gain, double d0,
+                      const void* out, int channel, vfik::AvoidArgs& a) {
+    char msg[160];
+    const int rc = vfik::avoid_check(h->n_links, q, pts4, out, n_rep, first, count, mask, gain, d0, channel, h->d_ext != nullptr, msg, sizeof msg);
+    if (rc != 0) return fail(rc, "vfik_link_avoid: %s", msg);
+    a = vfik::AvoidArgs{};
+    a.img = static_cast<const vfik::LinkImage*>(h->d_link_img);
+    a.B = h->B; a.n_rep = n_rep; a.first = first; a.count = count;
+    a.gain = gain; a.d0 = d0;
+    vfik::clear_mask(h->link_img, mask, count, a.mask);
+    return VFIK_OK;
+}
+
+static int avoid_launch(vfik_handle* h, const vfik::AvoidArgs& a) {
+    const hipError_t e = vfik::launch_avoid(h->io_dtype, h->n, a, h->stream);
+    if (e != hipSuccess) return fail(VFIK_E_HIP, "avoid launch: %s", hipGetErrorString(e));
+    return VFIK_OK;
+}
+
+int vfik_link_avoid(vfik_handle* h, const void* q, const void* pts4, int n_rep, int first, int count, const uint32_t* mask, double gain, double d0,
+                    const void* scale, void* out, int channel) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    vfik::AvoidArgs a;
+    const int rc = avoid_args(h, q, pts4, n_rep, first, count, mask, gain, d0, out, channel, a);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    a.q = q; a.pts4 = pts4; a.scale = scale; a.out = out;
+    if (channel >= 0) a.chan_out = ext_chan(h, channel);
+    return avoid_launch(h, a);
+}
+
+int vfik_link_avoid_host(vfik_handle* h, const double* q, const double* pts4, int n_rep, int first, int count, const uint32_t* mask, double gain,
+                         double d0, const double* scale, double* out) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (drain_side_streams(h) != VFIK_OK) return VFIK_E_HIP;
+    vfik::AvoidArgs a;
+    alignas(16) static const char aligned_stand_in = 0;   // (the caller's pts4 is copied: its alignment is not the kernel's concern)
+    const int rc = avoid_args(h, q, pts4 ? &aligned_stand_in : nullptr, n_rep, first, count, mask, gain, d0, out, -1, a);
+    if (rc != VFIK_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_link_avoid_host copies and synchronises: not while the stream is being captured")) return VFIK_E_STATE;
+    // one stage: q | the rows (16-byte aligned) | scale | out
+    const size_t B = (size_t)h->B, nq = B * h->n, np = B * (size_t)n_rep * 4;
+    const size_t pts_off = (nq * h->esz + 15) / 16 * 16, scale_off = pts_off + np * h->esz, out_off = (scale_off + B * h->esz + 15) / 16 * 16;
+    std::vector<char> buf(out_off + nq * h->esz);
+    for (size_t k = 0; k < nq; ++k) put_io(h, buf, k, q[k]);
+    for (size_t k = 0; k < np; ++k) put_io(h, buf, pts_off / h->esz + k, pts4[k]);
+    for (size_t k = 0; scale && k < B; ++k) put_io(h, buf, scale_off / h->esz + k, scale[k]);
+    if (reserve(h, h->link_stage, buf.size(), true, true) != VFIK_OK) return VFIK_E_HIP;
+    char* const d = static_cast<char*>(h->link_stage.p);
+    HIP_TRY(hipMemcpyAsync(d, buf.data(), out_off, hipMemcpyHostToDevice, h->stream));
+    a.q = d; a.pts4 = d + pts_off; a.scale = scale ? d + scale_off : nullptr; a.out = d + out_off;
+    const int rl = avoid_launch(h, a);
+    if (rl != VFIK_OK) return rl;
+    HIP_TRY(hipMemcpyAsync(buf.data() + out_off, d + out_off, nq * h->esz, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < nq; ++k) {
+        const char* src = buf.data() + out_off + k * h->esz;
+        if (h->io_dtype == 32) { float f; std::memcpy(&f, src, sizeof f); out[k] = f; } else std::memcpy(&out[k], src, sizeof(double));
+    }
+    return VFIK_OK;
+}
+
+// ---- the avoid rule: the push every block of a timed move under a coupling writes into one ext channel (avoid_block) ----
+size_t vfik_avoid_rule_size(void) { return sizeof(vfik_avoid_rule); }
+
+int vfik_set_avoid_rule(vfik_handle* h, const vfik_avoid_rule* r) {
+    if (check_handle(h)) return VFIK_E_ARG;
+    if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
+    if (!r) { h->avoid_on = false; return VFIK_OK; }
+    if (!h->couple_on) return fail(VFIK_E_STATE, "vfik_set_avoid_rule before vfik_set_coupling: the rule pushes away from the coupling's rows");
+    char msg[160];
+    const int L = h->n_links;
+    if (vfik::avoid_rule_check(L, r->gain, r->d0, r->channel, r->reserved, r->mask, msg, sizeof msg) != 0) return fail(VFIK_E_ARG, "avoid rule: %s", msg);
+    if (r->scale && (!gpu_visible(r->scale) || reinterpret_cast<uintptr_t>(r->scale) % h->esz))
+        return fail(VFIK_E_ARG, "avoid rule: scale must be a DEVICE pointer aligned to the I/O type");
+    if (r->avoid_traj && (!gpu_visible(r->avoid_traj) || reinterpret_cast<uintptr_t>(r->avoid_traj) % h->esz))
+        return fail(VFIK_E_ARG, "avoid rule: avoid_traj must be a DEVICE pointer aligned to the I/O type");
+    HIP_TRY(hipSetDevice(h->device));
+    if (refuse_capture(h->stream, "vfik_set_avoid_rule may allocate the handle's ext buffer and zeroes its channel: call it before capturing the stream")) return VFIK_E_STATE;
+    if (!h->d_ext && dev_alloc(h, &h->d_ext, ext_chan_bytes(h) * (VFIK_MIX_CHANNELS - 2), true)) return VFIK_E_HIP;
+    HIP_TRY(hipMemsetAsync(ext_chan(h, r->channel), 0, ext_chan_bytes(h), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    bool any = false;
+    for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i) any = any || r->mask[i] != 0;
+    h->avoid = *r;
+    vfik::clear_mask(h->link_img, any ? r->mask : nullptr, L, h->avoid_mask);
+    h->avoid_on = true;
     return VFIK_OK;
 }
 
@@ -1173,6 +1275,8 @@ int vfik_set_ext_cmd(vfik_handle* h, int channel, const void* cmd_host) {
     if (check_handle(h)) return VFIK_E_ARG;
     if (quiesce(h) != VFIK_OK) return VFIK_E_HIP;
     if (channel < 2 || channel >= VFIK_MIX_CHANNELS) return fail(VFIK_E_ARG, "channel %d: only 2..%d are external", channel, VFIK_MIX_CHANNELS - 1);
+    if (h->avoid_on && channel == h->avoid.channel)
+        return fail(VFIK_E_STATE, "vfik_set_ext_cmd: channel %d is written by the handle's avoid rule (vfik_set_avoid_rule)", channel);
     HIP_TRY(hipSetDevice(h->device));
     const size_t chan = (size_t)h->B * h->n * h->esz;
     if (!h->d_ext) {
@@ -1464,6 +1568,8 @@ int timed_check(vfik_handle* h, TimedMove& m) {
     if (!io->q_lo != !io->q_hi) return fail(VFIK_E_ARG, "io->q_lo and io->q_hi come together (both or neither)");
     if (!h->chain_set) return fail(VFIK_E_STATE, "vfik_set_chain has not been called");
     if (h->couple_on && !h->fields_set) return fail(VFIK_E_STATE, "a timed move under a coupling before any vfik_set_fields: there are no repellers to move");
+    if (h->avoid_on && !(h->params.flags & VFIK_F_MIXER))
+        return fail(VFIK_E_STATE, "a timed move under an avoid rule: the push enters through mixer channel %d, and the handle's params lack VFIK_F_MIXER", (int)h->avoid.channel);
     m.n_checks = m.n_cycles / m.stride;
     m.gated = m.hold || io->active || m.list || (h->stall_on && h->stall.stop) || h->wait_on;   // (a stalled arm that stops, and one that waits, are gated like a held one)
     return VFIK_OK;
@@ -1684,6 +1790,21 @@ int wait_block(vfik_handle* h, int k, const void* q_prev) {
     return clear_launch(h, a);
 }
 
+// The handle's avoid rule (vfik_set_avoid_rule) behind the coupling's launches and the wait rule's: every arm's push at the block's input row
+// away from the partner's rows as just placed, into the rule's ext channel -- where the block's cycles read it -- and row k of its trace.
+int avoid_block(vfik_handle* h, int k, const void* q_prev) {
+    const int L = h->n_links;
+    vfik::AvoidArgs a{};
+    a.img = static_cast<const vfik::LinkImage*>(h->d_link_img);
+    a.q = q_prev; a.pts4 = h->couple_rep.p; a.scale = h->avoid.scale;
+    a.B = h->B; a.n_rep = h->couple.first_rep + L; a.first = h->couple.first_rep; a.count = L;
+    a.gain = h->avoid.gain; a.d0 = h->avoid.d0;
+    std::memcpy(a.mask, h->avoid_mask, sizeof a.mask);
+    a.chan_out = ext_chan(h, h->avoid.channel);
+    if (h->avoid.avoid_traj) a.traj = static_cast<char*>(h->avoid.avoid_traj) + (size_t)k * ext_chan_bytes(h);
+    return avoid_launch(h, a);
+}
+
 // block k -- `stride` cycles through launch_cycles, as vfik_rollout runs them -- and its check
 int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     const vfik::BlockRows w = vfik::block_rows(m, timed_dims(h, m), k, h->d_gotoq, h->d_goto_dist);
@@ -1695,6 +1816,7 @@ int timed_block(vfik_handle* h, const TimedMove& m, int k) {
     if (h->couple_on) {
         int rl = couple_block(h, k, w.q_prev);
         if (rl == VFIK_OK && h->wait_on) rl = wait_block(h, k, w.q_prev);
+        if (rl == VFIK_OK && h->avoid_on) rl = avoid_block(h, k, w.q_prev);
         if (rl != VFIK_OK) return rl;
     }
     const int rc = launch_cycles(h, &b, m.stride, m.dt, m.clamp, w.q_now, h->stream, k > 0, m.script ? h->d_script_mixw : nullptr);
@@ -1704,6 +1826,8 @@ int timed_block(vfik_handle* h, const TimedMove& m, int k) {
 // q_out: the row the last executed block wrote; io->goal_dist beside a trace: the trace's last row
 int timed_end(vfik_handle* h, const TimedMove& m, int checks_run) {
     if (checks_run < 1) return VFIK_OK;
+    // (a velocity push must not outlive the move: the avoid rule's channel back to zero, behind the last block on the stream)
+    if (h->avoid_on && h->couple_on) HIP_TRY(hipMemsetAsync(ext_chan(h, h->avoid.channel), 0, ext_chan_bytes(h), h->stream));
     const vfik::TimedDims d = timed_dims(h, m);
     const vfik::BlockRows w = vfik::block_rows(m, d, checks_run - 1, h->d_gotoq, h->d_goto_dist);
     if (m.x[vfik::X_Q_OUT]) HIP_TRY(hipMemcpyAsync(m.x[vfik::X_Q_OUT], w.q_now, vfik::extra_bytes(vfik::X_Q_OUT, d, 1), hipMemcpyDeviceToDevice, h->stream));

@@ -654,7 +654,137 @@ __global__ void __launch_bounds__(64) clear_kernel(const LinkImage* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// vfik_link_avoid: link spheres that push their own joints (AvoidArgs, vfik_kernel.h).  clear_kernel's walk once more -- one lane per arm, one
+// wave a block, link_joint, link_fixed_row, twelve named doubles, the image at uniform addresses, the mask by value in the image's order --
+// and at every own sphere P_i a repulsive velocity from the rows it is close to,
+//     F_i = g_b sum_j a_ij (P_i - Q_j) / s_ij,   a_ij = 1 - (s_ij - r_i - R_j) / d0 > 0,  s_ij > 0      (strict: a NaN row, a NaN radius never push)
+// which the Jacobian transpose of that point turns into a joint command: tau_k = sum over the spheres beyond joint k of z_k . ((P_i - o_k) x F_i),
+// prismatic z_k . F_i.  ONE forward walk: with  z . ((P - o) x F) = z . (P x F) - (z x o) . F,  T_F = sum F_i, T_N = sum P_i x F_i and the same
+// sums over the spheres up to link k,
+//     revolute  tau_k = (z_k . T_N - m_k . T_F) - c_k,  c_k = z_k . Pre_N(k) - m_k . Pre_F(k),  m_k = z_k x o_k;    prismatic  tau_k = z_k . T_F - z_k . Pre_F(k)
+// When the walk stands at link k it has emitted exactly the spheres of links <= k, so the running totals ARE the prefix sums: it keeps z_k,
+// m_k, c_k -- seven doubles a joint -- and a loop over the joints finishes once the totals are known.  Those doubles go to LDS, double s of
+// lane t at [s * 64 + t]: a wave's ds_write_b64 / ds_read_b64 covers 512 consecutive bytes, no bank conflict, a lane reads only what it
+// wrote, no barrier.  No register array indexed at run time, no scratch.  n x 3.5 KiB; behind them the arm's rows, staged as clear_kernel
+// stages them where both fit into 64 KiB, else (a.stage == 0, uniform) read through the cache at every sphere (launch_avoid).
+// A NaN in q[b]: a row of zeros (one NaN command would poison qdot_out through a zero mixer weight); no active pair: zeros, +0 each.  Every
+// arm b < B is written on every call, each destination once.
+// Resources (tools/resusage.py): 104 VGPRs and 73 SGPRs in either I/O type, no scratch, no static LDS; dynamic LDS as launch_avoid says.
+// ------------------------------------------------------------------------------------------------
+// a row at its place in memory, its 16-byte units side by side, widened exactly
+__device__ __forceinline__ void avoid_row_mem(const ClearU4* p, float, double& x, double& y, double& z, double& w) {
+    clear_row(p, 0.0f, x, y, z, w);
+}
+__device__ __forceinline__ void avoid_row_mem(const ClearU4* p, double, double& x, double& y, double& z, double& w) {
+    const ClearD2 a = (ClearD2)p[0], b = (ClearD2)p[1];
+    x = a.x; y = a.y; z = b.x; w = b.y;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) avoid_kernel(const LinkImage* __restrict__ im, const AvoidArgs a) {
+    constexpr int U = (int)(4 * sizeof(T) / 16);   // 16-byte units per row
+    extern __shared__ ClearU4 avoid_lds[];
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= a.B) return;
+    const int n = im->n, L = im->L, count = a.count;
+    double* const jl = reinterpret_cast<double*>(avoid_lds) + threadIdx.x;   // the joints' doubles: 7 n slots of 64
+    ClearU4* const rl = avoid_lds + n * (7 * 64 * 8 / 16) + threadIdx.x;     // the staged rows behind them
+    const T* const qs = static_cast<const T*>(a.q) + (long)b * n;
+    bool bad = false;
+    for (int i = 0; i < n; ++i) {
+        const T v = qs[i];
+        bad = bad || v != v;
+    }
+    const ClearU4* const rows = static_cast<const ClearU4*>(a.pts4) + ((long)b * a.n_rep + a.first) * U;
+    const bool stage = a.stage != 0;
+    if (stage)
+        for (int u = 0; u < count * U; ++u) rl[u * 64] = rows[u];
+    const double g = a.gain * (a.scale ? (double)static_cast<const T*>(a.scale)[b] : 1.0), d0 = a.d0;
+    double tfx = 0, tfy = 0, tfz = 0, tnx = 0, tny = 0, tnz = 0;
+    bool any = false;
+    LinkFrame X = {im->B[0][0], im->B[0][1], im->B[0][2], im->B[0][3], im->B[0][4], im->B[0][5],
+                   im->B[0][6], im->B[0][7], im->B[0][8], im->B[0][9], im->B[0][10], im->B[0][11]};
+    int j = 0;
+    for (int i = 0;; ++i) {
+        for (; j < L && im->link[j] == i; ++j) {
+            const unsigned m = a.mask[j];
+            if (m == 0u) continue;
+            const double cx = im->c[j][0], cy = im->c[j][1], cz = im->c[j][2], ri = im->c[j][3];
+            const double px = __builtin_fma(X.r02, cz, __builtin_fma(X.r01, cy, __builtin_fma(X.r00, cx, X.p0)));
+            const double py = __builtin_fma(X.r12, cz, __builtin_fma(X.r11, cy, __builtin_fma(X.r10, cx, X.p1)));
+            const double pz = __builtin_fma(X.r22, cz, __builtin_fma(X.r21, cy, __builtin_fma(X.r20, cx, X.p2)));
+            double fx = 0, fy = 0, fz = 0;
+            for (int r = 0; r < count; ++r) {
+                if (!((m >> r) & 1u)) continue;
+                double x, y, z, R;
+                if (stage) clear_row(rl + r * U * 64, T(), x, y, z, R);
+                else avoid_row_mem(rows + r * U, T(), x, y, z, R);
+                const double dx = px - x, dy = py - y, dz = pz - z;
+                const double s = sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+                const double act = 1.0 - ((s - ri) - R) / d0;
+                const bool on = act > 0.0 && s > 0.0;   // (a NaN anywhere in the row makes act NaN: no obstacle)
+                const double w = on ? act / s : 0.0;
+                fx = __builtin_fma(w, on ? dx : 0.0, fx);
+                fy = __builtin_fma(w, on ? dy : 0.0, fy);
+                fz = __builtin_fma(w, on ? dz : 0.0, fz);
+                any = any || on;
+            }
+            fx *= g; fy *= g; fz *= g;
+            tfx += fx; tfy += fy; tfz += fz;
+            tnx += py * fz - pz * fy;
+            tny += pz * fx - px * fz;
+            tnz += px * fy - py * fx;
+        }
+        if (i >= n) break;
+        {   // joint i turns about / shifts along z of X_i through its origin; the totals so far are the sums over the links <= i
+            const double zx = X.r02, zy = X.r12, zz = X.r22;
+            const double mx = zy * X.p2 - zz * X.p1, my = zz * X.p0 - zx * X.p2, mz = zx * X.p1 - zy * X.p0;
+            const double zf = __builtin_fma(zz, tfz, __builtin_fma(zy, tfy, zx * tfx));
+            const double zn = __builtin_fma(zz, tnz, __builtin_fma(zy, tny, zx * tnx));
+            const double mf = __builtin_fma(mz, tfz, __builtin_fma(my, tfy, mx * tfx));
+            double* const s = jl + i * (7 * 64);
+            s[0] = zx; s[64] = zy; s[128] = zz; s[192] = mx; s[256] = my; s[320] = mz;
+            s[384] = im->jtype[i] == 0 ? zn - mf : zf;
+        }
+        link_joint(X, im->jtype[i], bad ? 0.0 : (double)qs[i]);
+        const double* __restrict__ const Bn = im->B[i + 1];
+        link_fixed_row(X.r00, X.r01, X.r02, X.p0, Bn);
+        link_fixed_row(X.r10, X.r11, X.r12, X.p1, Bn);
+        link_fixed_row(X.r20, X.r21, X.r22, X.p2, Bn);
+    }
+    const bool zero = bad || !any;
+    T* const out = a.out ? static_cast<T*>(a.out) + (long)b * n : nullptr;
+    T* const chan = a.chan_out ? static_cast<T*>(a.chan_out) + (long)b * n : nullptr;
+    T* const trj = a.traj ? static_cast<T*>(a.traj) + (long)b * n : nullptr;
+    for (int k = 0; k < n; ++k) {
+        const double* const s = jl + k * (7 * 64);
+        const double zx = s[0], zy = s[64], zz = s[128], mx = s[192], my = s[256], mz = s[320], c = s[384];
+        const double zf = __builtin_fma(zz, tfz, __builtin_fma(zy, tfy, zx * tfx));
+        const double zn = __builtin_fma(zz, tnz, __builtin_fma(zy, tny, zx * tnx));
+        const double mf = __builtin_fma(mz, tfz, __builtin_fma(my, tfy, mx * tfx));
+        const double tau = (im->jtype[k] == 0 ? zn - mf : zf) - c;
+        const T v = zero ? (T)0 : (T)tau;
+        if (out) out[k] = v;
+        if (chan) chan[k] = v;
+        if (trj) trj[k] = v;
+    }
+}
+
 }  // namespace
+
+// Dynamic LDS of avoid_kernel: the joints' doubles, n x 7 x 64 x 8 bytes = n x 3.5 KiB (56 KiB at 16 joints), and behind them the arm's rows as
+// clear_kernel stages them, count KiB at float32, twice that at float64 -- WHERE BOTH FIT INTO 64 KiB.  Where they do not (16 joints and more
+// than 8 rows of float32 or 4 of float64, say) the rows stay where they are and every own sphere reads them through the cache: a.stage = 0.
+hipError_t launch_avoid(int io_dtype, int n, AvoidArgs a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.B + 63) / 64)), blk(64);
+    const size_t joints = (size_t)n * 7 * 64 * 8, rows = (size_t)a.count * (io_dtype == 32 ? 1024 : 2048);
+    a.stage = joints + rows <= 65536 ? 1 : 0;
+    const size_t lds = joints + (a.stage ? rows : 0);
+    if (io_dtype == 32) hipLaunchKernelGGL(avoid_kernel<float>, grid, blk, lds, stream, a.img, a);
+    else hipLaunchKernelGGL(avoid_kernel<double>, grid, blk, lds, stream, a.img, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_clear(int io_dtype, const ClearArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.B + 63) / 64)), blk(64);   // one wave a block; the arm's rows: count x 16 bytes (float64: 32) a lane of LDS

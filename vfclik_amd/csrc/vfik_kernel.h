@@ -541,6 +541,26 @@ struct ClearArgs {
     int first_block;
 };
 hipError_t launch_clear(int io_dtype, const ClearArgs& a, hipStream_t stream);
+// vfik_link_avoid and the avoid rule of the timed moves (avoid_kernel<T>, vfik_aux.hip): every own link sphere is pushed away from the rows
+// it is close to, and the push goes through the Jacobian transpose of the sphere's point into a joint command.  The walk, the rows, the mask
+// and the NaN-row rule are ClearArgs'; with s = sqrt(|P - Q|^2) in float64:
+//     a = 1 - (s - r_own - R_row) / d0,  active iff a > 0 and s > 0;    F_own = gain * scale[b] * sum a (P - Q) / s
+//     tau_k = sum over own spheres on links > k of  z_k . ((P - o_k) x F)  (revolute)  or  z_k . F  (prismatic);    row[b][k] = (T) tau_k
+// A NaN in q[b] or no active pair: a row of zeros.  The row of every arm b < B goes to each of out, chan_out and traj that is given.
+struct AvoidArgs {
+    const LinkImage* img;
+    const void* q;              // [B][n]
+    const void* pts4;           // [B][n_rep][4], 16-byte aligned
+    const void* scale;          // [B] io dtype or NULL (all ones)
+    void* out;                  // [B][n] io dtype or NULL
+    void* chan_out;             // [B][n]: the handle's rows of one ext channel, or NULL
+    void* traj;                 // [B][n]: a trace row, or NULL
+    int B, n_rep, first, count;
+    uint32_t mask[VFIK_MAX_LINK_SPHERES];   // the image's sorted order (vfik_links.h: clear_mask)
+    double gain, d0;
+    int stage;                  // set by launch_avoid: the rows are staged in LDS behind the joints' doubles
+};
+hipError_t launch_avoid(int io_dtype, int n, AvoidArgs a, hipStream_t stream);
 hipError_t launch_monitor(int io_dtype, const void* pose, const void* frames, int O, long count, void* out, hipStream_t stream, const int* active = nullptr);
 hipError_t launch_track(int io_dtype, const void* pose, const void* v6, double* state, void* out, const int* active, int B, hipStream_t stream);
 hipError_t launch_mix(int io_dtype, const void* cmds, const double* w_dev, int K, long count, long chan_stride,

@@ -3,7 +3,8 @@
 // wave-uniform addresses (scalar loads).  Pure host code on the C++ standard library and include/vfik_types.h: no HIP symbol, so a
 // stand-alone program holds it on the CPU (tests/test_links_host.py).  The device code reads LinkImage through vfik_kernel.h, which includes
 // this header; vfik_abi.cpp uploads the image.  Behind them, likewise pure host code: the argument checks of vfik_link_clearance and the
-// pair mask in the image's order (clear_check, clear_mask; tests/test_clearance_host.py).
+// pair mask in the image's order (clear_check, clear_mask; tests/test_clearance_host.py), and the checks of vfik_link_avoid and
+// vfik_set_avoid_rule (avoid_check, avoid_rule_check; tests/test_avoid_host.py).
 //
 // Frames are those of the PUBLIC chain, X_link = B[0] Jz(q_1) B[1] ... Jz(q_link) B[link] (vfik_types.h).  The DH form of the cycle kernels
 // (vfik_kconst.h: dh_factor) moves z-screws between neighbouring links -- its intermediate frames are not the caller's -- so KConst is of
@@ -128,6 +129,69 @@ inline int clear_check(int L, const void* q, const void* pts4, const void* clear
 inline void clear_mask(const LinkImage& im, const uint32_t* mask, int count, uint32_t sorted[VFIK_MAX_LINK_SPHERES]) {
     const uint32_t all = count >= 32 ? 0xFFFFFFFFu : ((1u << count) - 1u);
     for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i) sorted[i] = i < im.L ? (mask ? mask[im.perm[i]] : all) : 0u;
+}
+
+// ---- vfik_link_avoid / vfik_set_avoid_rule: the checks of a push (avoid_kernel) ----
+// The law's own parameters, shared by the call and the rule.  0 or -1 with the reason in msg.
+inline int avoid_law_check(double gain, double d0, char* msg, size_t len) {
+    if (!std::isfinite(d0) || !(d0 > 0.0)) {
+        std::snprintf(msg, len, "d0 = %g: the influence distance must be finite and greater than 0", d0);
+        return -1;
+    }
+    if (!std::isfinite(gain)) {
+        std::snprintf(msg, len, "gain = %g must be finite", gain);
+        return -1;
+    }
+    return 0;
+}
+
+// A mixer channel that a push may write: 3..5 (2 is the joint controller's).  `none_ok`: -1, no channel, passes.
+inline int avoid_channel_check(int channel, bool none_ok, char* msg, size_t len) {
+    if (none_ok && channel == -1) return 0;
+    if (channel == 2) {
+        std::snprintf(msg, len, "channel 2 is the joint controller's: 3..%d take a push", VFIK_MIX_CHANNELS - 1);
+        return -1;
+    }
+    if (channel < 3 || channel >= VFIK_MIX_CHANNELS) {
+        std::snprintf(msg, len, none_ok ? "channel %d: -1 (none) or 3..%d" : "channel %d outside 3..%d", channel, VFIK_MIX_CHANNELS - 1);
+        return -1;
+    }
+    return 0;
+}
+
+// vfik_link_avoid: 0, -1 (VFIK_E_ARG) or -4 (VFIK_E_STATE: no spheres set; a channel and no ext buffer) with the reason in msg.  The row window
+// and the mask are clear_check's (its `clear` stands for "some destination": out, or a channel); then the law and the channel.
+inline int avoid_check(int L, const void* q, const void* pts4, const void* out, int n_rep, int first, int count, const uint32_t* mask, double gain,
+                       double d0, int channel, bool have_ext, char* msg, size_t len) {
+    if (avoid_channel_check(channel, true, msg, len) != 0) return -1;
+    if (!out && channel < 0) {
+        std::snprintf(msg, len, "out is required where no channel takes the command");
+        return -1;
+    }
+    const int rc = clear_check(L, q, pts4, q /* a destination exists */, n_rep, first, count, mask, msg, len);
+    if (rc != 0) return rc;
+    if (avoid_law_check(gain, d0, msg, len) != 0) return -1;
+    if (channel >= 0 && !have_ext) {
+        std::snprintf(msg, len, "channel %d: the handle has no ext buffer yet (vfik_set_ext_cmd or vfik_set_avoid_rule allocates it)", channel);
+        return -4;
+    }
+    return 0;
+}
+
+// vfik_set_avoid_rule: the rule's numbers (the pointers are the library's to look at).  L own spheres against the partner's L.
+inline int avoid_rule_check(int L, double gain, double d0, int channel, int reserved, const uint32_t mask[VFIK_MAX_LINK_SPHERES], char* msg, size_t len) {
+    if (avoid_law_check(gain, d0, msg, len) != 0) return -1;
+    if (avoid_channel_check(channel, false, msg, len) != 0) return -1;
+    if (reserved != 0) {
+        std::snprintf(msg, len, "reserved must be 0");
+        return -1;
+    }
+    for (int i = 0; i < VFIK_MAX_LINK_SPHERES; ++i)
+        if ((i >= L && mask[i] != 0) || (L < 32 && (mask[i] >> L) != 0)) {
+            std::snprintf(msg, len, "mask[%d] = 0x%08x names a sphere at or beyond the %d of the handle", i, (unsigned)mask[i], L);
+            return -1;
+        }
+    return 0;
 }
 
 }  // namespace vfik

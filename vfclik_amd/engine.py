@@ -107,6 +107,12 @@ def load_library(path=None):
         "vfik_wait_rule_size": (C.c_size_t, []),
         "vfik_set_wait_rule": (C.c_int, [H, C.POINTER(_abi.WaitRule)]),
         "vfik_waited_host": (C.c_int, [H, C.c_void_p]),
+        "vfik_link_avoid": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                      C.c_void_p, C.c_int]),
+        "vfik_link_avoid_host": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                           C.c_void_p]),
+        "vfik_avoid_rule_size": (C.c_size_t, []),
+        "vfik_set_avoid_rule": (C.c_int, [H, C.POINTER(_abi.AvoidRule)]),
         "vfik_mix": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "vfik_track_error": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "vfik_track_reset": (C.c_int, [H]),
@@ -162,7 +168,8 @@ def load_library(path=None):
                                ("vfik_stall_rule", lib.vfik_stall_rule_size(), _abi.StallRule),
                                ("vfik_link_sphere", lib.vfik_link_sphere_size(), _abi.LinkSphere),
                                ("vfik_coupling", lib.vfik_coupling_size(), _abi.Coupling),
-                               ("vfik_wait_rule", lib.vfik_wait_rule_size(), _abi.WaitRule)):
+                               ("vfik_wait_rule", lib.vfik_wait_rule_size(), _abi.WaitRule),
+                               ("vfik_avoid_rule", lib.vfik_avoid_rule_size(), _abi.AvoidRule)):
         if size != C.sizeof(mirror):
             raise VfikError("struct layout mismatch: %s is %d bytes in the library, %d in the Python mirror" % (name, size, C.sizeof(mirror)))
     if path == _abi.HIP_LIB_PATH or _lib is None:
@@ -208,6 +215,7 @@ class Engine:
         self.n_links = 0  # link spheres held by the handle (set_link_spheres)
         self._coupling = None  # the coupling of the timed moves (set_coupling): the device arrays it reads and writes, kept alive
         self._wait_rule = None  # the wait rule of the timed moves (set_wait_rule): likewise
+        self._avoid_rule = None  # the avoid rule of the timed moves (set_avoid_rule): likewise
         self._make_specs()
 
     # -- plumbing -------------------------------------------------------------------------------
@@ -527,8 +535,123 @@ class Engine:
         self.d2h(pair, self._wait_rule["traj"][1])
         return clear, pair
 
+    # -- whole-arm avoidance: link spheres that push their own joints (vfik_link_avoid, vfik_set_avoid_rule) --
+    def link_avoid(self, q, points, first=0, count=None, mask=None, gain=1.0, d0=0.1, scale=None, out=None, channel=None):
+        """A joint command that pushes every arm's own link spheres away from the spheres they are close to, on the device
+        (include/vfik.h: vfik_link_avoid): asynchronous on the engine's stream.  ``q``, ``points``, ``first``, ``count`` and ``mask`` as
+        in :meth:`link_clearance`.  A pair closer than ``d0`` (centre distance less both radii) pushes with ``gain * scale[b] *
+        (1 - d / d0)`` along the line of centres; the pushes go through the Jacobian transpose of each sphere's point.  ``scale``:
+        (batch,) of the engine's dtype or None (all ones); 0 means the arm does not give way.  ``channel`` 3..5: the command is also
+        written into that mixer channel of the engine's ext buffer, which must exist (:meth:`set_ext_cmd` with a command, or
+        :meth:`set_avoid_rule`) -- whose mixer weight is the caller's; an existing ext buffer takes launches off the lean kernels.
+        Returns ``out``, (batch, n) of the engine's dtype: zeros for an arm without an active pair or with a NaN in q; made when not
+        given."""
+        import torch
+        B, ft = self.batch, self.io_dtype.name
+        if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 4:
+            raise ValueError("points must be (%d, n_rep, 4), got %s" % (B, tuple(points.shape)))
+        n_rep = points.shape[1]
+        count = n_rep - int(first) if count is None else int(count)
+        if out is None:
+            out = torch.empty((B, self.n), dtype=getattr(torch, ft), device="cuda:%d" % self.device)
+        self._check_dev((("q", q, (B, self.n), ft), ("points", points, None, ft), ("scale", scale, (B,), ft), ("out", out, (B, self.n), ft)))
+        mw = self._mask_words(mask, count)
+        self._chk(self.lib.vfik_link_avoid(self.h, C.c_void_p(_ptr(q)), C.c_void_p(_ptr(points)), n_rep, int(first), count,
+                                           None if mw is None else mw.ctypes.data, float(gain), float(d0), C.c_void_p(_ptr(scale)),
+                                           C.c_void_p(_ptr(out)), -1 if channel is None else int(channel)))
+        return out
+
+    def link_avoid_host(self, q, points, first=0, count=None, mask=None, gain=1.0, d0=0.1, scale=None):
+        """The host form (vfik_link_avoid_host; synchronous): NumPy arrays of doubles, rounded to the engine's dtype.  Returns float64
+        (batch, n) holding the engine-typed values."""
+        B = self.batch
+        qh = np.ascontiguousarray(q, dtype=np.float64)
+        if qh.shape != (B, self.n):
+            raise ValueError("q must be (%d, %d), got %s" % (B, self.n, qh.shape))
+        ph = np.ascontiguousarray(points, dtype=np.float64)
+        if ph.ndim != 3 or ph.shape[0] != B or ph.shape[2] != 4:
+            raise ValueError("points must be (%d, n_rep, 4), got %s" % (B, ph.shape))
+        sh = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        if sh is not None and sh.shape != (B,):
+            raise ValueError("scale must be (%d,), got %s" % (B, sh.shape))
+        n_rep = ph.shape[1]
+        count = n_rep - int(first) if count is None else int(count)
+        mw = self._mask_words(mask, count)
+        out = np.empty((B, self.n), dtype=np.float64)
+        self._chk(self.lib.vfik_link_avoid_host(self.h, qh.ctypes.data, ph.ctypes.data, n_rep, int(first), count,
+                                                None if mw is None else mw.ctypes.data, float(gain), float(d0),
+                                                None if sh is None else sh.ctypes.data, out.ctypes.data))
+        return out
+
+    def _drop_avoid_rule(self):
+        if self._avoid_rule is not None:
+            if self._avoid_rule["own"]:
+                self.lib.vfik_sync(self.h)   # an enqueued move may still read and write the arrays the engine uploaded
+            for p in self._avoid_rule["own"]:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            self._avoid_rule = None
+
+    def set_avoid_rule(self, gain, d0=None, channel=4, scale=None, mask=None, trace_checks=None, avoid_traj=None):
+        """Let every arm's link spheres push their own joints inside every timed move from now on (include/vfik.h:
+        vfik_set_avoid_rule); needs a coupling (:meth:`set_coupling`), and goes when the coupling goes.  In front of each block the
+        command of :meth:`link_avoid` against the partner's link spheres is written into mixer ``channel`` (3..5) and holds for the
+        block; the channel is zeroed when the move ends.  The channel's mixer weight is the caller's (``mix_w`` of the parameters,
+        :meth:`set_mixer_weights`); the parameters need ``F_MIXER``.  In a script channel 4 is the natural choice: weights 4 and 5 come
+        from the arm's own row there.  ``scale``: (batch,) of the engine's dtype -- a torch tensor on this device or a raw address, used
+        as it is, or a NumPy array / sequence, uploaded and kept alive.  ``mask``: own sphere i against partner sphere j, None: every
+        pair.  ``avoid_traj``: a device array (n_checks, batch, n) that receives every block's command; ``trace_checks=N`` instead:
+        the engine keeps it for N checks itself (:meth:`avoid_traj`).  ``gain=None`` switches the rule off, the default.  The rule
+        allocates the engine's ext buffer, which takes launches off the lean kernels, as any ext command does."""
+        self._chk(self.lib.vfik_set_avoid_rule(self.h, None))
+        self._drop_avoid_rule()
+        if gain is None:
+            return
+        if d0 is None:
+            raise ValueError("an avoid rule needs d0, the distance at which a pair begins to push")
+        if trace_checks is not None and avoid_traj is not None:
+            raise ValueError("give avoid_traj (a device array of the caller's) or trace_checks (a trace of the engine's), not both")
+        B, L, ft, own = self.batch, self.n_links, self.io_dtype, []
+        mw = self._mask_words(mask, L)
+        if mw is not None and not mw.any():
+            raise ValueError("a mask without a pair: the library reads all zeros as every pair")
+        try:
+            if scale is not None and not isinstance(scale, int) and not hasattr(scale, "data_ptr"):
+                sa = np.ascontiguousarray(scale, dtype=ft)
+                if sa.shape != (B,):
+                    raise ValueError("scale must be (%d,), got %s" % (B, sa.shape))
+                scale = self._upload(sa, own)
+            n_traj = None
+            if trace_checks is not None:
+                n_traj = int(trace_checks)
+                if n_traj < 1:
+                    raise ValueError("trace_checks must be at least 1, got %d" % n_traj)
+                avoid_traj = self._upload(np.full((n_traj, B, self.n), np.nan, dtype=ft), own)
+            self._check_dev((("scale", scale, (B,), ft.name), ("avoid_traj", avoid_traj, None, ft.name)))
+            r = _abi.AvoidRule()
+            r.gain, r.d0, r.channel = float(gain), float(d0), int(channel)
+            r.scale, r.avoid_traj = _ptr(scale), _ptr(avoid_traj)
+            for i in range(L if mw is not None else 0):
+                r.mask[i] = int(mw[i])
+            self._chk(self.lib.vfik_set_avoid_rule(self.h, C.byref(r)))
+        except Exception:
+            for p in own:
+                self.lib.vfik_dev_free(self.h, C.c_void_p(p))
+            raise
+        self._avoid_rule = {"own": own, "keep": (scale, avoid_traj), "n_traj": n_traj, "traj": avoid_traj if n_traj else None}
+
+    def avoid_traj(self):
+        """The engine's own trace of an avoid rule set with ``trace_checks=n_checks``: (n_checks, batch, n) of the engine's dtype -- row k
+        the command written in front of block k of the last timed move (NaN: a block that never ran).  Synchronises."""
+        if self._avoid_rule is None or self._avoid_rule["traj"] is None:
+            raise VfikError("no avoid rule with a trace of the engine's own: set_avoid_rule(..., trace_checks=n_checks)")
+        out = np.empty((self._avoid_rule["n_traj"], self.batch, self.n), dtype=self.io_dtype)
+        self.sync()
+        self.d2h(out, self._avoid_rule["traj"])
+        return out
+
     def _drop_coupling(self):
         self._drop_wait_rule()   # (the library switched the rule off with the coupling)
+        self._drop_avoid_rule()  # (likewise)
         if self._coupling is not None:
             if self._coupling["own"]:
                 self.lib.vfik_sync(self.h)   # an enqueued move may still read the arrays the engine uploaded

@@ -352,6 +352,31 @@ class ShardedEngine:
         import numpy as np
         return np.concatenate([e.waited() for e in self.engines], axis=0)
 
+    # -- whole-arm avoidance: per arm like the wait rule ----------------------------------------------------------------------------------
+    def link_avoid_host(self, q, points, first=0, count=None, mask=None, gain=1.0, d0=0.1, scale=None, global_rows=True):
+        """Engine.link_avoid_host over this rank's arms: ``q`` (rows, n), ``points`` (rows, n_rep, 4) and ``scale`` (rows,) are sharded
+        with the arms.  Returns this rank's commands (rows, n) in arm order."""
+        import numpy as np
+        qs = self._rows(np.asarray(q), "q", global_rows)
+        ps = self._rows(np.asarray(points), "points", global_rows)
+        ss = self._rows(None if scale is None else np.asarray(scale), "scale", global_rows)
+        outs = [e.link_avoid_host(qs[i], ps[i], first=first, count=count, mask=mask, gain=gain, d0=d0, scale=ss[i])
+                for i, e in enumerate(self.engines)]
+        return np.concatenate(outs, axis=0) if outs else np.zeros((0, 0))
+
+    def set_avoid_rule(self, gain, d0=None, channel=4, scale=None, mask=None, trace_checks=None, global_rows=True):
+        """Engine.set_avoid_rule on every engine of this rank (``gain=None``: off); ``scale`` (rows,) is a host array sharded with the
+        arms.  With ``trace_checks`` each engine keeps its own trace (:meth:`avoid_traj`)."""
+        import numpy as np
+        ss = self._rows(None if scale is None else np.asarray(scale), "scale", global_rows)
+        for i, e in enumerate(self.engines):
+            e.set_avoid_rule(gain, d0, channel=channel, scale=ss[i], mask=mask, trace_checks=trace_checks)
+
+    def avoid_traj(self):
+        """Engine.avoid_traj of this rank's arms: (n_checks, rows, n) in arm order."""
+        import numpy as np
+        return np.concatenate([e.avoid_traj() for e in self.engines], axis=1)
+
     def _checked_host(self, run, global_rows, kw):
         """``run(engine, part, keywords)`` -- an Engine.goto_host or Engine.follow_host on the part's rows -- for every part of this rank,
         each on a thread of its own, and the parts' results put together in arm order."""
