@@ -35,6 +35,8 @@ class Waiting:
         self.gate = None
         self.calls = 0
         self.waiting = None
+        self.per_cycle = False     # a script (tests/rules_reference.py): several calls per cycle, told apart as avoid_reference does
+        self.last_ext = None
 
     def __getattr__(self, name):
         return getattr(self.oc, name)
@@ -46,7 +48,11 @@ class Waiting:
         return groups
 
     def cycle_batch(self, chain, params, q, fields, nfields, **kw):
-        if self.calls % self.stride == 0:
+        # `calls` counts cycles: every call is one, or with `per_cycle` every call that brings a new ext_cmd array (`_run` makes one per cycle
+        # and hands the same one to every controller group)
+        new_cycle = not self.per_cycle or kw.get("ext_cmd") is None or kw["ext_cmd"] is not self.last_ext
+        self.last_ext = kw.get("ext_cmd")
+        if new_cycle and self.calls % self.stride == 0:
             k = self.calls // self.stride
             B, L = q.shape[0], len(self.spheres)
             if self.waiting is None:
@@ -64,7 +70,7 @@ class Waiting:
             self.waited = wait.astype(np.int32) if k == 0 else self.waited + wait
             self.gate[wait] = False
             self.waiting = wait
-        self.calls += 1
+        self.calls += int(new_cycle)
         if "active" in kw and kw["active"] is not None:
             kw["active"] = (np.asarray(kw["active"]) != 0) & ~self.waiting
         else:
