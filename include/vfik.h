@@ -14,6 +14,26 @@
  *     logs and ignores malformed bottles (scripts/vf:176-179,204-207,264-266).
  *   - per-arm numeric trouble (NaN, limit stop, ...) is reported in status[B] (VFIK_ST_*),
  *     never by failing the call (src/command_mixer.py:71-75 only prints).
+ *     Non-finite inputs stay inside their arm.  Three sentences hold for every cycle kernel, the rollout and the five timed moves, and the
+ *     suite holds every built kernel variant to them (tests/test_gpu_poison_isolation.py, tests/test_gpu_poison_moves.py):
+ *       C1, isolation.  Two runs whose inputs differ only in rows of a set P of arms give the arms outside P the same BITS in every
+ *           output row and in every piece of per-arm device state (as the next clean cycle's outputs show it); in a timed move also
+ *           arrived / reached, q_traj, dist_traj, diff, the waypoint reports and stalled, and pending[k] differs from the clean run's by
+ *           the change in the number of arms of P still under way.
+ *       C2, no laundering.  Where the C oracle (oracle/vfik_oracle.c, stepped on the host; a clamp is numpy.clip, which keeps a NaN) has a
+ *           NaN or an infinity in an element of a joint-command row (qdot_vf, qdot_null, qdot_out, the q_cmded form) or of the integrated
+ *           q (q_out, q_traj) of an arm of P, the library's element is not finite either; where both are finite they agree as for a clean
+ *           arm; VFIK_ST_NAN is set exactly where the oracle sets it.  A poisoned arm never arrives, is never reported at a waypoint and
+ *           counts in pending as an arm under way (until a stall rule declares it stalled: NaN is never progress).  pose, v6, qdist and
+ *           goal_dist of such an arm are specified only where both sides are finite: the kernels skip arithmetic on a chain's structural
+ *           zeros, where the oracle's general product has 0 * NaN.
+ *       C3, recovery.  No NaN is kept: once the inputs are finite again the arm's rows are the oracle's from the first cycle on, with no
+ *           vfik_reset_state -- the nullspace sign memory of a cycle without a usable Jacobian is left as it was --; io->track_error shows an
+ *           input of one cycle for three more calls (the command of three calls ago), io->obj_dist for none.
+ *     A goal or repeller row of vfik_move_fields whose FIRST element is finite and a later one NaN or infinite: a goal position or a repeller
+ *     row that is not finite makes the arm's commands NaN with VFIK_ST_NAN (a NaN is no short distance: the field's sum keeps it); a goal
+ *     ROTATION that is not finite is swallowed by the specification -- the angle fails vf's compare, the goal turns the arm nowhere, no NaN
+ *     reaches a command and VFIK_ST_NAN stays clear (tests/poison_reference.py: SWALLOWED, with the oracle's lines).
  *   - batch arrays are batch-major: q[B][n], qdot[B][n], pose[B][16], ...  Element type is the
  *     handle's io dtype (float for 32, double for 64).  Arithmetic is always float64.
  *   - one host thread per handle; one handle per device (shards are independent).
@@ -194,7 +214,15 @@ int vfik_reset_state(vfik_handle* h);
 
 /* Buffers of one control cycle.  NULL = not wanted / not supplied. */
 typedef struct vfik_io {
-    const void* q;            /* in  [B][n]   /qIn, /nullspace/qin, /debug/qin (vf:312, nullspace:162) */
+    const void* q;            /* in  [B][n]   /qIn, /nullspace/qin, /debug/qin (vf:312, nullspace:162).  Angles of up to about 1e5 rad: sine and
+                                 cosine keep their 1 - 2 ulp.  The kernels built for a chain's DH pattern (lean and publishing-lean launches
+                                 of the LWR, two LWRs in series and the 6-joint arm: vfik_dh_pattern) take the angle as it is and publish a
+                                 pose within 8 units of the 50-digit kinematics at |q| ~ 10, 1e3 and 1e5 (a unit: 2^-53 per joint).  Every
+                                 other kernel -- launches with per-arm options, chains off a pattern, the eight-lanes kernel -- ADDS a link's
+                                 DH angle offset to the joint angle in double: each joint with a nonzero offset carries up to
+                                 (|q| + |offset|) 2^-53 rad, 1.6e-11 in the pose at 1e5 rad (tests/test_gpu_far_angles.py holds both to their
+                                 bars).  Finite angles beyond 1e5 rad are outside the contract.  NaN and +-inf: the
+                                 arm's commands are NaN and VFIK_ST_NAN is set (C1 - C3 above). */
     const void* null_control; /* in  [B][4]   /nullspace/control (nullspace:169-173); NULL = zeros.  HONOURED ONLY where the
                                  nullspace is one-dimensional (7 joints at a regular pose: element 0 scales the unique
                                  basis vector, nullspace:110-117).  With nullity >= 2 -- every chain of 8+ joints, a

@@ -124,7 +124,9 @@ static void prim_eval(const vfik_field* f, const double F[12], double rot_slowdo
         const double* G = f->p; /* rows 0..2 of the 4x4 are a 3x4 */
         double d[3] = {G[3] - p[0], G[7] - p[1], G[11] - p[2]};
         double D = norm3(d);
-        if (D > EPS_LEN) for (int k = 0; k < 3; ++k) v[k] = d[k] / D;
+        /* (`!(D <= EPS_LEN)`, not `D > EPS_LEN`: a distance that is NaN -- a NaN in the goal's or the tool's position -- is no short distance.
+         * The pull is then NaN, the sum below is, and the arm's command is NaN with VFIK_ST_NAN: a broken goal is reported, not skipped.) */
+        if (!(D <= EPS_LEN)) for (int k = 0; k < 3; ++k) v[k] = d[k] / D;
         double r[3];
         double th = rot_log(F, G, r);
         if (th > EPS_LEN) for (int k = 0; k < 3; ++k) v[3 + k] = r[k] / th;
@@ -185,7 +187,9 @@ void vfo_field_eval(const vfik_field* f, int nf, const double F[12], double rot_
     }
     double nt = norm3(tot), nr = norm3(tot + 3);
     for (int k = 0; k < 3; ++k) {
-        vec6[k] = nt > EPS_LEN ? tot[k] / nt : 0.0;
+        /* (zero stays zero; a translational sum that is not finite stays not finite -- NaN is no short length: a goal position or a repeller
+         * row with a NaN is reported, VFIK_ST_NAN.  The rotational sum keeps `>`: a goal ROTATION that is not finite turns the arm nowhere.) */
+        vec6[k] = !(nt <= EPS_LEN) ? tot[k] / nt : 0.0;
         vec6[3 + k] = nr > EPS_LEN ? tot[3 + k] / nr : 0.0;
     }
 }
@@ -371,6 +375,11 @@ static void sym_jacobi(double* A, int n, double* V, double* w) {
 int vfo_nullspace_basis(const double* J, int n, double* lastvec, int* sig, double* basis) {
     double B[MAXJ * MAXJ], V[MAXJ * MAXJ], w[MAXJ];
     int order[MAXJ];
+    /* A Jacobian that is not finite (a NaN or infinite joint angle): numpy's svd raises "SVD did not converge" and the reference's process
+     * moves nothing in the null space that cycle -- no vector, sig and lastvec untouched.  (The solves below skip what a NaN fails to
+     * compare and would hand back finite numbers nobody computed: a nullspace row of an arm whose every other row is NaN.) */
+    for (int i = 0; i < 6 * n; ++i)
+        if (!isfinite(J[i])) return 0;
     vfo_restrict(J, n, B);
     for (int i = 0; i < n; ++i)
         for (int j = i + 1; j < n; ++j) B[i * n + j] = B[j * n + i] = 0.5 * (B[i * n + j] + B[j * n + i]);

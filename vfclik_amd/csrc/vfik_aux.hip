@@ -142,7 +142,10 @@ __global__ void __launch_bounds__(256) monitor_kernel(const T* pose, const T* fr
     const double c = 0.5 * (E[0] + E[4] + E[8] - 1.0);
     const double sn = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
     out[2 * t] = (T)sqrt(dx * dx + dy * dy + dz * dz);
-    out[2 * t + 1] = (T)(atan2_pos(sn, c) * 57.295779513082320877);
+    // (atan2_pos answers 0 for a pair that holds a NaN -- its compares fail and the quotient is taken for 0 / 0: a pose that is not finite has
+    // no angle, and a monitor that reported 0 degrees for it would call a poisoned arm aligned)
+    const double both = sn + c;
+    out[2 * t + 1] = (T)((both == both ? atan2_pos(sn, c) : both) * 57.295779513082320877);
 }
 
 // ------------------------------------------------------------------------------------------------

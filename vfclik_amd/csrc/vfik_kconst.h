@@ -91,6 +91,12 @@ template <> struct DhPattern<14, 1> {
     static constexpr bool BASE_I = true;
 };
 template <> struct DhPattern<6, 1> { static constexpr unsigned SWAP = 0x1Du, NONE = 0x20u, D0 = 0x16u, OFF0 = 0x27u, OFFPI = 0x18u; static constexpr bool BASE_I = true; };
+// A pattern whose LAST link keeps its frame (NONE) must give that link a z-offset (D0 clear): the last joint's angle reaches the position through
+// that offset alone (cycle_body: J_LAST_AXIAL; the eight-lanes kernel likewise) -- with d = 0 a NaN last angle would be a finite command again.
+template <int NJ> constexpr bool dh_last_axial_has_offset() {
+    return !((DhPattern<NJ, 1>::NONE >> (NJ - 1)) & 1u) || !((DhPattern<NJ, 1>::D0 >> (NJ - 1)) & 1u);
+}
+static_assert(dh_last_axial_has_offset<6>() && dh_last_axial_has_offset<7>() && dh_last_axial_has_offset<14>(), "DhPattern: an axial last link needs d != 0");
 // the pattern id of a chain with these masks (0: none built for it)
 inline int dh_pattern_of(int nj, unsigned swap, unsigned none, unsigned d0, unsigned off0, unsigned offpi, bool base_identity) {
     unsigned ps = 0, pn = 0, pd = 0, p0 = 0, ppi = 0;

@@ -561,7 +561,12 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
         Jm[i][0] = p[0]; Jm[i][1] = p[1]; Jm[i][2] = p[2];
         const double ci = PLAIN ? cs[i] : __builtin_fma(klc->dh[i].crev, cs[i], klc->dh[i].cprs);
         const double si = PLAIN ? sn[i] : __builtin_fma(klc->dh[i].crev, sn[i], klc->dh[i].sprs);
-        const double di = PLAIN ? klc->dh[i].d : __builtin_fma(klc->dh[i].qd, q[i], klc->dh[i].d);
+        // (A pattern chain's last link has a = 0 and alpha = 0: the last joint's angle reaches nothing but the x and y columns of the tool rotation,
+        // which the field reads behind compares that a NaN fails -- a NaN or infinite angle there came out as a finite command.  The general
+        // product has 0 * NaN in the position (vfik_oracle.c: vfo_jacobian); here the angle enters the link's offset with weight zero: d + 0 q
+        // is d for every finite q, one operation, and NaN otherwise -- position, Jacobian and command then are, as the oracle's.)
+        const bool J_LAST_AXIAL = PLAIN && i == NJ - 1 && ((DHP_NONE >> i) & 1u) && !((DHP_D0 >> i) & 1u);
+        const double di = PLAIN ? (J_LAST_AXIAL ? __builtin_fma(0.0, q[i], klc->dh[i].d) : klc->dh[i].d) : __builtin_fma(klc->dh[i].qd, q[i], klc->dh[i].d);
         const double ai = klc->dh[i].a, ca = klc->dh[i].ca, sa = klc->dh[i].sa;
         // DH pattern of the chain, joint by joint, as compile-time masks (DHP): joints whose link has a = 0 and alpha = +-pi/2 (the
         // rotation about x is a swap with signs: 6 instead of 12 operations, no a-term), a = 0 and alpha = 0 (no rotation at all), d = 0
@@ -1631,8 +1636,13 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             }
             put_rows(a.qdist, KNJ(), [&](int i) { return dc[i]; });
         }
-        if (a.goal_dist)  // /dmonitor/distOut entry of object 0: xyz distance, rotation angle in DEGREES (monitor_distance:76-84,161-172)
-            put_rows(a.goal_dist, std::integral_constant<int, 2>(), [&](int i) { return i == 0 ? gdist[0] : gdist[1] * 57.295779513082320877; });
+        if (a.goal_dist) {  // /dmonitor/distOut entry of object 0: xyz distance, rotation angle in DEGREES (monitor_distance:76-84,161-172)
+            // (rot_axis_angle reports pi where no lane of the wave needs the angle, also for a pose that is not finite: a NaN pose has a NaN
+            // angle -- a finite one was progress to the stall rule, which then took a poisoned arm out one check late)
+            const double ps = Rt[0] + Rt[4] + Rt[8];
+            const double ang = ps == ps ? gdist[1] : ps;
+            put_rows(a.goal_dist, std::integral_constant<int, 2>(), [&](int i) { return i == 0 ? gdist[0] : ang * 57.295779513082320877; });
+        }
     }
     if (ROLL || a.q_out) {  // joint_sim: integrate the commanded velocity; optionally stay inside the joint limits
 #pragma unroll
@@ -1641,7 +1651,10 @@ cycle_body(const typename std::conditional<SmallArgs<LEAN, ROLL, FASTF, MIXO>::v
             double lo[NJ], hi[NJ];
             limits_of(lo, hi);
 #pragma unroll
-            for (int i = 0; i < NJ; ++i) q[i] = fmin(fmax(q[i], lo[i]), hi[i]);
+            for (int i = 0; i < NJ; ++i) {   // (fmax / fmin return the operand that is not NaN: a NaN q would come back as q_lo, a healthy arm -- np.clip keeps it)
+                const double c = fmin(fmax(q[i], lo[i]), hi[i]);
+                q[i] = q[i] == q[i] ? c : q[i];
+            }
         }
     }
     }  // cycles of this launch
@@ -1844,7 +1857,8 @@ __device__ __forceinline__ void cycle_sub8_body(const KArgs& a) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) { xn[r] = __builtin_fma(ci, R[3 * r], xn[r]); ym[r] = __builtin_fma(ci, R[3 * r + 1], -ym[r]); }
         if (!J_D0) {
-            const double di = kc->dh[i].d;
+            // (the last, axial joint: its angle enters the offset with weight zero, so that a NaN angle is a NaN position -- see cycle_body)
+            const double di = (J_NONE && i == NJ - 1) ? __builtin_fma(0.0, q[i], kc->dh[i].d) : kc->dh[i].d;
 #pragma unroll
             for (int r = 0; r < 3; ++r) p[r] = __builtin_fma(di, R[3 * r + 2], p[r]);
         }
