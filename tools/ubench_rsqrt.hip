@@ -1,21 +1,26 @@
-// ubench_rsqrt.hip -- the relative error of v_rsq_f64 alone and after ONE Newton step (the sequence of vfik_kernel.hip's rsqrt_1nr /
-// rsqrt_1nr_pos, restated here instruction for instruction), in units of u = 2^-53, against 1 / sqrtl(x) in the host's long double
+// ubench_rsqrt.hip -- the relative error of v_rsq_f64 alone and after ONE Newton step (vfclik_amd/csrc/vfik_device.h's own rsqrt_1nr_pos,
+// through the include vfik_aux.hip uses: nothing is restated here; rsqrt_1nr is the same sequence behind a clamp at 1e-300, and
+// tests/test_gpu_blocks.py holds the two to the same bits), in units of u = 2^-53, against 1 / sqrtl(x) in the host's long double
 // (64-bit mantissa): 2^20 arguments, mantissas from a fixed linear congruential sequence, exponents cycling over 1e-20 ... 1e4 --
 // the squared distances |o - p|^2 a decay repeller can see between the 1e-10 floor tests and a workspace of 100 m.
 // Prints the largest and the root-mean-square error of both; the figures quoted in DESIGN 6.2 come from this program on an MI355X.
-#include <hip/hip_runtime.h>
+#include "../vfclik_amd/csrc/vfik_kernel.h"
+
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
+namespace vfik {
+namespace {
+#include "../vfclik_amd/csrc/vfik_device.h"
+}  // namespace
+}  // namespace vfik
+
 __global__ void __launch_bounds__(256) k(const double* x, double* raw, double* one, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double v = x[i];
-    const double y = __builtin_amdgcn_rsq(v);
-    const double e = __builtin_fma(-(v * y), y, 1.0);
-    raw[i] = y;
-    one[i] = __builtin_fma(0.5 * y, e, y);
+    raw[i] = __builtin_amdgcn_rsq(x[i]);
+    one[i] = vfik::rsqrt_1nr_pos(x[i]);
 }
 
 int main() {

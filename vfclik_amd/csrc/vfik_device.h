@@ -49,7 +49,9 @@ __device__ __forceinline__ void flange_rotation(const double* Rt, const double* 
 }
 
 // 1/sqrt(x) from ONE Newton step on v_rsq_f64 (5 instructions): the decay repellers' 1 / D, which is raised to the decay order (up to 127).
-// The step's error is measured directly by tools/ubench_rsqrt.hip (figures in DESIGN 6.2).  An error COMMON to the slots of one order is
+// The step's error is measured directly by tools/ubench_rsqrt.hip (figures in DESIGN 6.2) and held by tests/test_gpu_blocks.py to
+// 1.5 e0^2 + 2 u of the 50-digit value, e0 the worst error of v_rsq_f64 itself on the same arguments (profiles/device_blocks_accuracy.txt:
+// e0 = 4.9e-8 over 1e-300 ... 1e300, the step leaves 32 u; rsqrt_1nr and rsqrt_1nr_pos agree bit for bit from 1e-300 up).  An error COMMON to the slots of one order is
 // a common factor of their terms and leaves a normalised sum unchanged but for the goal's share; tests/test_gpu_field_edges.py bounds
 // what the twist sees of it.  sqrt_rsqrt's two Goldschmidt steps (10 instructions) stay where the value itself is published.
 // x = 0 gives a large finite value.
@@ -65,9 +67,11 @@ __device__ __forceinline__ double rsqrt_1nr_pos(double x) {   // ... for x > 0 k
     return __builtin_fma(0.5 * y, e, y);
 }
 
-// 1/x from ONE Newton step on v_rcp_f64: the LDL^T pivots of the IK's normal matrix.  Measured on gfx950 (profiles/conditioning_accuracy.txt),
-// not assumed: the raw v_rcp_f64 is off by ~5e-9 relative (with it alone the joint velocities miss the reference by 5e7 cond u), so one step
-// leaves ~3e-17, under the rounding of its own last fma -- against the 50-digit reference (tests/test_gpu_conditioning.py) the joint
+// 1/x from ONE Newton step on v_rcp_f64: the LDL^T pivots of the IK's normal matrix.  Measured on gfx950, not assumed: over all mantissas
+// (tests/test_gpu_blocks.py, profiles/device_blocks_accuracy.txt) the raw v_rcp_f64 is off by up to 4.2e-8 relative, so one step leaves up to
+// e0^2 = 1.8e-15 = 16 u -- NOT under the rounding of its own last fma, as this comment said while it took the seed's error for ~5e-9 (the
+// figure of the conditioning sweep's build without the step: the joint velocities then miss the reference by 5e7 cond u); the test holds it
+// to e0^2 + 1.5 u with e0 measured on the same arguments.  Against the 50-digit reference (tests/test_gpu_conditioning.py) the joint
 // velocities are within 2.5 cond u at lambda = 0.1 and 2.1 cond u at lambda = 1e-2 and 1e-3 (cond up to 1.4e7, singular poses included),
 // cond = (sigma_1^2 + lambda^2) / (sigma_6^2 + lambda^2), u = 2^-53; rcp_nr's second step gives 2.1 at every lambda, the C oracle's
 // plain-double solve 0.5 - 1.5.  No bound on lambda or on cond enters: the test holds every lambda >= 0 it runs to 8 cond u.
@@ -105,7 +109,10 @@ __device__ __forceinline__ double mul_unfused(double x, double w) {
 }
 
 // sin and cos: Cody-Waite reduction by pi/2 in three parts, then the classic minimax kernels on
-// [-pi/4, pi/4] (coefficients of fdlibm's __kernel_sin / __kernel_cos), < 1 ulp for |x| up to ~1e5 rad.
+// [-pi/4, pi/4] (coefficients of fdlibm's __kernel_sin / __kernel_cos).  Under 1.5 u ABSOLUTE (u = 2^-53) for |x| up to 1e5 rad, not "< 1 ulp":
+// fdlibm's kernels keep that only when given the reduction's tail, which is dropped here, so the reduction's last rounding (0.5 u) adds to
+// theirs; measured 1.52 u, held to 2 u by tests/test_gpu_blocks.py.  Relative: 0.5 ulp at the doubles nearest to k pi/2 (the three-part
+// reduction keeps the small remainder exact), up to 1.6 ulp elsewhere (profiles/device_blocks_accuracy.txt).
 // Joint angles live inside their limits (a few radians).  (The eight-lanes kernel's: not instantiated for the longer chains.)
 [[maybe_unused]] __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
     const double k = __builtin_rint(x * 6.36619772367581382433e-01);
@@ -191,8 +198,10 @@ __device__ __forceinline__ void sincos_fast_n(const double* x, double* s, double
 // with (S_k, C_k) = (sin, cos)(k pi/32) read from the wave's LDS copy of the table (one 16-byte read per angle, index
 // k mod 64) and Taylor polynomials that are exact to the last bit on so short an interval (r^9/9! < 1e-16 r,
 // r^10/10! < 3e-20).  23 instructions an angle against 33 for the pi/2 reduction above, whose minimax kernels need
-// six coefficients each and a sign / swap selection by quadrant; ~2 ulp (the table entries are rounded).  pi/32 is
-// split into a 33-bit head, so that k * head is exact for |x| < 1e5 rad, and a tail.
+// six coefficients each and a sign / swap selection by quadrant; ~2 u ABSOLUTE, u = 2^-53 (the table entries are rounded; measured
+// 1.8 u, held to 2.5 u by tests/test_gpu_blocks.py) and NO relative bound near the zeros of sin and cos, where the result is the difference
+// of two rounded products (1e15 ulp at the double nearest to a zero; sincos_fast keeps 0.5 ulp there).  pi/32 is
+// split into a 33-bit head, so that k * head is exact for |x| < 1e5 rad (asserted in tests/test_blocks_reference.py), and a tail.
 template <int N>
 __device__ __forceinline__ void sincos_tab_n(const double* x, const char* tab, double* s, double* c) {
     typedef double d2 __attribute__((ext_vector_type(2)));
