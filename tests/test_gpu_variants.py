@@ -79,9 +79,10 @@ def _tool(i=0):
 # ---- the recipe: template arguments -> configuration ----------------------------------------------------------------
 class Recipe:
     """What a variant needs.  `key` is the handle's configuration (variants with the same key share one handle); the rest is what the
-    launch asks for: outputs, the eight-lanes cap, per-arm limits, a rollout."""
+    launch asks for: outputs, the eight-lanes cap, per-arm limits, a rollout.  `b_small` / `b_big`: the batch of a one-wave-per-SIMD and of
+    a two-waves variant (tests/test_gpu_extents.py also runs a batch whose last wave is full)."""
 
-    def __init__(self, v):
+    def __init__(self, v, b_small=B_SMALL, b_big=B_BIG):
         a = v.args
         sub8 = v.kernel.startswith("cycle_sub8")
         self.v = v
@@ -101,7 +102,7 @@ class Recipe:
         self.fun = a.get("FUN", False)
         self.uni = a.get("UNI", False)
         self.big = a.get("WAVES", 1) == 2
-        self.B = B_BIG if self.big else B_SMALL
+        self.B = b_big if self.big else b_small
         lean = 3 if sub8 else a["LEAN"]
         self.roll = a.get("ROLL", False) or lean == 2
         self.cap = self.B if sub8 else 0
